@@ -2,7 +2,7 @@
 """Headline benchmark: SMTP pre-training steps of the Graph Eulerian Transformer on synthetic
 Eulerian-token batches (BASELINE.json: graph-tokens/sec + SMTP loss, PCQM4M-v2 base model).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,14 @@ One step = forward + backward (+ bucketed RCCL all-reduce overlapped on a side s
 clip/AdamW over one batch of B=256 x S=32 x F=13 tokens per GPU, inputs resident in HBM.  Prints ONE JSON
 line on rank 0.  `value` counts un-padded graph tokens (reference metric definition,
 src/conf/stats_configs.py:69-76) summed over all ranks.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else, outside the
+timed steps: the other token layouts, the batch hand-over, the in-step kernel probes and the dominant kernels'
+roofline, the per-sample kernels, the CPU baseline with its loss parity (single process) and the exchange
+diagnostics (N > 1).  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).  A dumping run
+takes the engine's reproducible mode from its first step on: the same kernels as the default, with the one unordered sum of the
+pre-train gradient path - the RMSNorm weight gradients - added in block order, so that two runs of a pre-train workload with the
+same arguments write bit-identical outputs.  Plain runs, the ones to time, keep the default.
 """
 import argparse
 import importlib
@@ -227,13 +235,42 @@ KERNEL_NAMES = {
 }
 
 
+DUMP_SAMPLE = 1 << 22      # --dump-outputs: elements kept of a parameter-sized array (16 MB as float32)
+
+
+def dump_outputs(out_dir, loss, grad_norm, engine, task_logits=None):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy - `loss` (the loss the step returned),
+    `grad_norm` (the global gradient norm AdamW clipped with), `task_logits` (fine-tune workloads), `master_weights` (the fp32
+    master weights after the update) and `grads` (the step's bf16 gradient).  The last two are kept whole up to DUMP_SAMPLE
+    elements, else at fixed positions: the sorted unique draws of numpy.random.default_rng(0).integers(0, n, DUMP_SAMPLE).
+    Under 40 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = engine.master.numel()
+    idx = None if n <= DUMP_SAMPLE else torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))).to(engine.master.device)
+    arrays = {"loss": loss.detach().float().reshape(-1), "grad_norm": torch.as_tensor(grad_norm).detach().float().reshape(-1)}
+    if task_logits is not None:
+        arrays["task_logits"] = task_logits.detach().float()
+    for name, flat in (("master_weights", engine.master), ("grads", engine.grad_bf16)):
+        arrays[name] = (flat if idx is None else flat[idx]).float()
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="pcqm4m-v2-pretrain-base", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and its loss parity")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line's steps, measure and check everything else (other token layouts, batch hand-over, "
+                         "in-step kernel probes, roofline, per-sample kernels, CPU baseline and loss parity; N > 1: exchange-free step "
+                         "time, replica checksum, rank devices), all outside the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as float32 DIR/<name>.npy (dump_outputs); the "
+                         "steps run in the engine's reproducible mode (same kernels, block-ordered RMSNorm weight-gradient sums), so that "
+                         "pre-train runs with the same arguments write bit-identical outputs; time plain runs")
     ap.add_argument("--batches", type=int, default=4,
                     help="distinct synthetic batches the steps rotate through (pre-train workloads; every batch has its own lengths, so the "
                          "var-len row count - and with it the launch shapes - changes from step to step like in a real epoch; 1 = the "
@@ -280,6 +317,12 @@ def main():
     synth = importlib.import_module("graph-gpt_amd.synth")
     modeling = importlib.import_module("graph-gpt_amd.modeling")
     training = importlib.import_module("graph-gpt_amd.training")
+    if a.dump_outputs:
+        # outputs to compare run against run: the engine's reproducible mode from the first step on (include/gget.h, gget_debug_set key 4 =
+        # GGET_DETERMINISTIC=1) - the same kernel selection as the default; the RMSNorm weight gradients, otherwise added with fp32 atomics
+        # in whatever order the blocks finish, are summed in block order, so two pre-train runs compute bit-identical steps
+        L_ = importlib.import_module("graph-gpt_amd._lib")
+        L_.check(L_.load().gget_debug_set(4, 1))
 
     kind, size, B, S, F, V = WORKLOADS[a.workload]
     if a.seq_len:
@@ -334,6 +377,8 @@ def main():
     # as the reference computes it.  Packed batches (3-D masks) have no padding to skip.
     layout = a.layout if kind != "pt-packed" else "padded"
 
+    last_logits = [None]      # task logits of the last fine-tune step (--dump-outputs)
+
     def make_step(lay):
         datas = [dict(d_, num_tokens=r_) if lay == "varlen-count" else d_ for d_, r_ in zip(devs, reals)]
 
@@ -342,7 +387,10 @@ def main():
             if lay == "padded":
                 os.environ["GGET_VARLEN"] = "0"
             try:
-                return training.batch_training(data, engine) if pt else training.ft_batch_training(data, engine)[0]
+                if pt:
+                    return training.batch_training(data, engine)
+                loss_, last_logits[0] = training.ft_batch_training(data, engine)
+                return loss_
             finally:
                 if lay == "padded":
                     del os.environ["GGET_VARLEN"]
@@ -352,7 +400,7 @@ def main():
 
     # eval-mode forward of the bench batch on the initial (seed 0) weights: the loss the oracle leg is compared with (`loss_parity`)
     gpu_eval_loss = None
-    if pt and kind == "pt":
+    if a.full and pt and kind == "pt":
         model.eval()
         with torch.no_grad():
             gpu_eval_loss = float(model(input_ids=dev["input_ids"], attention_mask=dev["attention_mask"], labels=dev["labels"]).head1_loss)
@@ -387,9 +435,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    loss_value = float(loss.item())
+    if a.dump_outputs and rank == 0:       # (before anything below runs more steps on these weights)
+        dump_outputs(a.dump_outputs, loss, engine.last_grad_norm, model._engine, last_logits[0])
     # the other token layouts, same batch, same K steps each (outside the reported time; single process only)
     layouts = None
-    if world == 1 and kind != "pt-packed":
+    if a.full and world == 1 and kind != "pt-packed":
         layouts = {layout: dt / a.steps * 1e3}
         for lay in ("varlen", "varlen-count", "padded"):
             if lay in layouts:
@@ -410,7 +461,7 @@ def main():
     # the compute queue: what TrainingPipeline's loop does) and (b) the reference's way, every tensor `.to(device)` at the top of the step
     # (training_utils.py:17-26).  `value` stays the device-resident figure the contract asks for; these two sit next to it.
     h2d = None
-    if world == 1 and kind != "pt-packed":
+    if a.full and world == 1 and kind != "pt-packed":
         host_t = [{k: torch.from_numpy(v) for k, v in b_.items() if k not in ("lengths", "segments")} for b_ in host_batches]
         run_on = (lambda d_: training.batch_training(d_, engine)) if pt else (lambda d_: training.ft_batch_training(d_, engine)[0])
 
@@ -447,7 +498,7 @@ def main():
     # side stream), max over ranks; exposed = reported step - that.  The replicas drift apart in these steps: they come last.
     dp_info = None
     replicas_identical = None
-    if world > 1:
+    if a.full and world > 1:
         # replicas must still be bit-identical after the timed steps (same init, averaged gradients, same update on every rank): a
         # 64-bit checksum of the fp32 master weights, min- and max-reduced over the ranks
         chk = model._engine.master.view(torch.int32).to(torch.int64).sum().reshape(1)
@@ -482,11 +533,14 @@ def main():
         dist.all_gather_object(allr, me)
         dp_info["rank_devices"] = allr
         dp_info["distinct_devices"] = len({(d_["device_index"], d_["pci_bus_id"], d_["uuid"]) for d_ in allr})
+    elif world > 1:      # (a plain run: the exchange arrangement the timed steps ran with, nothing measured beyond them)
+        dp_info = engine.describe_dp()
+        dp_info["menu_probe"] = menu_probe
     # the dominant kernels' launch durations INSIDE a step: three more (untimed) steps with HIP events around those launches, on the
     # stream they run on (single process only - the extra steps would otherwise need every rank)
     in_step = {}
     gemm_info = None
-    if world == 1:
+    if a.full and world == 1:
         eng_ = model._engine
         eng_.debug_probe(True)
         for _ in range(3):
@@ -513,7 +567,7 @@ def main():
                          "note": "executed rows (var-len layout: real tokens); HIP events around every launch, untimed extra steps"}
     timed = [(a.warmup + i) % nb for i in range(a.steps)]        # batch index of every timed step
     real_per_step = sum(reals[j] for j in timed) / a.steps           # real tokens of this rank per timed step (mean over the rotation)
-    stats = torch.tensor([dt, float(real_per_step), float(loss.item())], dtype=torch.float64, device="cuda")
+    stats = torch.tensor([dt, float(real_per_step), loss_value], dtype=torch.float64, device="cuda")
     if world > 1:
         mx = stats.clone()
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
@@ -521,13 +575,13 @@ def main():
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
         dt, tot_real, mean_loss = float(mx[0]), float(sm[1]), float(sm[2]) / world
     else:
-        tot_real, mean_loss = float(real_per_step), float(loss.item())
+        tot_real, mean_loss = float(real_per_step), loss_value
 
     if rank == 0:
         M, Lm = model._engine.head_counts() if pt else (0, 0)       # (of the last forward)
         ran_varlen, t_rows, mismatch = model._engine.varlen_status()
         assert not mismatch, "the batch's real-token count handed to the engine disagrees with its attention mask"
-        if kind == "pt" and world == 1:                             # (single process: the last forward was a probe step on batch 0)
+        if a.full and kind == "pt" and world == 1:                  # (single process: the last forward was a probe step on batch 0)
             lab0 = host_batches[0]["labels"] != -100
             assert (M, Lm) == (int(lab0.any(-1).sum()), int(lab0.sum())), "head counts of batch 0 differ from its labels"
         if ran_varlen:
@@ -548,28 +602,30 @@ def main():
         fexec = sum(batch_flops(j, True) for j in timed) / a.steps       # what the engine executed (mean over the timed steps)
         ms = dt / a.steps * 1e3
         step_tflops = fstep / (ms * 1e-3) / 1e12
-        kt = time_kernels(spec, t_rows)
-        L_ = spec.num_layers
-        share = lambda fl_per_layer: round(100.0 * fl_per_layer * L_ / fstep, 1)
-        # the dominant kernel = the launch that takes the largest share of the step's TIME (each of the three runs once per
-        # layer): with the GEGLU fused into the gate|up GEMM that is the grouped weight-gradient launch (~20 % of a C1 step)
-        c1_shape = B * S == 8192 and spec.hidden_size == 768
+        roofline = None
+        if a.full:
+            kt = time_kernels(spec, t_rows)
+            L_ = spec.num_layers
+            share = lambda fl_per_layer: round(100.0 * fl_per_layer * L_ / fstep, 1)
+            # the dominant kernel = the launch that takes the largest share of the step's TIME (each of the three runs once per
+            # layer): with the GEGLU fused into the gate|up GEMM that is the grouped weight-gradient launch (~20 % of a C1 step)
+            c1_shape = B * S == 8192 and spec.hidden_size == 768
 
-        def entry(k):
-            fl, alone = kt[k]
-            kms = in_step.get(k, alone)      # inside the step when the probe covers the kernel, else the stand-alone loop
-            tf = fl / (kms * 1e-3) / 1e12
-            return {"kernel": KERNEL_NAMES[k], "step_flops_pct": share(fl), "step_time_pct": round(100.0 * kms * L_ / ms, 1),
-                    "avg_launch_ms": kms, "timed": "HIP events around the launch inside the step" if k in in_step else "stand-alone loop",
-                    "avg_launch_ms_standalone": alone, "achieved": tf, "frac": tf / PEAK_BF16_TFLOPS,
-                    "traffic": pmc_traffic(k, t_rows) if c1_shape else None}
-        order = sorted(kt, key=lambda k: -in_step.get(k, kt[k][1]))
-        dom = entry(order[0])
-        roofline = {"bound": "mfma", "kernel": dom["kernel"] + f" ({dom['step_time_pct']}% of the step's time, {dom['step_flops_pct']}% of its FLOPs)",
-                    "achieved": dom["achieved"], "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": dom["frac"],
-                    "traffic": dom["traffic"], "avg_launch_ms": dom["avg_launch_ms"], "timed": dom["timed"],
-                    "avg_launch_ms_standalone": dom["avg_launch_ms_standalone"],
-                    "other_kernels": [entry(k) for k in order[1:]]}
+            def entry(k):
+                fl, alone = kt[k]
+                kms = in_step.get(k, alone)      # inside the step when the probe covers the kernel, else the stand-alone loop
+                tf = fl / (kms * 1e-3) / 1e12
+                return {"kernel": KERNEL_NAMES[k], "step_flops_pct": share(fl), "step_time_pct": round(100.0 * kms * L_ / ms, 1),
+                        "avg_launch_ms": kms, "timed": "HIP events around the launch inside the step" if k in in_step else "stand-alone loop",
+                        "avg_launch_ms_standalone": alone, "achieved": tf, "frac": tf / PEAK_BF16_TFLOPS,
+                        "traffic": pmc_traffic(k, t_rows) if c1_shape else None}
+            order = sorted(kt, key=lambda k: -in_step.get(k, kt[k][1]))
+            dom = entry(order[0])
+            roofline = {"bound": "mfma", "kernel": dom["kernel"] + f" ({dom['step_time_pct']}% of the step's time, {dom['step_flops_pct']}% of its FLOPs)",
+                        "achieved": dom["achieved"], "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": dom["frac"],
+                        "traffic": dom["traffic"], "avg_launch_ms": dom["avg_launch_ms"], "timed": dom["timed"],
+                        "avg_launch_ms_standalone": dom["avg_launch_ms_standalone"],
+                        "other_kernels": [entry(k) for k in order[1:]]}
         names = {"pt": "SMTP loss", "pt-packed": "SMTP loss", "ft": "task loss", "ft-long": "task loss"}
         out = {
             "metric": f"graph-tokens/sec (un-padded Eulerian tokens, whole job) + {names[kind]}, "
@@ -581,6 +637,7 @@ def main():
                        f"({spec.num_params() / 1e6:.1f}M params)", "per_gpu_batch": B, "global_batch": B * world,
                        "seq_len": S, "stacked_feat": F, "vocab": V, "parallelism": f"dp{world}",
                        "step": "fwd+bwd+allreduce+clip+AdamW", "attention_dropout": cfg.attention_dropout,
+                       "reproducible_mode": bool(a.dump_outputs),
                        "token_layout": ("varlen (real tokens compacted on the device; same batch, loss and gradients as the padded grid); "
                                         + ("the step is called like the reference's - device tensors, no token count: the engine counts the mask"
                                            if layout == "varlen" else "token count passed by the caller")) if ran_varlen else "padded",
@@ -599,16 +656,18 @@ def main():
                           "rows_per_batch": [(r_ + 63) // 64 * 64 if ran_varlen else B * S for r_ in reals],
                           "reference_grid": {"flops_per_step": fstep, "equivalent_tflops_per_gpu": step_tflops,
                                              "equivalent_frac_of_peak": step_tflops / PEAK_BF16_TFLOPS}},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if gemm_info is not None:
             out["step_mfma"]["gemms"] = gemm_info
-        if world == 1 and kind == "pt":
+        if a.full and world == 1 and kind == "pt":
             psk = time_per_sample_kernels(spec, B, S, host_batches[0].get("lengths"), cfg.attention_dropout)
             if psk is not None:
                 out["per_sample_kernels"] = psk
         if dp_info is not None:
-            dp_info["exposed_comm_ms"] = ms - dp_info["ms_per_step_without_exchange"]
+            if "ms_per_step_without_exchange" in dp_info:
+                dp_info["exposed_comm_ms"] = ms - dp_info["ms_per_step_without_exchange"]
             out["dp"] = dp_info
         if h2d is not None:
             h2d["vs_device_resident"] = h2d["h2d_inclusive_ms_per_step"] / ms
@@ -619,7 +678,7 @@ def main():
                               "note": "varlen = reference-shaped call (device tensors only; the engine sums the mask and reads 4 bytes back), "
                                       "varlen-count = caller passes data['num_tokens'], padded = every row of the [B,S] grid; same batch, same "
                                       "K steps each, outside the reported time"}
-        if world == 1 and not a.no_cpu_baseline and kind == "pt":
+        if a.full and world == 1 and not a.no_cpu_baseline and kind == "pt":
             state = weights.make_state_dict(spec, seed=0)
             out["cpu_baseline"], oracle_loss = cpu_baseline(spec, state, B, S, F, V, 1234, min(os.cpu_count() or 1, 32), tail=tail)
             if gpu_eval_loss is not None:
@@ -627,7 +686,7 @@ def main():
                                       "rel": abs(gpu_eval_loss - oracle_loss) / abs(oracle_loss),
                                       "what": "SMTP loss of the bench batch (seed 1234) on the initial weights (seed 0, rounded to bf16), "
                                               "eval mode: HIP engine forward vs the CPU oracle's forward"}
-        elif world == 1 and not a.no_cpu_baseline:
+        elif a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = None   # the CPU port is timed on the headline workload only
         print(json.dumps(out), flush=True)
     if world > 1:

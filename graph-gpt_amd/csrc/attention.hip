@@ -3304,12 +3304,23 @@ int k_attn_oproj_bwd(const void* dxn, const void* x_mid, const void* nw, const f
                      void* dattn_long, const int32_t* long_list) {
   *taken = 0;
   // S <= 32, or - var-len layout, with room for the long samples' dattn rows - S <= 64: every sample by its own row count
-  if (B == 0 || S == 0 || S > 64 || (S > 32 && (!row_base || !dattn_long || !attn_by_sample_rows())) || !attn_oproj_enabled() ||
-      k_get_deterministic())
+  if (B == 0 || S == 0 || S > 64 || (S > 32 && (!row_base || !dattn_long || !attn_by_sample_rows())) || !attn_oproj_enabled())
     return 0;
   if (H != 2 && H != 4 && H != 8 && H != 12) return 0;
   GGET_REQUIRE(!row_base || key_len, "attention: the var-len token layout needs key_len");
   if (copies < 1) copies = 1;
+  // Reproducible mode: the kernel's norm-weight gradient goes to one zeroed row per sample instead of the shared replicas (copies = B:
+  // block b owns row b, and its at most two adds onto zero are exact in either order); the rows are then summed in block order
+  float* part = nullptr;
+  float* dw_out = dw_accum;
+  if (k_get_deterministic()) {
+    const int d = H * 64;
+    if (int e = k_det_scratch((size_t)(B + (B + 63) / 64) * d, &part)) return e;
+    GGET_HIP_CHECK(hipMemsetAsync(part, 0, (size_t)B * d * sizeof(float), st));
+    dw_accum = part;
+    copies = B;
+    copy_stride = (uint64_t)d;
+  }
   const Rope R{cos_tab, sin_tab, position_ids, S};     // rotation of dq, dk back to the un-rotated projections (q, k in memory are rotated)
   const Drop D = make_drop(dropout_p, dropout_seed);
   int rc = 0;
@@ -3320,6 +3331,8 @@ int k_attn_oproj_bwd(const void* dxn, const void* x_mid, const void* nw, const f
 #undef GGET_AOB
   if (rc) return rc;
   *taken = 1;
+  if (part)
+    if (int e = k_ordered_colsum(part, B, H * 64, dw_out, st)) return e;
   if (S > 32) {     // the attention backward of the 33 .. 64-row samples, from the dattn rows the kernel above wrote for them
     hipLaunchKernelGGL(attn_bwd_long_kernel, dim3(1, H, long_list ? std::min(B, kLongGrid) : B), dim3(128), 0, st, (const bf16_t*)qkv, (const bf16_t*)dattn_long,
                        lse, key_len, (bf16_t*)dqkv, B, S, H, causal, R, D, row_base, long_list);

@@ -46,6 +46,11 @@ void k_set_deterministic(int on);   // reproducible summation order of the RMSNo
 void k_set_rms_wide(int on);   // 1 (default): short RMSNorm backward launches run one 16-wave block per CU (kernels.hip rmsnorm_bwd_kernel)
 void k_set_ce_parts(int on);    // 1 (default): ce_rows_kernel leaves one partial loss sum per block where the caller has the slots (no same-address atomics)
 int k_get_deterministic();
+// reproducible mode: the scratch of the block-ordered weight-gradient sums (grown on demand; its users run in stream order)
+int k_det_scratch(size_t floats, float** out);
+// dst[j] += part[0][j] + part[1][j] + ... + part[nblk - 1][j] in a fixed order (two launches); part holds nblk rows of d floats followed by
+// room for ceil(nblk / 64) rows of segment sums
+int k_ordered_colsum(float* part, int nblk, int d, float* dst, hipStream_t st);
 int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
                   float* dw_accum, int T, int d, hipStream_t st, int copies = 1, uint64_t copy_stride = 0);
 int k_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H,

@@ -2254,14 +2254,8 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
   // Reproducible mode: the per-block partials of the weight gradient go to a scratch matrix and are summed in block order (the
   // fp32 atomics into the replicated accumulators are the one unordered sum of the pre-train gradient path: DESIGN.md section 5).
   float* part = nullptr;
-  if (g_deterministic) {
-    const size_t need = (size_t)(4096 + 64) * d * sizeof(float);   // per-block partials [4096][d] + segment sums [64][d]
-    if (g_det_bytes < need) {
-      if (g_det_scratch) GGET_HIP_CHECK(hipFree(g_det_scratch));
-      GGET_HIP_CHECK(hipMalloc(&g_det_scratch, need));
-      g_det_bytes = need;
-    }
-    part = g_det_scratch;
+  if (g_deterministic) {     // per-block partials [4096][d] + segment sums [64][d]
+    if (int e = k_det_scratch((size_t)(4096 + 64) * d, &part)) return e;
   }
   // short launches (<= 4 rows per wave of a 16-wave block per CU): the one-block-per-CU form (kernel comment); GGET_RMS_WIDE=0 / gget_debug_set(13, 0)
   // = the 4-wave blocks everywhere
@@ -2289,18 +2283,34 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
   else
     hipLaunchKernelGGL(rmsnorm_bwd_kernel<4>, dim3(grid), dim3(kBlock), 4 * d * sizeof(float), st, (const bf16_t*)dy,
                        (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, dw_accum, T, d, copies, copy_stride, part);
-  if (part) {
-    constexpr int kPer = 64;
-    const int nseg = (wgrid + kPer - 1) / kPer;
-    float* seg = part + (size_t)4096 * d;
-    hipLaunchKernelGGL(ordered_colsum_kernel, dim3((d + 63) / 64, nseg), dim3(kBlock), 0, st, part, wgrid, d, kPer, seg, 0);
-    hipLaunchKernelGGL(ordered_colsum_kernel, dim3((d + 63) / 64, 1), dim3(kBlock), 0, st, seg, nseg, d, nseg, dw_accum, 1);
-  }
   GGET_LAUNCH_CHECK();
+  if (part) return k_ordered_colsum(part, wgrid, d, dw_accum, st);
   return 0;
 }
 
 void k_set_deterministic(int on) { g_deterministic = on; }
+
+int k_det_scratch(size_t floats, float** out) {
+  if (g_det_bytes < floats * sizeof(float)) {
+    if (g_det_scratch) GGET_HIP_CHECK(hipFree(g_det_scratch));
+    g_det_scratch = nullptr;
+    g_det_bytes = 0;
+    GGET_HIP_CHECK(hipMalloc(&g_det_scratch, floats * sizeof(float)));
+    g_det_bytes = floats * sizeof(float);
+  }
+  *out = g_det_scratch;
+  return 0;
+}
+
+int k_ordered_colsum(float* part, int nblk, int d, float* dst, hipStream_t st) {
+  constexpr int kPer = 64;
+  const int nseg = (nblk + kPer - 1) / kPer;
+  float* seg = part + (size_t)nblk * d;
+  hipLaunchKernelGGL(ordered_colsum_kernel, dim3((d + 63) / 64, nseg), dim3(kBlock), 0, st, part, nblk, d, kPer, seg, 0);
+  hipLaunchKernelGGL(ordered_colsum_kernel, dim3((d + 63) / 64, 1), dim3(kBlock), 0, st, seg, nseg, d, nseg, dst, 1);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
 void k_set_rms_wide(int on) { g_rms_bwd_wide = on; }
 void k_set_ce_parts(int on) { g_ce_parts = on; }
 int k_get_deterministic() { return g_deterministic; }

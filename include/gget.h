@@ -354,7 +354,8 @@ int gget_op_gemm_grouped(int mode, int count, const void* const* A, const void* 
  * last round, 16 the 64- / 96-row tiles of the K-split kernel, 32 two co-resident workgroups per CU for the dh + GEGLU' launch.  key 2 = LDS headroom of the 128x192 tile (0: 4-slot ring).
  * key 3 = 1: split the K range of the last, partial round's tiles among the idle workgroups (off by default).
  * key 4 = 1 (also env GGET_DETERMINISTIC=1): reproducible mode of the pre-train step - the RMSNorm weight gradients, the one sum of that
- * gradient path added with fp32 atomics, are summed in block order instead; two runs then produce bit-identical parameters.
+ * gradient path added with fp32 atomics, are summed in block order instead (same kernel selection, the per-sample kernels included); two
+ * runs then produce bit-identical parameters.
  * key 10 = 1: the per-sample kernels of S <= 32 off (the three launches each replaces run).  key 11 = 1: the fused RMSNorm + LayerScale
  * backward in its 16-byte-chunk form for every width (0: the 8-byte, all-lanes form for d = 512 / 768 / 1024).
  * key 13 = 0: the RMSNorm backward of short launches (<= 64 rows per CU) in 4-wave blocks as everywhere else (1, default: one 16-wave block
@@ -477,7 +478,8 @@ int gget_op_pack_wo(const void* w, uint64_t layer_stride, void* fwd, void* bwd, 
  * `copies` replicas `copy_stride` floats apart, as gget_op_rmsnorm_bwd's) - then dattn = dx_mid Wo (never written to memory) and the
  * attention backward of every head: dqkv [rows, 3 d] with dq / dk rotated BACK by cos_tab / sin_tab / position_ids (NULL tables: no
  * rotation).  wot_packed = gget_op_pack_wo's `bwd` output.  t_rows = rows of the token-major buffers (var-len layout: dx_mid of the pad
- * rows behind the last sample is zeroed).  *taken as above; also 0 in the reproducible mode (gget_debug_set(4, 1)).
+ * rows behind the last sample is zeroed).  *taken as above.  In the reproducible mode (gget_debug_set(4, 1)) the norm-weight gradient
+ * goes through one zeroed row per sample, summed in block order into dw_accum's first copy.
  * Var-len layout (row_base != NULL) with 32 < S <= 64: every sample by its own row count.  A sample of 33 .. 64 rows takes the first two
  * steps in its workgroup, over two row tiles; its dattn rows go to dattn_long (bf16 [t_rows, d]; rows of other samples are not touched;
  * NULL: the launch is not taken for S > 32) and a second launch on the same stream (attn_bwd_long_kernel) does its attention backward. */

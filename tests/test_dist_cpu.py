@@ -23,7 +23,14 @@ def _free_port():
     return p
 
 
+def _host_only():
+    """The workers run the host path (gloo, CPU tensors) on any box: where a GPU is visible, set_dist_env would bind rank r to device r,
+    and a box with one GPU has no device 1."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, q):
+    _host_only()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     r, _, w = tr.set_dist_env(backend="gloo")
@@ -91,6 +98,7 @@ class _FakeModel:
 
 
 def _eval_worker(rank, world, port, q):
+    _host_only()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     tr.set_dist_env(backend="gloo")
@@ -203,6 +211,7 @@ class _FakeTaskModel:
 
 
 def _ft_eval_worker(rank, world, port, q):
+    _host_only()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     tr.set_dist_env(backend="gloo")
     # eval sharding rule: sorted positions modulo world; rank 0 gets 6 samples, rank 1 gets 5 (variable-length gather)

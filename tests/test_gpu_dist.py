@@ -276,7 +276,7 @@ def test_bench_two_ranks_gloo_smoke():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--workload", "toy-tiny", "--no-cpu-baseline"]
+           "--workload", "toy-tiny", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -289,6 +289,35 @@ def test_bench_two_ranks_gloo_smoke():
     assert dp["menu_probe"]["probed"] and dp["overlap_with_backward"] == dp["menu_probe"]["chosen"]["overlap"]
     assert dp["ms_per_step_without_exchange"] > 0 and abs(dp["exposed_comm_ms"] - (d["ms_per_step"] - dp["ms_per_step_without_exchange"])) < 1e-9
     assert np.isfinite(d["smtp_loss"])
+
+
+def test_bench_two_ranks_gloo_plain_run():
+    """The plain `bench.py --gpus 2` (no --full): the headline line with the exchange arrangement the timed steps ran with - bucket layout
+    and the start-up probe's choice - and none of what only --full measures (the exchange-free steps, replica checksum, rank devices,
+    layouts, roofline)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GGET_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--workload", "toy-tiny"]
+    res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert all(k in d for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and np.isfinite(d["smtp_loss"])
+    assert d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 2 * d["config"]["per_gpu_batch"]
+    dp = d["dp"]
+    assert dp["world"] == 2 and dp["n_buckets"] == 2 + 2 and dp["backend"].endswith("gloo")
+    assert dp["menu_probe"]["probed"] and dp["overlap_with_backward"] == dp["menu_probe"]["chosen"]["overlap"]
+    assert not any(k in dp for k in ("ms_per_step_without_exchange", "exposed_comm_ms", "replicas_bit_identical", "rank_devices"))
+    assert not any(k in d for k in ("roofline", "layouts", "batch_handover", "cpu_baseline"))
 
 
 def test_c_abi_exchange_schedule_loopback_world2_and_coalesced_buckets(monkeypatch):
@@ -361,7 +390,7 @@ def test_bench_eight_ranks_gloo_smoke():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-           "--workload", "toy-tiny", "--no-cpu-baseline"]
+           "--workload", "toy-tiny", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -399,7 +428,8 @@ def test_bench_two_gpus_over_rccl(backend):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "GGET_BENCH_BACKEND"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+           "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -30,7 +30,7 @@ def run(n, env_extra, a):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    tail = ["--gpus", str(n), "--steps", str(a.steps), "--warmup", str(a.warmup), "--workload", a.workload, "--no-cpu-baseline"]
+    tail = ["--gpus", str(n), "--steps", str(a.steps), "--warmup", str(a.warmup), "--workload", a.workload, "--no-cpu-baseline", "--full"]
     if n == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + tail
     else:

@@ -35,7 +35,7 @@ def main():
         runs = []
         for _ in range(a.repeat):
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline",
-                   "--seq-len", str(S)] + (["--long-tail", str(a.long_tail)] if a.long_tail > 0 and S > 32 else [])
+                   "--full", "--seq-len", str(S)] + (["--long-tail", str(a.long_tail)] if a.long_tail > 0 and S > 32 else [])
             r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if r.returncode != 0 or not line:
