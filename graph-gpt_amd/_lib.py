@@ -60,6 +60,12 @@ SIGNATURES = {
     "gget_allreduce_grads_async": (i32, [vp, i32, i32, vp]),
     "gget_allreduce_range_async": (i32, [vp, u64, u64, i32, vp]),
     "gget_comm_init_loopback": (i32, [vp, i32]),
+    "gget_shard_plan": (i32, [C.POINTER(GgetConfig), i32, i32, C.POINTER(u64)]),
+    "gget_shard_init": (i32, [vp, i32, i32, C.POINTER(i32)]),
+    "gget_reduce_scatter_grads_async": (i32, [vp, i32, i32, vp]),
+    "gget_shard_sqnorm_partials": (i32, [vp, vp, vp]),
+    "gget_shard_allgather_async": (i32, [vp, i32, vp, vp]),
+    "gget_adamw_step_sharded": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp]),
     "gget_head_counts": (i32, [vp, C.POINTER(i32 * 2), vp]),
     "gget_head_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i32)]),
     "gget_hidden_states": (i32, [vp, C.POINTER(vp)]),
@@ -119,6 +125,8 @@ SIGNATURES = {
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 OPT_NORM_FROM_BACKWARD = 1   # gget_set_option
 OPT_SKIP_NONFINITE_STEP = 2
+SHARD_CHUNK = 4096   # include/gget.h GGET_SHARD_CHUNK: the sharded norm's chunk grid and the granule of the body slices
+SHARD_PARAMS, SHARD_MASTER, SHARD_ADAM_M, SHARD_ADAM_V, SHARD_SLOTS = 0, 1, 2, 3, 4   # gget_shard_allgather_async arenas
 TOKENS_AUTO = -2   # gget_set_token_count: count the real tokens on the device (include/gget.h GGET_TOKENS_AUTO)
 EPI_NONE, EPI_RESIDUAL, EPI_ATOMIC_F32, EPI_SLAB_F32 = 0, 1, 2, 3
 

@@ -363,6 +363,34 @@ int check_cfg(const gget_config_t* c) {
 
 }  // namespace
 
+// gradient buckets in completion order: heads (layer L) first, then layers L-1..0, then the embeddings (layer -1)
+static int bucket_of(int layer, int L) { return layer == L ? 0 : layer < 0 ? L + 1 : L - layer; }
+
+// [first, last) element range of every bucket; they tile [0, n_params) (the zero rows behind lm_head travel with the head bucket)
+static std::vector<std::pair<uint64_t, uint64_t>> bucket_ranges(const gget_config_t& cfg, const Plan& plan) {
+  const int L = cfg.num_layers;
+  std::vector<std::pair<uint64_t, uint64_t>> r(L + 2, {UINT64_MAX, 0});
+  for (const ParamRec& p : plan.params) {
+    auto& b = r[bucket_of(p.layer, L)];
+    b.first = std::min(b.first, p.off);
+    b.second = std::max(b.second, p.off + align_up(p.count, 128));
+  }
+  if (plan.lm_pad_count) {
+    auto& b = r[bucket_of(L, L)];
+    b.second = std::max(b.second, plan.lm_pad_off + align_up(plan.lm_pad_count, 128));
+  }
+  return r;
+}
+
+// ZeRO-2 shard plan of one bucket (include/gget.h gget_shard_plan): `world` equal body slices of slice = floor(cnt / (world C)) C elements,
+// rank r owning [off + r slice, off + (r + 1) slice); the tail [off + world slice, off + cnt) (< world C elements) is all-reduced and updated
+// by every rank
+struct ShardBucket { uint64_t off, cnt, slice, tail_off, tail_cnt; };
+static ShardBucket shard_bucket(uint64_t off, uint64_t cnt, int world) {
+  const uint64_t C = GGET_SHARD_CHUNK, slice = cnt / ((uint64_t)world * C) * C;
+  return ShardBucket{off, cnt, slice, off + (uint64_t)world * slice, cnt - (uint64_t)world * slice};
+}
+
 struct gget_engine {
   gget_config_t cfg;
   Plan plan;
@@ -463,17 +491,23 @@ struct gget_engine {
   int comm_rank = 0, comm_world = 1;
   float* comm_f32 = nullptr;
   uint64_t comm_f32_elems = 0;
+  // sharded optimizer step (ZeRO stage 2, gget_shard_init): the plan per bucket, and one device allocation owned by the handle with the
+  // AdamW work items of this rank's share, the norm chunks it sums (+ their slots in the gathered partial vector) and the chunk -> slot map
+  int shard_world = 0, shard_rank = 0;   // shard_world 0 = off (the replicated step)
+  int shard_slots = 0;                   // partial-vector slots per rank
+  int shard_nitems = 0, shard_nchunks = 0, shard_nglobal = 0;
+  std::vector<ShardBucket> shard_plan;
+  unsigned char* shard_tab = nullptr;
+  const GgetSqChunk* shard_items() const { return reinterpret_cast<const GgetSqChunk*>(shard_tab); }
+  const GgetSqChunk* shard_chunks() const { return shard_items() + shard_nitems; }
+  const int32_t* shard_chunk_slot() const { return reinterpret_cast<const int32_t*>(shard_chunks() + shard_nchunks); }
+  const int32_t* shard_slot_of() const { return shard_chunk_slot() + shard_nchunks; }
   const int32_t* klo() const { return packed ? wsp<int32_t>(ws.key_lo) : nullptr; }
   const int32_t* khi() const { return packed ? wsp<int32_t>(ws.key_hi) : nullptr; }
 
   template <typename Tp>
   Tp* wsp(uint64_t off) const { return reinterpret_cast<Tp*>(W + off); }
-  int bucket_of_layer(int layer) const {  // completion order: heads(L) first, then L-1..0, then embeddings(-1)
-    const int L = cfg.num_layers;
-    if (layer == L) return 0;
-    if (layer < 0) return L + 1;
-    return L - layer;
-  }
+  int bucket_of_layer(int layer) const { return bucket_of(layer, cfg.num_layers); }
 };
 
 // the engine's GEMM launches may run stream-K through the handle's workspace slice (zeroed at creation); op-level calls of the same
@@ -527,20 +561,12 @@ extern "C" int gget_create(const gget_config_t* cfg, const gget_buffers_t* bufs,
   // gradient buckets in completion order + fp32->bf16 conversion segments per bucket
   const int L = cfg->num_layers;
   const int nb = L + 2;
-  h->bucket_range.assign(nb, {UINT64_MAX, 0});
+  h->bucket_range = bucket_ranges(*cfg, h->plan);
   std::vector<std::vector<GgetSegment>> segs(nb);
   for (const ParamRec& p : h->plan.params) {
-    const int b = h->bucket_of_layer(p.layer);
-    auto& r = h->bucket_range[b];
-    r.first = std::min(r.first, p.off);
-    r.second = std::max(r.second, p.off + align_up(p.count, 128));
     if (p.accum32)
-      segs[b].push_back(GgetSegment{p.off32, p.off, align_up(p.count, 128),
-                                    (uint64_t)(p.count <= kAccumCopyMax ? kAccumCopies : 1), align_up(p.count, 128)});
-  }
-  if (h->plan.lm_pad_count) {   // the zero rows behind lm_head travel with the head bucket: the buckets tile [0, n_params)
-    auto& r = h->bucket_range[h->bucket_of_layer(L)];
-    r.second = std::max(r.second, h->plan.lm_pad_off + align_up(h->plan.lm_pad_count, 128));
+      segs[h->bucket_of_layer(p.layer)].push_back(GgetSegment{p.off32, p.off, align_up(p.count, 128),
+                                                              (uint64_t)(p.count <= kAccumCopyMax ? kAccumCopies : 1), align_up(p.count, 128)});
   }
   std::vector<GgetSegment> flat;
   h->bucket_segs.resize(nb);
@@ -601,6 +627,7 @@ extern "C" int gget_create(const gget_config_t* cfg, const gget_buffers_t* bufs,
 extern "C" int gget_comm_destroy(gget_handle_t h);
 extern "C" int gget_destroy(gget_handle_t h) {
   if (h) gget_comm_destroy(h);
+  if (h && h->shard_tab) (void)hipFree(h->shard_tab);
   if (h && h->host_word) (void)hipHostFree(h->host_word);
   if (h && h->count_event) (void)hipEventDestroy(h->count_event);
   delete h;
@@ -2148,6 +2175,110 @@ extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float bet
                  max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite);
 }
 
+// ================================================================================================
+// sharded optimizer step (ZeRO stage 2; reference: DeepSpeed zero_optimization.stage 2, examples/ds_config2_pt.json:29-32, engine built at
+// src/training/pretrain_mode.py:281-287)
+// ================================================================================================
+extern "C" int gget_shard_plan(const gget_config_t* cfg, int world, int bucket, uint64_t out[5]) {
+  if (int e = check_cfg(cfg)) return e;
+  GGET_REQUIRE(out && world >= 1, "shard_plan: bad arguments (world %d)", world);
+  GGET_REQUIRE(bucket >= 0 && bucket < cfg->num_layers + 2, "shard_plan: bucket %d out of range", bucket);
+  const auto r = bucket_ranges(*cfg, make_plan(*cfg))[bucket];
+  const ShardBucket sb = shard_bucket(r.first, r.second - r.first, world);
+  out[0] = sb.off;
+  out[1] = sb.cnt;
+  out[2] = sb.slice;
+  out[3] = sb.tail_off;
+  out[4] = sb.tail_cnt;
+  return 0;
+}
+
+extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* slots_per_rank) {
+  GGET_REQUIRE(h && world >= 0 && (world == 0 || (rank >= 0 && rank < world)), "shard_init: bad arguments (rank %d world %d)", rank, world);
+  GGET_REQUIRE(world == 0 || !(h->comm || h->comm_loopback) || (world == h->comm_world && rank == h->comm_rank),
+               "shard_init: rank %d of %d does not match the communicator (rank %d of %d)", rank, world, h->comm_rank, h->comm_world);
+  if (h->shard_tab) GGET_HIP_CHECK(hipFree(h->shard_tab));
+  h->shard_tab = nullptr;
+  h->shard_world = h->shard_rank = h->shard_slots = h->shard_nitems = h->shard_nchunks = h->shard_nglobal = 0;
+  h->shard_plan.clear();
+  if (slots_per_rank) *slots_per_rank = 0;
+  if (world == 0) return 0;
+  // the loopback communicator stands for `world` ranks that hold this rank's gradients: the handle then does the work of all of them
+  const bool all_ranks = h->comm_loopback;
+  const uint64_t C = GGET_SHARD_CHUNK;
+  std::vector<ShardBucket> plan;
+  for (const auto& r : h->bucket_range) plan.push_back(shard_bucket(r.first, r.second - r.first, world));
+  // the norm's chunk grid: off_b + j C inside every bucket (independent of world: slices are multiples of C); owner = the rank of the body
+  // slice, rank 0 for the tail
+  std::vector<GgetSqChunk> grid;
+  std::vector<int> owner;
+  for (const ShardBucket& b : plan)
+    for (uint64_t j = 0; j * C < b.cnt; ++j) {
+      grid.push_back(GgetSqChunk{b.off + j * C, std::min(C, b.cnt - j * C)});
+      owner.push_back(j * C < (uint64_t)world * b.slice ? (int)(j * C / b.slice) : 0);
+    }
+  std::vector<int> count(world, 0);
+  std::vector<int32_t> local(grid.size());
+  for (size_t j = 0; j < grid.size(); ++j) local[j] = count[owner[j]]++;
+  const int S = *std::max_element(count.begin(), count.end());
+  std::vector<int32_t> slot_of(grid.size()), chunk_slot;
+  std::vector<GgetSqChunk> chunks;
+  for (size_t j = 0; j < grid.size(); ++j) {
+    slot_of[j] = owner[j] * S + local[j];
+    if (all_ranks || owner[j] == rank) {
+      chunks.push_back(grid[j]);
+      chunk_slot.push_back(slot_of[j]);
+    }
+  }
+  // AdamW work items: this rank's body slice of every bucket (all of them for the loopback) and every tail
+  std::vector<GgetSqChunk> items;
+  auto cut = [&](uint64_t off, uint64_t cnt) {
+    for (uint64_t o = 0; o < cnt; o += kAdamwItemElems) items.push_back(GgetSqChunk{off + o, std::min<uint64_t>(kAdamwItemElems, cnt - o)});
+  };
+  for (const ShardBucket& b : plan) {
+    for (int r = 0; r < world; ++r)
+      if (all_ranks || r == rank) cut(b.off + (uint64_t)r * b.slice, b.slice);
+    cut(b.tail_off, b.tail_cnt);
+  }
+  const size_t bytes = (items.size() + chunks.size()) * sizeof(GgetSqChunk) + (chunks.size() + slot_of.size()) * sizeof(int32_t);
+  GGET_HIP_CHECK(hipMalloc(&h->shard_tab, bytes));
+  h->shard_nitems = (int)items.size();
+  h->shard_nchunks = (int)chunks.size();
+  h->shard_nglobal = (int)slot_of.size();
+  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_items(), items.data(), items.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
+  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_chunks(), chunks.data(), chunks.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
+  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_chunk_slot(), chunk_slot.data(), chunk_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_slot_of(), slot_of.data(), slot_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->shard_world = world;
+  h->shard_rank = rank;
+  h->shard_slots = S;
+  h->shard_plan = plan;
+  if (slots_per_rank) *slots_per_rank = S;
+  return 0;
+}
+
+extern "C" int gget_shard_sqnorm_partials(gget_handle_t h, float* slots_dev, void* stream) {
+  GGET_REQUIRE(h && h->shard_world > 0 && slots_dev, "shard_sqnorm_partials: call gget_shard_init first (and pass the slot vector)");
+  return k_grad_sqnorm_partials(h->G, h->shard_chunks(), h->shard_chunk_slot(), h->shard_nchunks, slots_dev, (hipStream_t)stream);
+}
+
+extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                       float max_grad_norm, float grad_scale, int step, const float* slots_dev, float* gnorm_dev, void* stream) {
+  GGET_REQUIRE(h && h->master && h->am && h->av, "adamw needs master/m/v arenas");
+  GGET_REQUIRE(h->shard_world > 0, "adamw_step_sharded: call gget_shard_init first");
+  GGET_REQUIRE(step >= 1, "step is 1-based");
+  hipStream_t st = (hipStream_t)stream;
+  h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies from the gathered weights)
+  float* sq = h->wsp<float>(h->ws.sqnorm);
+  const bool need_norm = max_grad_norm > 0.f || gnorm_dev != nullptr || h->opt_skip_nonfinite;
+  if (need_norm) {
+    GGET_REQUIRE(slots_dev, "adamw_step_sharded: the norm needs the gathered partial vector");
+    if (int e = k_grad_sqnorm_slots(slots_dev, h->shard_slot_of(), h->shard_nglobal, sq, st)) return e;
+  }
+  return k_adamw_items(h->master, h->am, h->av, h->G, h->P, h->shard_items(), h->shard_nitems, lr, beta1, beta2, eps, weight_decay, step,
+                       max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite);
+}
+
 extern "C" int gget_head_counts(gget_handle_t h, int32_t counts[2], void* stream) {
   GGET_REQUIRE(h && counts, "null argument");
   GGET_REQUIRE(h->cfg.kind == GGET_KIND_PRETRAIN, "head counts exist only for the pre-train head");
@@ -2522,6 +2653,10 @@ struct RcclApi {
   ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
   ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
   ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*ReduceScatter)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*GroupStart)() = nullptr;
+  ncclResult_t (*GroupEnd)() = nullptr;
   const char* (*GetErrorString)(ncclResult_t) = nullptr;
   bool ok = false;
   char why[256] = "symbols missing";     // dlerror() text captured once, at the failing dlopen (a second dlerror() call returns NULL)
@@ -2543,8 +2678,13 @@ RcclApi* rccl() {
       api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(dlsym(lib, "ncclCommInitRank"));
       api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(dlsym(lib, "ncclCommDestroy"));
       api.AllReduce = reinterpret_cast<decltype(api.AllReduce)>(dlsym(lib, "ncclAllReduce"));
+      api.ReduceScatter = reinterpret_cast<decltype(api.ReduceScatter)>(dlsym(lib, "ncclReduceScatter"));
+      api.AllGather = reinterpret_cast<decltype(api.AllGather)>(dlsym(lib, "ncclAllGather"));
+      api.GroupStart = reinterpret_cast<decltype(api.GroupStart)>(dlsym(lib, "ncclGroupStart"));
+      api.GroupEnd = reinterpret_cast<decltype(api.GroupEnd)>(dlsym(lib, "ncclGroupEnd"));
       api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(dlsym(lib, "ncclGetErrorString"));
-      api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.AllReduce && api.GetErrorString;
+      api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.AllReduce && api.ReduceScatter && api.AllGather &&
+               api.GroupStart && api.GroupEnd && api.GetErrorString;
     }
   }
   return &api;
@@ -2647,6 +2787,23 @@ extern "C" int gget_comm_init_loopback(gget_handle_t h, int world) {
   return 0;
 }
 
+// the communicator's fp32 staging buffer (grown to the largest bucket) holding the widened [g, g + n)
+static int widen_to_stage(gget_handle_t h, const bf16_t* g, uint64_t n, hipStream_t st) {
+  if (h->comm_f32_elems < n) {
+    if (h->comm_f32) GGET_HIP_CHECK(hipFree(h->comm_f32));
+    h->comm_f32 = nullptr;
+    uint64_t cap = 0;
+    for (const auto& r : h->bucket_range) cap = std::max<uint64_t>(cap, r.second - r.first);
+    cap = std::max<uint64_t>(cap, n);
+    GGET_HIP_CHECK(hipMalloc(&h->comm_f32, cap * sizeof(float)));
+    h->comm_f32_elems = cap;
+  }
+  const int grid = (int)std::min<uint64_t>(4096, (n / 8 + 255) / 256);
+  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid), dim3(256), 0, st, g, h->comm_f32, n);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int gget_allreduce_range_async(gget_handle_t h, uint64_t offset, uint64_t count, int fp32_accumulate, void* side_stream) {
   GGET_REQUIRE(h && (h->comm || h->comm_loopback), "allreduce_grads: call gget_comm_init first");
   GGET_REQUIRE(offset <= h->plan.n_params && count <= h->plan.n_params - offset, "allreduce_range: [%llu, +%llu) leaves the gradient array",
@@ -2668,20 +2825,79 @@ extern "C" int gget_allreduce_range_async(gget_handle_t h, uint64_t offset, uint
   }
   // fp32 reduction: a bf16 ring sum rounds after every hop (world - 1 roundings); widening the bucket first makes the sum
   // exact up to the single final rounding, at twice the bytes on the wire.  Staging buffer owned by the communicator.
-  if (h->comm_f32_elems < n) {
-    if (h->comm_f32) GGET_HIP_CHECK(hipFree(h->comm_f32));
-    h->comm_f32 = nullptr;
-    uint64_t cap = 0;
-    for (const auto& r : h->bucket_range) cap = std::max<uint64_t>(cap, r.second - r.first);
-    cap = std::max<uint64_t>(cap, n);
-    GGET_HIP_CHECK(hipMalloc(&h->comm_f32, cap * sizeof(float)));
-    h->comm_f32_elems = cap;
-  }
-  const int grid = (int)std::min<uint64_t>(4096, (n / 8 + 255) / 256);
-  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid), dim3(256), 0, st, g, h->comm_f32, n);
-  GGET_LAUNCH_CHECK();
+  if (int e = widen_to_stage(h, g, n, st)) return e;
   GGET_RCCL_CHECK(rccl()->AllReduce(h->comm_f32, h->comm_f32, n, ncclFloat32, ncclSum, c, st));
   return k_f32_to_bf16(h->comm_f32, g, n, st);
+}
+
+extern "C" int gget_reduce_scatter_grads_async(gget_handle_t h, int bucket, int fp32_accumulate, void* side_stream) {
+  GGET_REQUIRE(h && (h->comm || h->comm_loopback), "reduce_scatter_grads: call gget_comm_init first");
+  GGET_REQUIRE(h->shard_world > 0, "reduce_scatter_grads: call gget_shard_init first");
+  GGET_REQUIRE(bucket >= 0 && bucket < (int)h->shard_plan.size(), "reduce_scatter_grads: bucket %d out of range", bucket);
+  const ShardBucket& b = h->shard_plan[bucket];
+  // the loopback stands for world ranks with this rank's gradients and does the work of all of them: body and tail are world x
+  if (h->comm_loopback) return gget_allreduce_range_async(h, b.off, b.cnt, 0, side_stream);
+  hipStream_t st = (hipStream_t)side_stream;
+  ncclComm_t c = static_cast<ncclComm_t>(h->comm);
+  const uint64_t body = (uint64_t)h->shard_world * b.slice, mine = (uint64_t)h->shard_rank * b.slice;
+  bf16_t* g = h->G + b.off;
+  // in-place reduce-scatter (recvbuff = sendbuff + rank * recvcount) of the body and all-reduce of the tail, one group
+  if (!fp32_accumulate) {
+    GGET_RCCL_CHECK(rccl()->GroupStart());
+    ncclResult_t r1 = ncclSuccess, r2 = ncclSuccess;
+    if (b.slice) r1 = rccl()->ReduceScatter(g, g + mine, b.slice, ncclBfloat16, ncclSum, c, st);
+    if (b.tail_cnt) r2 = rccl()->AllReduce(g + body, g + body, b.tail_cnt, ncclBfloat16, ncclSum, c, st);
+    GGET_RCCL_CHECK(rccl()->GroupEnd());
+    GGET_RCCL_CHECK(r1);
+    GGET_RCCL_CHECK(r2);
+    return 0;
+  }
+  // fp32 reduction, as gget_allreduce_range_async: the bucket widened once, the two collectives on the staging copy, this rank's slice
+  // and the tail rounded back
+  if (int e = widen_to_stage(h, g, b.cnt, st)) return e;
+  float* w = h->comm_f32;
+  GGET_RCCL_CHECK(rccl()->GroupStart());
+  ncclResult_t r1 = ncclSuccess, r2 = ncclSuccess;
+  if (b.slice) r1 = rccl()->ReduceScatter(w, w + mine, b.slice, ncclFloat32, ncclSum, c, st);
+  if (b.tail_cnt) r2 = rccl()->AllReduce(w + body, w + body, b.tail_cnt, ncclFloat32, ncclSum, c, st);
+  GGET_RCCL_CHECK(rccl()->GroupEnd());
+  GGET_RCCL_CHECK(r1);
+  GGET_RCCL_CHECK(r2);
+  if (b.slice)
+    if (int e = k_f32_to_bf16(w + mine, g + mine, b.slice, st)) return e;
+  if (b.tail_cnt)
+    if (int e = k_f32_to_bf16(w + body, g + body, b.tail_cnt, st)) return e;
+  return 0;
+}
+
+extern "C" int gget_shard_allgather_async(gget_handle_t h, int what, float* slots_dev, void* stream) {
+  GGET_REQUIRE(h && (h->comm || h->comm_loopback), "shard_allgather: call gget_comm_init first");
+  GGET_REQUIRE(h->shard_world > 0, "shard_allgather: call gget_shard_init first");
+  GGET_REQUIRE(what >= GGET_SHARD_PARAMS && what <= GGET_SHARD_SLOTS, "shard_allgather: unknown arena %d", what);
+  GGET_REQUIRE(what != GGET_SHARD_SLOTS || slots_dev, "shard_allgather: null slot vector");
+  GGET_REQUIRE(what == GGET_SHARD_PARAMS || what == GGET_SHARD_SLOTS || (h->master && h->am && h->av), "shard_allgather: no fp32 state");
+  if (h->comm_loopback) return 0;    // (the loopback handle updated and summed every rank's share itself)
+  hipStream_t st = (hipStream_t)stream;
+  ncclComm_t c = static_cast<ncclComm_t>(h->comm);
+  const int rank = h->shard_rank;
+  if (what == GGET_SHARD_SLOTS) {
+    GGET_RCCL_CHECK(rccl()->AllGather(slots_dev + (size_t)rank * h->shard_slots, slots_dev, h->shard_slots, ncclFloat32, c, st));
+    return 0;
+  }
+  // in place (sendbuff = recvbuff + rank * sendcount), one collective per bucket body in the order the forward reads them: embeddings,
+  // layer 0, ..., heads (= the buckets backwards)
+  for (int bi = (int)h->shard_plan.size() - 1; bi >= 0; --bi) {
+    const ShardBucket& b = h->shard_plan[bi];
+    if (!b.slice) continue;
+    const uint64_t mine = b.off + (uint64_t)rank * b.slice;
+    if (what == GGET_SHARD_PARAMS) {
+      GGET_RCCL_CHECK(rccl()->AllGather(h->P + mine, h->P + b.off, b.slice, ncclBfloat16, c, st));
+    } else {
+      float* x = what == GGET_SHARD_MASTER ? h->master : what == GGET_SHARD_ADAM_M ? h->am : h->av;
+      GGET_RCCL_CHECK(rccl()->AllGather(x + mine, x + b.off, b.slice, ncclFloat32, c, st));
+    }
+  }
+  return 0;
 }
 
 extern "C" int gget_allreduce_grads_async(gget_handle_t h, int bucket, int fp32_accumulate, void* side_stream) {

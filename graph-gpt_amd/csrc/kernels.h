@@ -121,6 +121,14 @@ inline size_t k_grad_sqnorm_ws_bytes() { return (16 + 1024) * sizeof(float); }
 // ready-made partial sums (the weight-gradient kernels' per-tile sums): ws[0] = sum of both, fixed order
 struct GgetSqChunk { uint64_t off; uint64_t cnt; };
 int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st);
+// sharded step (ZeRO-2, engine.hip gget_shard_*): per-chunk sums into out[slot[c]]; the one-block sum of the gathered partials in global chunk
+// order (ws[0]); AdamW over work items of <= kAdamwItemElems elements (offsets / counts multiples of 4, one block each)
+constexpr int kAdamwItemElems = 2048;
+int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st);
+int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, float* ws, hipStream_t st);
+int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
+                  float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
+                  float* gnorm_out, hipStream_t st, bool skip_nonfinite);
 int k_adamw(float* master, float* m, float* v, const void* grad, void* param, size_t n, float lr, float beta1, float beta2,
             float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm, float* gnorm_out,
             hipStream_t st, bool skip_nonfinite = false);   // skip_nonfinite: leave everything untouched when the gradient norm is inf / NaN

@@ -1674,9 +1674,9 @@ __global__ void __launch_bounds__(kBlock) grad_sqnorm_final_kernel(float* __rest
   if (threadIdx.x == 0) ws[0] = part[0];
 }
 
-// one block per chunk (see k_grad_sqnorm_chunks): ws[16 + chunk] = sum of squares of the chunk
+// one block per chunk (see k_grad_sqnorm_chunks): out[slot ? slot[chunk] : chunk] = sum of squares of the chunk
 __global__ void __launch_bounds__(kBlock) grad_sqnorm_chunks_kernel(const bf16_t* __restrict__ g, const GgetSqChunk* __restrict__ chunks,
-                                                                    float* __restrict__ ws) {
+                                                                    float* __restrict__ out, const int32_t* __restrict__ slot) {
   __shared__ float part[kBlock / 64];
   const GgetSqChunk c = chunks[blockIdx.x];
   const bf16_t* p = g + c.off;
@@ -1693,7 +1693,7 @@ __global__ void __launch_bounds__(kBlock) grad_sqnorm_chunks_kernel(const bf16_t
   if (threadIdx.x == 0) {
     float t = 0.f;
     for (int w = 0; w < kBlock / 64; ++w) t += part[w];
-    ws[16 + blockIdx.x] = t;
+    out[slot ? slot[blockIdx.x] : (int)blockIdx.x] = t;
   }
 }
 __global__ void __launch_bounds__(kBlock) grad_sqnorm_final2_kernel(float* __restrict__ ws, int nblocks, const float* __restrict__ extra,
@@ -1711,21 +1711,89 @@ __global__ void __launch_bounds__(kBlock) grad_sqnorm_final2_kernel(float* __res
   if (threadIdx.x == 0) ws[0] = part[0];
 }
 
-template <int UNR>
-__global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                       const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
-                                                       float lr, float beta1, float beta2, float eps, float wd, float bc1,
-                                                       float bc2_sqrt, float max_norm, float grad_scale,
-                                                       const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
-  float coef = grad_scale;
+// sharded step (ZeRO-2): ws[0] = sum of the per-chunk partials of ALL ranks in global chunk order (slots[slot_of[j]] = chunk j, wherever
+// the rank that owns it left it in the gathered [world][slots] vector) - thread t adds chunks t, t + 1024, ... in order (eight independent
+// gathers in flight per batch: the base model has ~30 000 chunks and this is the one block of the step), then a fixed tree: the same bits
+// on every rank and for every world size (the chunk grid does not depend on it)
+constexpr int kSlotsBlock = 1024;
+__global__ void __launch_bounds__(kSlotsBlock) grad_sqnorm_slots_kernel(const float* __restrict__ slots, const int32_t* __restrict__ slot_of,
+                                                                        int n, float* __restrict__ ws) {
+  __shared__ float part[kSlotsBlock];
+  float t = 0.f;
+  for (int j0 = threadIdx.x; j0 < n; j0 += 8 * kSlotsBlock) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int j = j0 + u * kSlotsBlock;
+      v[u] = j < n ? slots[slot_of[j]] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t += v[u];
+  }
+  part[threadIdx.x] = t;
+  __syncthreads();
+  for (int o = kSlotsBlock / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) ws[0] = part[0];
+}
+
+// the clip coefficient and the skip rule of one AdamW step (shared by the replicated and the sharded kernel); false = skip the step
+__device__ __forceinline__ bool adamw_coef(float grad_scale, float max_norm, const float* __restrict__ sqnorm, float* __restrict__ gnorm_out,
+                                           int skip_nonfinite, float& coef) {
+  coef = grad_scale;
   if (sqnorm) {
     const float nrm = sqrtf(sqnorm[0]) * grad_scale;
     if (max_norm > 0.f) coef *= fminf(1.0f, max_norm / (nrm + 1e-6f));
     if (gnorm_out && blockIdx.x == 0 && threadIdx.x == 0) gnorm_out[0] = nrm;
     // GradScaler's rule (torch.cuda.amp.GradScaler.step: the optimizer step is skipped when the unscaled gradients hold an inf / NaN;
     // reference src/utils/training_utils.py:76-82, the DDP branch): nothing is touched, the caller reads the norm and leaves its step count
-    if (skip_nonfinite && !(nrm < INFINITY)) return;      // (uniform: every thread reads the same scalar; NaN fails the comparison too)
+    if (skip_nonfinite && !(nrm < INFINITY)) return false;      // (uniform: every thread reads the same scalar; NaN fails the comparison too)
   }
+  return true;
+}
+
+// the per-element AdamW update of four consecutive elements (vector index i): ONE definition for both kernels, so that a sharded update
+// is bit-identical to the replicated one given the same coefficient
+__device__ __forceinline__ void adamw_update4(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
+                                              const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t i, float coef,
+                                              float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  const u2v gr = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(grad + i * 4));
+  float g[4] = {__uint_as_float(gr.x << 16), __uint_as_float(gr.x & 0xffff0000u), __uint_as_float(gr.y << 16),
+                __uint_as_float(gr.y & 0xffff0000u)};
+  f4v w = __builtin_nontemporal_load(reinterpret_cast<f4v*>(master) + i);
+  f4v mm = __builtin_nontemporal_load(reinterpret_cast<f4v*>(m_) + i);
+  f4v vv = __builtin_nontemporal_load(reinterpret_cast<f4v*>(v_) + i);
+  float wp[4] = {w.x, w.y, w.z, w.w}, mp[4] = {mm.x, mm.y, mm.z, mm.w}, vp[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float ge = g[e] * coef;
+    mp[e] = beta1 * mp[e] + (1.f - beta1) * ge;
+    vp[e] = beta2 * vp[e] + (1.f - beta2) * ge * ge;
+    wp[e] *= (1.f - lr * wd);
+    const float denom = sqrtf(vp[e]) / bc2_sqrt + eps;
+    wp[e] -= (lr / bc1) * (mp[e] / denom);
+  }
+  __builtin_nontemporal_store(f4v{wp[0], wp[1], wp[2], wp[3]}, reinterpret_cast<f4v*>(master) + i);
+  __builtin_nontemporal_store(f4v{mp[0], mp[1], mp[2], mp[3]}, reinterpret_cast<f4v*>(m_) + i);
+  __builtin_nontemporal_store(f4v{vp[0], vp[1], vp[2], vp[3]}, reinterpret_cast<f4v*>(v_) + i);
+  uint2 o;
+  o.x = pack2bf(wp[0], wp[1]);
+  o.y = pack2bf(wp[2], wp[3]);
+  __builtin_nontemporal_store(u2v{o.x, o.y}, reinterpret_cast<u2v*>(param + i * 4));
+}
+
+template <int UNR>
+__global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
+                                                       const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
+                                                       float lr, float beta1, float beta2, float eps, float wd, float bc1,
+                                                       float bc2_sqrt, float max_norm, float grad_scale,
+                                                       const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
+  float coef;
+  if (!adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef)) return;
   const size_t nv = n >> 2;
   const size_t stride = (size_t)gridDim.x * kBlock;
   for (size_t i0 = (size_t)blockIdx.x * kBlock + threadIdx.x; i0 < nv; i0 += stride * UNR)
@@ -1733,32 +1801,24 @@ __global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ maste
   for (int u = 0; u < UNR; ++u) {
     const size_t i = i0 + u * stride;
     if (i >= nv) break;
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    const u2v gr = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(grad + i * 4));
-    float g[4] = {__uint_as_float(gr.x << 16), __uint_as_float(gr.x & 0xffff0000u), __uint_as_float(gr.y << 16),
-                  __uint_as_float(gr.y & 0xffff0000u)};
-    f4v w = __builtin_nontemporal_load(reinterpret_cast<f4v*>(master) + i);
-    f4v mm = __builtin_nontemporal_load(reinterpret_cast<f4v*>(m_) + i);
-    f4v vv = __builtin_nontemporal_load(reinterpret_cast<f4v*>(v_) + i);
-    float wp[4] = {w.x, w.y, w.z, w.w}, mp[4] = {mm.x, mm.y, mm.z, mm.w}, vp[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float ge = g[e] * coef;
-      mp[e] = beta1 * mp[e] + (1.f - beta1) * ge;
-      vp[e] = beta2 * vp[e] + (1.f - beta2) * ge * ge;
-      wp[e] *= (1.f - lr * wd);
-      const float denom = sqrtf(vp[e]) / bc2_sqrt + eps;
-      wp[e] -= (lr / bc1) * (mp[e] / denom);
-    }
-    __builtin_nontemporal_store(f4v{wp[0], wp[1], wp[2], wp[3]}, reinterpret_cast<f4v*>(master) + i);
-    __builtin_nontemporal_store(f4v{mp[0], mp[1], mp[2], mp[3]}, reinterpret_cast<f4v*>(m_) + i);
-    __builtin_nontemporal_store(f4v{vp[0], vp[1], vp[2], vp[3]}, reinterpret_cast<f4v*>(v_) + i);
-    uint2 o;
-    o.x = pack2bf(wp[0], wp[1]);
-    o.y = pack2bf(wp[2], wp[3]);
-    __builtin_nontemporal_store(u2v{o.x, o.y}, reinterpret_cast<u2v*>(param + i * 4));
+    adamw_update4(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
   }
+}
+
+// sharded step (ZeRO-2): the same update over a list of work items (element ranges of <= kAdamwItemElems elements, offsets and counts multiples
+// of 4) that cut the rank's body slices and the replicated tails - one launch, one block per item, every thread two float4 groups
+static_assert(kAdamwItemElems == kBlock * 8, "an AdamW work item is two float4 groups per thread");
+__global__ void __launch_bounds__(kBlock) adamw_items_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
+                                                             const bf16_t* __restrict__ grad, bf16_t* __restrict__ param,
+                                                             const GgetSqChunk* __restrict__ items, float lr, float beta1, float beta2,
+                                                             float eps, float wd, float bc1, float bc2_sqrt, float max_norm, float grad_scale,
+                                                             const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
+  float coef;
+  if (!adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef)) return;
+  const GgetSqChunk it = items[blockIdx.x];
+  const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
+  for (size_t i = threadIdx.x; i < nv; i += kBlock)
+    adamw_update4(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
 }
 
 __global__ void __launch_bounds__(kBlock) f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, size_t n) {
@@ -2819,7 +2879,8 @@ int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st) {
 
 int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st) {
   if (nchunks > 0)
-    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, ws);
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, ws + 16,
+                       (const int32_t*)nullptr);
   hipLaunchKernelGGL(grad_sqnorm_final2_kernel, dim3(1), dim3(kBlock), 0, st, ws, nchunks, extra, nextra);
   GGET_LAUNCH_CHECK();
   return 0;
@@ -2835,6 +2896,31 @@ int k_adamw(float* master, float* m, float* v, const void* grad, void* param, si
   hipLaunchKernelGGL(adamw_kernel<2>, dim3(grid_for((long)(n / 8), kBlock, 65536)), dim3(kBlock), 0, st, master, m, v,
                      (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
                      grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  hipLaunchKernelGGL(grad_sqnorm_chunks_kernel, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, out, slot_dev);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, float* ws, hipStream_t st) {
+  hipLaunchKernelGGL(grad_sqnorm_slots_kernel, dim3(1), dim3(kSlotsBlock), 0, st, slots, slot_of_dev, n, ws);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
+                  float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
+                  float* gnorm_out, hipStream_t st, bool skip_nonfinite) {
+  if (nitems <= 0) return 0;
+  const float bc1 = 1.0f - powf(beta1, (float)step);      // (the constants exactly as k_adamw derives them)
+  const float bc2 = 1.0f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adamw_items_kernel, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, items_dev,
+                     lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
   GGET_LAUNCH_CHECK();
   return 0;
 }

@@ -98,6 +98,13 @@ class Engine:
             self.buckets.append((int(o.value), int(c.value)))
         self.step_count = 0
         self.comm_world = 0     # > 0 once this handle owns an RCCL communicator (comm_init / comm_adopt)
+        # sharded optimizer step (ZeRO-2, shard_init): (world, rank) of the plan, its per-bucket ranges, the norm's partial vector
+        self.shard = None
+        self.shard_buckets = []
+        self.shard_slots = None
+        # True while master / m / v hold stale values outside this rank's share (after a sharded step, until a consolidation)
+        self.shard_stale = False
+        self._params_ready = None   # event behind the all-gather of the bf16 copy: the next reader of the weights waits for it
         self._keep = None  # keeps the last batch tensors alive until backward has consumed them
 
     def __del__(self):
@@ -124,6 +131,9 @@ class Engine:
             if k in state:
                 t = torch.as_tensor(state[k]).to(torch.float32).reshape(p["shape"])
                 self.view(k, "master").copy_(t.to(self.device))
+        self.await_params()
+        if not missing:
+            self.shard_stale = False    # (every master weight written)
         self.sync_params()
         return missing, unexpected
 
@@ -131,7 +141,16 @@ class Engine:
         return OrderedDict((k, self.view(k, "master").detach().clone()) for k in self.params)
 
     def sync_params(self):
+        if self.shard_stale:
+            raise L.GgetError("sync_params: the fp32 master weights are partitioned after a sharded (ZeRO-2) step - outside this rank's "
+                              "share they are stale; call GgetEngine.consolidate() on every rank first")
         L.check(self.lib.gget_sync_params(self.h, _stream()))
+
+    def await_params(self):
+        """Make the current stream wait for the all-gather of the bf16 weights a sharded step left in flight (no-op otherwise)."""
+        ev, self._params_ready = self._params_ready, None
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
 
     def grads(self) -> "OrderedDict[str, torch.Tensor]":
         return OrderedDict((k, self.view(k, "grad")) for k in self.params)
@@ -158,6 +177,7 @@ class Engine:
         self.set_token_count(L.TOKENS_AUTO if n == "auto" else n)
 
     def forward_pretrain(self, input_ids, attention_mask, labels=None, sample_wgt=None, position_ids=None, num_tokens=None):
+        self.await_params()
         dev = self.device
         ids = self._i64(input_ids, dev)
         if ids.dim() == 2:
@@ -185,6 +205,7 @@ class Engine:
 
     def forward_task(self, input_ids, attention_mask, position_ids=None, task_labels=None, sample_wgt=None,
                      problem: int = L.PROBLEM_SINGLE_LABEL, num_tokens=None):
+        self.await_params()
         dev = self.device
         ids = self._i64(input_ids, dev)
         if ids.dim() == 2:
@@ -302,6 +323,51 @@ class Engine:
                                          self.step_count, _ptr(self._gnorm), _stream()))
         return self._gnorm[0]
 
+    # ------------------------------------------------------------------ sharded optimizer step (ZeRO stage 2)
+    @staticmethod
+    def shard_plan_of(cfg, world: int, n_buckets: int):
+        """[(offset, count, slice, tail_offset, tail_count)] of every bucket for `world` ranks (gget_shard_plan: the plan is defined once,
+        in C, from the configuration alone)."""
+        lib, out = L.load(), (C.c_uint64 * 5)()
+        plan = []
+        for b in range(n_buckets):
+            L.check(lib.gget_shard_plan(C.byref(cfg), int(world), b, out))
+            plan.append(tuple(int(x) for x in out))
+        return plan
+
+    def shard_init(self, world: int, rank: int):
+        """Switch this handle to the sharded step of rank `rank` of `world` (gget_shard_init; world 0 = back to the replicated step)."""
+        n = C.c_int32(0)
+        L.check(self.lib.gget_shard_init(self.h, int(world), int(rank), C.byref(n)))
+        if world <= 0:
+            self.shard, self.shard_buckets, self.shard_slots = None, [], None
+            return
+        self.shard = (int(world), int(rank))
+        self.shard_buckets = self.shard_plan_of(self.cfg, world, len(self.buckets))
+        self.shard_slots = torch.zeros(int(world) * n.value, dtype=torch.float32, device=self.device)
+
+    def reduce_scatter_grads_async(self, bucket: int, fp32_accumulate: bool = False, stream: Optional[torch.cuda.Stream] = None):
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        L.check(self.lib.gget_reduce_scatter_grads_async(self.h, int(bucket), int(bool(fp32_accumulate)), st))
+
+    def shard_sqnorm_partials(self):
+        L.check(self.lib.gget_shard_sqnorm_partials(self.h, _ptr(self.shard_slots), _stream()))
+
+    def shard_allgather_async(self, what: int, stream: Optional[torch.cuda.Stream] = None):
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        L.check(self.lib.gget_shard_allgather_async(self.h, int(what), _ptr(self.shard_slots), st))
+
+    def adamw_step_sharded(self, lr, beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, grad_scale=1.0):
+        """clip + AdamW over this rank's share (gget_adamw_step_sharded); the partial vector must have been gathered.  Marks the fp32
+        state stale (a world-1 plan owns everything and stays coherent)."""
+        self.step_count += 1
+        self._gnorm = torch.empty(1, dtype=torch.float32, device=self.device)
+        L.check(self.lib.gget_adamw_step_sharded(self.h, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale,
+                                                 self.step_count, _ptr(self.shard_slots), _ptr(self._gnorm), _stream()))
+        if self.shard[0] > 1 and not getattr(self, "_loopback", False):    # (the loopback handle updates every rank's share itself)
+            self.shard_stale = True
+        return self._gnorm[0]
+
     # ------------------------------------------------------------------ data-parallel exchange through the C ABI (RCCL)
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -319,10 +385,12 @@ class Engine:
         of a `world`-rank job on one GPU."""
         L.check(self.lib.gget_comm_init_loopback(self.h, int(world)))
         self.comm_world = int(world)
+        self._loopback = True
 
     def comm_destroy(self):
         L.check(self.lib.gget_comm_destroy(self.h))
         self.comm_world = 0
+        self._loopback = False
 
     def comm_adopt(self, other: "Engine"):
         """Take over `other`'s communicator (gget_comm_move): used when the model re-creates its engine with larger capacities,
@@ -330,6 +398,7 @@ class Engine:
         if other.comm_world > 0:
             L.check(self.lib.gget_comm_move(self.h, other.h))
             self.comm_world, other.comm_world = other.comm_world, 0
+            self._loopback, other._loopback = getattr(other, "_loopback", False), False
 
     def allreduce_grads_async(self, bucket: int = -1, fp32_accumulate: bool = False, stream: Optional[torch.cuda.Stream] = None):
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)

@@ -273,7 +273,11 @@ class _GgetModel(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, state_dict, strict: bool = True):
+        if self._engine is not None:
+            self._engine.await_params()
         res = super().load_state_dict(state_dict, strict=strict)
+        if self._engine is not None:
+            self._engine.shard_stale = False    # (the master weights were written in full: the next forward refreshes the bf16 copy)
         self._dirty = True
         return res
 
@@ -292,6 +296,8 @@ class _GgetModel(nn.Module):
         cap_tok = max(need_tok, e.cfg.max_tokens if e else 0)
         cap_b = max(need_b, e.cfg.max_batch if e else 0)
         new = Engine(self.spec, cap_tok, cap_b)
+        if e is not None:
+            e.await_params()        # (a sharded step's all-gather of the bf16 weights may still be in flight)
         for name, p in self._flat.items():
             new.view(name, "master").view(p.shape).copy_(p.data.to(new.device, torch.float32))
         if e is not None:
@@ -301,7 +307,12 @@ class _GgetModel(nn.Module):
             new.comm_adopt(e)       # an RCCL communicator bound through the C ABI moves to the new handle
         for name, p in self._flat.items():
             p.data = new.view(name, "master").view(p.shape)      # (emb_mask_token is [1,1,e] in the reference, flat in the engine)
-        new.sync_params()
+        if e is not None and e.shard_stale:
+            # after a sharded step the master weights are partitioned: the bf16 copy (gathered in full) moves over as it is
+            new.param_bf16.copy_(e.param_bf16)
+            new.shard_stale = True
+        else:
+            new.sync_params()
         new.set_stack_method(getattr(self.config, "stack_method", None) == "long")
         new.set_rope_range(float(getattr(self.config, "rope_range", 0) or 0))
         new.varlen_mode = self._LAYOUTS[self._token_layout]

@@ -51,11 +51,24 @@ def warmup_decay_lr(step: int, max_lr: float, min_lr: float, warmup: int, total:
     return min_lr + (max_lr - min_lr) * gamma
 
 
+def _check_zero_stage(stage) -> int:
+    stage = int(stage)
+    if stage not in (0, 1, 2):
+        raise ValueError(f"zero_stage {stage}: only 0 (replicated optimizer step) and 1 / 2 (sharded optimizer step) exist; stage 3 "
+                         "(partitioned parameters) is not implemented")
+    return stage
+
+
 class OptimConfig:
     """Defaults = the reference pre-train launch script (examples/graph_lvl/pcqm4m_v2_pretrain.sh:53-57)."""
 
     def __init__(self, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, min_lr=0.0,
-                 warmup_num_steps=0, total_num_steps=0, schedule="constant", onecycle_extra_step=1, gradient_accumulation_steps=1):
+                 warmup_num_steps=0, total_num_steps=0, schedule="constant", onecycle_extra_step=1, gradient_accumulation_steps=1,
+                 zero_stage=0):
+        # DeepSpeed's zero_optimization.stage (examples/ds_config2_pt.json:29-32): 1 and 2 select the sharded optimizer step of a
+        # data-parallel run (see GgetEngine; this engine partitions the work, not the buffers, so the two stages are one path), 0 the
+        # replicated step; the environment variable GGET_ZERO_STAGE overrides it
+        self.zero_stage = _check_zero_stage(zero_stage)
         # micro-batches per optimizer step (the DeepSpeed engine's `gradient_accumulation_steps`, conf_utils.py:59-66): see GgetEngine.step
         self.gradient_accumulation_steps = max(1, int(gradient_accumulation_steps))
         self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
@@ -106,6 +119,46 @@ def all_reduce_bucket(flat: torch.Tensor, bucket, group=None, async_op: bool = T
     return h
 
 
+def _host_staged(flat: torch.Tensor, group) -> bool:
+    # gloo's reduce-scatter / all-gather are fed host tensors: a device arena is staged through host memory (NCCL takes device tensors)
+    return flat.is_cuda and dist.get_backend(group) == "gloo"
+
+
+def reduce_scatter_bucket(flat: torch.Tensor, plan, rank: int, world: int, group=None, fp32_accumulate: bool = False):
+    """Sharded exchange of ONE gradient bucket (ZeRO-2): the body [off, off + world * slice) reduce-scattered (SUM; rank r's slice
+    [off + r slice, off + (r + 1) slice) receives the sum) and the tail [tail_off, tail_off + tail_cnt) all-reduced.  `plan` = the bucket's
+    (offset, count, slice, tail_offset, tail_count) of gget_shard_plan.  Synchronous; device-agnostic like all_reduce_bucket (the CPU tests
+    drive it on gloo).  Outside the rank's slice the body keeps its local values."""
+    off, _, sl, toff, tcnt = plan
+    body, mine, tail = flat[off: off + world * sl], flat[off + rank * sl: off + (rank + 1) * sl], flat[toff: toff + tcnt]
+    wide = torch.float32 if fp32_accumulate else flat.dtype
+    dev = torch.device("cpu") if _host_staged(flat, group) else flat.device
+    if sl:
+        src = body.to(device=dev, dtype=wide)
+        out = torch.empty(sl, dtype=wide, device=dev)
+        dist.reduce_scatter_tensor(out, src, op=dist.ReduceOp.SUM, group=group)
+        mine.copy_(out)
+    if tcnt:
+        t = tail.to(device=dev, dtype=wide)
+        if t.data_ptr() == tail.data_ptr():
+            t = t.clone()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        tail.copy_(t)
+
+
+def all_gather_bucket(flat: torch.Tensor, plan, rank: int, world: int, group=None):
+    """The inverse of reduce_scatter_bucket's partition: every rank's body slice of `flat` (any dtype: the bf16 weights, the fp32 master /
+    Adam arenas) gathered into the body on every rank.  Tails are not touched (every rank holds the same).  Synchronous."""
+    off, _, sl, _, _ = plan
+    if not sl:
+        return
+    body, mine = flat[off: off + world * sl], flat[off + rank * sl: off + (rank + 1) * sl]
+    dev = torch.device("cpu") if _host_staged(flat, group) else flat.device
+    out = torch.empty(world * sl, dtype=flat.dtype, device=dev)
+    dist.all_gather_into_tensor(out, mine.to(dev).clone(), group=group)
+    body.copy_(out)
+
+
 def shard_seed(base_seed: int, rank: int) -> int:
     """Per-rank data seed: ranks draw independent batches (reference misc_utils.py:536-538 seeds with
     `initial_seed - rank`; the synthetic generator uses base + rank)."""
@@ -153,6 +206,13 @@ def schedule_steps(total_tokens: float, tokens_per_sample: float, batch_size: in
 
 
 # ----------------------------------------------------------------------------- engine protocol
+def _refuse_stale_state(module, prefix, keep_vars):
+    e = getattr(module, "_engine", None)
+    if e is not None and e.shard_stale:
+        raise RuntimeError("state_dict(): the fp32 master weights are partitioned after a sharded (ZeRO-2) optimizer step and stale outside "
+                           "this rank's share; call engine.consolidate() on every rank first")
+
+
 class GgetEngine:
     """What `deepspeed.initialize(model=...)` returns in the reference (pretrain_mode.py:281-287), rebuilt on
     the HIP engine: forward via `engine(...)`, `engine.backward(loss)`, `engine.step()`."""
@@ -186,6 +246,16 @@ class GgetEngine:
         # fewer, larger messages (14 buckets of ~19 MB for the base model; 60 -> 4-5 collectives).  0 (default) = one per bucket.
         self.bucket_mb = float(os.environ.get("GGET_DP_BUCKET_MB", "0"))
         self._groups = None
+        # sharded optimizer step (ZeRO stage 1 / 2 = one path; OptimConfig.zero_stage, GGET_ZERO_STAGE overrides): gradients are
+        # reduce-scattered per bucket, every rank runs clip + AdamW over its 1/world of the fp32 state (gget_adamw_step_sharded) and the
+        # bf16 weights are all-gathered behind the step.  Taken only when the exchange is live: world > 1, a loopback world, or
+        # GGET_FORCE_STAGED=1 with a process group or the C-ABI communicator; otherwise the replicated step runs, unchanged.
+        self.zero_stage = _check_zero_stage(os.environ.get("GGET_ZERO_STAGE", getattr(self.optim, "zero_stage", 0)))
+        live = self.world > 1 or (self.force_staged and (self.abi_comm or (dist.is_available() and dist.is_initialized())))
+        self.sharded = self.zero_stage > 0 and live
+        self.rank = dist.get_rank(process_group) if dist.is_available() and dist.is_initialized() and self.loopback_world == 0 else 0
+        if self.sharded:
+            model.register_state_dict_pre_hook(_refuse_stale_state)
         # measurement switch (bench.py `dp.exposed_comm_ms`): False runs the same staged backward WITHOUT issuing the collectives -
         # the ranks then drift apart, so it is only ever set for a few untimed-for-throughput diagnostic steps
         self.exchange = True
@@ -250,6 +320,8 @@ class GgetEngine:
         return self.module.device
 
     def __call__(self, *a, **k):
+        if self.module._engine is not None:
+            self.module._engine.await_params()    # (the engine's forwards wait too; explicit for readers that bypass them)
         return self.module(*a, **k)
 
     def train(self, mode=True):
@@ -290,9 +362,15 @@ class GgetEngine:
         if self.world == 1 and not self.force_staged:
             e.backward()
             return
+        if self.sharded:
+            self._ensure_shard(e)
         if not self.overlap:
             e.backward()
             if not self.exchange:
+                return
+            if self.sharded:
+                for b in range(len(e.buckets)):
+                    self._exchange_shard(e, b, None)
                 return
             if self.abi_comm:
                 e.allreduce_grads_async(-1, self.fp32_reduce)
@@ -307,6 +385,15 @@ class GgetEngine:
         groups = self.exchange_groups(e)
 
         def reduce_bucket(b):
+            if self.sharded:             # (no coalescing: one reduce-scatter + tail all-reduce per bucket)
+                ev = torch.cuda.Event()
+                ev.record(main)
+                self._comm_stream.wait_event(ev)
+                with torch.cuda.stream(self._comm_stream):
+                    if self.exchange:
+                        self._exchange_shard(e, b, self._comm_stream)
+                    self._pending.append(None)
+                return
             if b not in groups:          # a bucket inside a coalesced group: exchanged with the group's last bucket
                 return
             off, cnt = groups[b]
@@ -334,6 +421,69 @@ class GgetEngine:
             reduce_bucket(L_ - i)
         e.backward_end()
         reduce_bucket(L_ + 1)
+
+    # -- sharded optimizer step (ZeRO stage 2)
+    def _ensure_shard(self, e):
+        # the plan belongs to the engine instance (a model that re-creates its engine for a larger batch gets it again; not a collective)
+        if e.shard != (self.world, self.rank):
+            e.shard_init(self.world, self.rank)
+
+    def _exchange_shard(self, e, b: int, stream):
+        """Reduce-scatter of bucket b's body + all-reduce of its tail, on the current stream (the side stream when overlapped)."""
+        if self.abi_comm:
+            e.reduce_scatter_grads_async(b, self.fp32_reduce, stream)
+        else:
+            reduce_scatter_bucket(e.grad_bf16, e.shard_buckets[b], self.rank, self.world, self.pg, self.fp32_reduce)
+
+    def _sharded_update(self, e, lr, o, grad_scale):
+        from . import _lib as L
+        e.shard_sqnorm_partials()
+        if self.abi_comm:
+            e.shard_allgather_async(L.SHARD_SLOTS)      # (a no-op on the loopback, which summed every rank's chunks itself)
+        else:
+            self._gather_slots(e)
+        gn = e.adamw_step_sharded(lr, o.betas[0], o.betas[1], o.eps, o.weight_decay, o.max_grad_norm, grad_scale)
+        # the bf16 weights: every rank's updated slices gathered on the side stream behind AdamW; the next reader of the weights waits
+        if self._comm_stream is None:
+            self._comm_stream = torch.cuda.Stream(device=e.device)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self._comm_stream.wait_event(ev)
+        with torch.cuda.stream(self._comm_stream):
+            self._gather_arena(e, L.SHARD_PARAMS, self._comm_stream)
+            done = torch.cuda.Event()
+            done.record(self._comm_stream)
+        e._params_ready = done
+        return gn
+
+    def _gather_slots(self, e):
+        slots = e.shard_slots
+        n = slots.numel() // self.world
+        dev = torch.device("cpu") if _host_staged(slots, self.pg) else slots.device
+        out = torch.empty(slots.numel(), dtype=slots.dtype, device=dev)
+        dist.all_gather_into_tensor(out, slots[self.rank * n: (self.rank + 1) * n].to(dev).clone(), group=self.pg)
+        slots.copy_(out)
+
+    def _gather_arena(self, e, what: int, stream):
+        if self.abi_comm:
+            e.shard_allgather_async(what, stream)
+            return
+        arena = {0: e.param_bf16, 1: e.master, 2: e.adam_m, 3: e.adam_v}[what]
+        for plan in reversed(e.shard_buckets):       # embeddings, layer 0, ..., heads: the order the forward reads them
+            all_gather_bucket(arena, plan, self.rank, self.world, self.pg)
+
+    def consolidate(self):
+        """Collective (every rank calls it): after sharded steps, all-gather the fp32 master weights and the Adam moments so that every
+        rank holds the whole optimizer state again (what DeepSpeed's zero_to_fp32 does offline).  Needed before module.state_dict(),
+        save_checkpoint and Engine.sync_params; a no-op when nothing is stale."""
+        e = self.module._engine
+        if e is None or not e.shard_stale:
+            return
+        e.await_params()
+        from . import _lib as L
+        for what in (L.SHARD_MASTER, L.SHARD_ADAM_M, L.SHARD_ADAM_V):
+            self._gather_arena(e, what, None)
+        e.shard_stale = False
 
     def exchange_groups(self, e) -> Dict[int, Any]:
         """{last bucket of a group: (offset, count)} - what one collective covers.  Buckets are numbered in completion order and laid
@@ -417,7 +567,16 @@ class GgetEngine:
                 "bucket_mb": [round(c * 2 / 2 ** 20, 1) for _, c in e.buckets] if e is not None else None,
                 "collectives_per_step": len(self.exchange_groups(e)) if e is not None else None,
                 "collective_mb": [round(c * 2 / 2 ** 20, 1) for _, c in self.exchange_groups(e).values()] if e is not None else None,
-                "reserved_cus": self.reserved_cus, "nccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS")}
+                "reserved_cus": self.reserved_cus, "nccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS"),
+                "zero_stage": self.zero_stage, "optimizer": "sharded" if self.sharded else "replicated"}
+        if self.sharded and e is not None:
+            # (GGET_DP_BUCKET_MB coalescing does not apply: one reduce-scatter + one tail all-reduce per bucket)
+            from .engine import Engine
+            plan = e.shard_buckets or Engine.shard_plan_of(e.cfg, self.world, len(e.buckets))
+            info.update(bucket_coalescing="off (sharded step)", collective_mb=[round(p[1] * 2 / 2 ** 20, 1) for p in plan],
+                        owned_elements={"body": sum(p[2] for p in plan), "tail": sum(p[4] for p in plan)},
+                        collectives_per_step={"reduce_scatter": sum(1 for p in plan if p[2]), "all_reduce_tail": sum(1 for p in plan if p[4]),
+                                              "all_gather_norm_partials": 1, "all_gather_params": sum(1 for p in plan if p[2])})
         try:
             v = torch.cuda.nccl.version()
             info["rccl_version"] = ".".join(str(x) for x in v) if isinstance(v, tuple) else str(v)
@@ -464,7 +623,11 @@ class GgetEngine:
         lr = o.lr_at(self.global_steps)
         if self.skip_nonfinite and getattr(e, "_skip_nonfinite", None) is not True:
             self.set_skip_nonfinite(True)       # (the model re-created its engine: the option lives on the engine instance)
-        gn = e.adamw_step(lr, o.betas[0], o.betas[1], o.eps, o.weight_decay, o.max_grad_norm, 1.0 / (self.world * k))
+        if self.sharded:
+            self._ensure_shard(e)
+            gn = self._sharded_update(e, lr, o, 1.0 / (self.world * k))
+        else:
+            gn = e.adamw_step(lr, o.betas[0], o.betas[1], o.eps, o.weight_decay, o.max_grad_norm, 1.0 / (self.world * k))
         self.global_steps += 1
         self.last_lr, self.last_grad_norm = lr, gn
         if self.skip_nonfinite and not bool(torch.isfinite(gn)):   # (GradScaler.step reads found_inf back as well: one sync per step on this branch)
@@ -474,9 +637,14 @@ class GgetEngine:
 
     # -- checkpoint = reference DDP layout (misc_utils.py:105-121): model.pt / optimizer.pt keyed by state-dict names
     def save_checkpoint(self, save_dir: str, tag: Optional[str] = None):
+        e = self.module._engine
+        if e is not None and e.shard_stale:     # (no collective here: the pipeline saves on rank 0 only; it consolidates on every rank first)
+            raise RuntimeError("save_checkpoint: the optimizer state is partitioned after a sharded (ZeRO-2) step; call engine.consolidate() "
+                               "on every rank before saving")
+        if e is not None:
+            e.await_params()
         d = os.path.join(save_dir, tag) if tag else save_dir
         os.makedirs(d, exist_ok=True)
-        e = self.module._engine
         # the MODULE's state dict: reference shapes (emb_mask_token is [1,1,embed_dim] there, flat in the engine arena)
         torch.save({k: v.detach().cpu().clone() for k, v in self.module.state_dict().items()}, os.path.join(d, "model.pt"))
         torch.save({"m": {k: e.view(k, "m").cpu() for k in e.params}, "v": {k: e.view(k, "v").cpu() for k in e.params},
@@ -497,6 +665,7 @@ class GgetEngine:
                 e.view(k, "v").copy_(st["v"][k].to(e.device))
             e.step_count = int(st["step"])
             self.global_steps = int(st["global_steps"])
+            e.shard_stale = False       # (every arena was written in full)
         return d, {}
 
 
@@ -1163,6 +1332,8 @@ class TrainingPipeline:
             self._save_model_config()
             self.mode.setup_training(self)
             self.mode.run_training(self)
+            if self.output_dir and self.mode.allow_save_config() and getattr(self, "engine", None) is not None:
+                self.engine.consolidate()       # (a collective of every rank: the sharded step leaves the optimizer state partitioned)
             if self.output_dir and self.rank == 0 and self.mode.allow_save_config():
                 self.engine.save_checkpoint(self.output_dir)
                 # the reference's save_all writes log.csv next to its checkpoints (misc_utils.py:150-154); its presence in output_dir is
@@ -1183,6 +1354,8 @@ class TrainingPipeline:
             self.engine.load_checkpoint(self.resume_from)
         self.mode.setup_training(self)
         self.mode.run_training(self)
+        if self.output_dir and getattr(self, "engine", None) is not None:
+            self.engine.consolidate()
         if self.output_dir and self.rank == 0:
             self.engine.save_checkpoint(self.output_dir)
         return self

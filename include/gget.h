@@ -303,6 +303,54 @@ int gget_comm_init_loopback(gget_handle_t h, int world);
 int gget_adamw_step(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay,
                     float max_grad_norm, float grad_scale, int step, float* gnorm_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sharded optimizer step (ZeRO stage 2).  replaces: DeepSpeed's `"zero_optimization": {"stage": 2}` of the reference's pre-training
+ * (examples/ds_config2_pt.json:29-32, engine built at src/training/pretrain_mode.py:281-287): gradients are reduce-scattered, every rank
+ * runs clip + AdamW over its 1/world of the fp32 state only, and the bf16 compute copy is all-gathered.  The fp32 arenas keep their full
+ * size (only the WORK is partitioned); outside a rank's share master / m / v are stale after a sharded step until gget_shard_allgather_async
+ * of GGET_SHARD_MASTER / _ADAM_M / _ADAM_V (the consolidation DeepSpeed's zero_to_fp32 does offline).
+ * Plan (per bucket b of gget_bucket_range, C = GGET_SHARD_CHUNK): slice = floor(cnt / (world C)) C; rank r owns the body slice
+ * [off + r slice, off + (r + 1) slice); the tail [off + world slice, off + cnt) (< world C elements) is all-reduced and updated by every
+ * rank.  The gradient norm is summed over the fixed chunk grid off + j C of every bucket, which does not depend on world: every rank
+ * writes the sums of the chunks it owns (rank 0 also the tails') into its `slots_per_rank` entries of a caller-owned fp32 vector
+ * [world][slots_per_rank], the vector is all-gathered, and gget_adamw_step_sharded adds the chunks in global order (fixed tree): the same
+ * bits on every rank and for every world size, equal to gget_adamw_step's norm to fp32 rounding (another order).  Given the same
+ * coefficient the update of an element is bit-identical to gget_adamw_step's (one device function).
+ * A loopback communicator (gget_comm_init_loopback) stands for `world` ranks holding this rank's gradients: the handle then does the work
+ * of every rank (all bodies, all chunks) and the all-gathers are no-ops - the schedule of a `world`-rank job on one GPU.
+ * ------------------------------------------------------------------------------------------ */
+#define GGET_SHARD_CHUNK 4096
+#define GGET_SHARD_PARAMS 0 /* the bf16 compute copy (after every sharded step, before anything reads the weights) */
+#define GGET_SHARD_MASTER 1 /* fp32 master weights */
+#define GGET_SHARD_ADAM_M 2
+#define GGET_SHARD_ADAM_V 3
+#define GGET_SHARD_SLOTS 4  /* the norm's partial vector (slots_dev) */
+/* replaces: DeepSpeed stage-2 partitioning (deepspeed/runtime/zero/stage_1_and_2.py, driven by ds_config2_pt.json:29-32).  The plan of
+ * one bucket for `world` ranks, from the configuration alone (no device): out = {offset, count, slice, tail_offset, tail_count}. */
+int gget_shard_plan(const gget_config_t* cfg, int world, int bucket, uint64_t out[5]);
+/* replaces: the partition set-up of deepspeed.initialize with stage 2 (pretrain_mode.py:281-287).  Switches the handle to the plan of
+ * rank `rank` of `world` (world 0 = off) and builds the device tables (AdamW work items, norm chunks, chunk -> slot map), owned by the
+ * handle; synchronous.  With a communicator, rank / world must be its own.  *slots_per_rank (may be NULL) = entries per rank of the
+ * partial vector. */
+int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* slots_per_rank);
+/* replaces: the bucketed reduce-scatter of DeepSpeed stage 2 (reduce_scatter: true in ds_config2_pt.json's zero_optimization): the body of
+ * bucket `bucket` reduce-scattered in place (this rank's slice receives the sum) and the tail all-reduced, one group on `side_stream`
+ * (stream protocol and fp32_accumulate as gget_allreduce_grads_async; the loopback multiplies the whole bucket by world). */
+int gget_reduce_scatter_grads_async(gget_handle_t h, int bucket, int fp32_accumulate, void* side_stream);
+/* replaces: the squared-norm part of DeepSpeed's clip over partitioned gradients (stage_1_and_2.py get_grad_norm, gradient_clipping of
+ * ds_config2_pt.json): the sums of the chunks this rank owns into slots_dev[rank * slots_per_rank ...] (all ranks' for the loopback). */
+int gget_shard_sqnorm_partials(gget_handle_t h, float* slots_dev, void* stream);
+/* replaces: the all-gather of the updated bf16 partitions (stage_1_and_2.py step -> all_gather_dp_groups) and, for the fp32 arenas, the
+ * consolidation of zero_to_fp32.py.  `what` = GGET_SHARD_*: the bucket bodies of that arena gathered in place, embeddings first (the order
+ * the forward reads them), one collective per bucket; GGET_SHARD_SLOTS gathers the partial vector slots_dev.  No-op for the loopback. */
+int gget_shard_allgather_async(gget_handle_t h, int what, float* slots_dev, void* stream);
+/* replaces: clip + FusedAdam.step over the rank's partition (DeepSpeed stage 2; training_utils.py:68-80 for the clip rule).  Arguments as
+ * gget_adamw_step; slots_dev = the GATHERED partial vector (may be NULL when no norm is needed: max_grad_norm <= 0, gnorm_dev NULL and
+ * GGET_OPT_SKIP_NONFINITE_STEP off).  Updates this rank's body slices and every tail (master, m, v and the bf16 copy) in one launch;
+ * GGET_OPT_SKIP_NONFINITE_STEP applies (every rank sees the same norm, so all skip together). */
+int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
+                            float grad_scale, int step, const float* slots_dev, float* gnorm_dev, void* stream);
+
 /* Head bookkeeping of the last pre-train forward.  counts[0] = M (positions with >=1 masked
  * feature), counts[1] = Lm (masked feature tokens).  Synchronises `stream`.
  * logits: bf16 [Lm][ld] with ld = round_up(V,64) (pad columns are zero). */
