@@ -68,3 +68,87 @@ def rel_l2(a, b):
 
 def tb(batch):
     return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in batch.items()}
+
+
+# ------------------------------------------------------------------------------------------ element-wise GEMM checks
+# Exact operands: values n * 2^e with integer |n| <= EXACT_NMAX (zero allowed), e constant along each row of the logical A [M,K] (one
+# exponent per output row) and along each column of the logical B [K,N] (one per output column).  Every product of the dot product
+# behind C[i,j] is then an integer multiple of u = 2^(ea_i + eb_j) of magnitude <= NMAX^2 u, and so is every partial sum, whatever the
+# summation order, of magnitude <= (K NMAX^2 + RMAX) u (RMAX: the residual, also a multiple of u).  Below 2^24 u such a number is an
+# fp32 value: fp32 accumulation is exact for any tiling, K split or stream-K partial, and the right bf16 output is bf16_rne(exact sum).
+EXACT_NMAX = 4
+EXACT_RMAX = 64
+EXACT_OCTAVES = 3
+
+
+def exact_bound(K, nmax=EXACT_NMAX, residual=False):
+    """Largest partial sum of a K-long exact dot product, in units of its own exponent (must stay below 2^24)."""
+    return K * nmax * nmax + (EXACT_RMAX if residual else 0)
+
+
+def exact_operands(M, N, K, seed, mode=0, residual=False, device="cpu", nmax=EXACT_NMAX, octaves=EXACT_OCTAVES):
+    """bf16 operands of C[M,N] = op(A) op(B) (+ R) in the memory layout of `mode` (0 NT: A [M,K], B [N,K]; 1 NN: A [M,K], B [K,N];
+    2 TN: A [K,M], B [K,N]) whose fp32 products and sums are exact (bound above, asserted here).  Returns (A, B, R); R is None unless
+    `residual`: bf16 [M,N], an integer in [-RMAX, RMAX] times the exponent of its output element."""
+    assert exact_bound(K, nmax, residual) < 2 ** 24, f"K = {K}: partial sums of exact operands would leave fp32's 24 bits"
+    assert nmax <= 256 and EXACT_RMAX <= 256      # (integers that bf16's 8-bit significand holds)
+    g = torch.Generator(device=device).manual_seed(seed)
+    ri = lambda lo, hi, shape: torch.randint(lo, hi, shape, generator=g, device=device, dtype=torch.int32).float()   # noqa: E731
+    ea, eb = ri(-octaves, 1, (M, 1)), ri(-octaves, 1, (1, N))
+    A = ri(-nmax, nmax + 1, (M, K)) * torch.exp2(ea)              # (fp32 holds these exactly)
+    B = ri(-nmax, nmax + 1, (K, N)) * torch.exp2(eb)
+    R = (ri(-EXACT_RMAX, EXACT_RMAX + 1, (M, N)) * torch.exp2(ea + eb)).to(torch.bfloat16) if residual else None
+    A = A.t() if mode == 2 else A
+    B = B.t() if mode == 0 else B
+    return A.to(torch.bfloat16).contiguous(), B.to(torch.bfloat16).contiguous(), R
+
+
+def _logical64(mode, A, B):
+    """op(A) [M,K] and op(B) [K,N] in fp64 from the memory layout of `mode`."""
+    a, b = A.double(), B.double()
+    return (a.t() if mode == 2 else a), (b.t() if mode == 0 else b)
+
+
+def gemm_expected(mode, A, B, R=None):
+    """(bf16, fp32) result of exact operands: the fp64 product (+ R), which is an fp32 number (checked), rounded to bf16 to nearest
+    even - what the kernels' fp32 accumulate + RNE convert must reproduce bit for bit."""
+    a, b = _logical64(mode, A, B)
+    c64 = a @ b
+    if R is not None:
+        c64 = c64 + R.double()
+    c32 = c64.float()
+    assert torch.equal(c32.double(), c64), "operands are not exact: the fp64 result is no fp32 number"
+    return c32.to(torch.bfloat16), c32
+
+
+def gemm_ref64(mode, A, B, R=None):
+    """fp64 reference and the fp64 |op(A)| @ |op(B)| (+ |R|) that scales its accumulation error bound."""
+    a, b = _logical64(mode, A, B)
+    ref, ab = a @ b, a.abs() @ b.abs()
+    if R is not None:
+        ref, ab = ref + R.double(), ab + R.double().abs()
+    return ref, ab
+
+
+def assert_elementwise(got, ref64, absprod64, K, c_out=1.0, c_acc=1.0, atol=0.0, tile=(64, 64), what=""):
+    """|got - ref| <= c_out 2^-8 |ref| + c_acc K 2^-24 (|A| @ |B|) + atol in every element (fp64).  The first term is the bf16 output
+    rounding (2x its unit roundoff), the second the fp32 accumulation bound of a K-long dot product.  On failure the message names the
+    worst elements with their (row, col), their `tile` coordinates and the excess over the bound, and how many tiles hold failures -
+    a broken tile shows as one tile.  Returns the largest |got - ref| / bound."""
+    got = got.double()
+    ref64 = ref64.double()
+    err = (got - ref64).abs()
+    bound = c_out * 2.0 ** -8 * ref64.abs() + c_acc * K * 2.0 ** -24 * absprod64.double() + atol
+    bad = ~(err <= bound)                       # (NaN counts as bad)
+    ratio = float((err / bound.clamp_min(1e-300)).nan_to_num(float("inf")).max()) if err.numel() else 0.0
+    if bool(bad.any()):
+        idx = bad.nonzero()
+        ex = (err - bound)[bad].nan_to_num(float("inf"))
+        top = ex.argsort(descending=True)[:8]
+        tiles = {(int(r) // tile[0], int(c) // tile[1]) for r, c in idx.tolist()}
+        lines = [f"  ({int(idx[t, 0])}, {int(idx[t, 1])}) tile {int(idx[t, 0]) // tile[0]},{int(idx[t, 1]) // tile[1]}: "
+                 f"got {float(got[idx[t, 0], idx[t, 1]]):.6g} ref {float(ref64[idx[t, 0], idx[t, 1]]):.6g} "
+                 f"excess {float(ex[t]):.3g} over bound {float(bound[idx[t, 0], idx[t, 1]]):.3g}" for t in top.tolist()]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements out of bound in {len(tiles)} "
+                             f"{tile[0]}x{tile[1]} tile(s) {sorted(tiles)[:6]}; worst:\n" + "\n".join(lines))
+    return ratio

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import rel_l2
+from _util import record_error, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -354,6 +354,69 @@ def _attn_ref(qkv, lens, B, S, H, causal):
     return o
 
 
+def _attn64(x, allow, dmask=None):
+    """fp64 attention of one problem per (sample, head): x [B,S,3,H,64] fp64 (q, k as the kernel multiplies them), allow [B,S(query),S(key)]
+    bool.  Returns out [B,S,H,64] and the natural-log lse [B,H,S] of the 0.125-scaled scores over the allowed keys (csrc/attention.hip
+    stores (m2 + log2 l) / log2(e) of the log2-domain scores: the same quantity)."""
+    q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
+    w = (q @ k.transpose(2, 3) * 0.125).masked_fill(~allow[:, None], float("-inf"))
+    lse = torch.logsumexp(w, -1)
+    p = torch.softmax(w, -1).nan_to_num(0.0)
+    if dmask is not None:
+        p = p * dmask.double()
+    return (p @ v).transpose(1, 2), lse
+
+
+def _per_problem_rel(got, ref, rows=None):
+    """rel-L2 of every (sample, head) problem alone: got / ref [B,S,H,64], rows [B,S] bool (None: all rows) -> [B,H]."""
+    d = (got.double() - ref.double()) ** 2
+    r = ref.double() ** 2
+    if rows is not None:
+        d, r = d * rows[:, :, None, None], r * rows[:, :, None, None]
+    num, den = d.sum((1, 3)).sqrt(), r.sum((1, 3)).sqrt()
+    return torch.where(den > 0, num / den.clamp_min(1e-300), num)
+
+
+# Per-problem bounds (forward rel-L2, |lse - lse64|, dq / dk / dv rel-L2) of one (sample, head), at 2-3x the maxima measured over every
+# parametrisation of test_attention_fwd_bwd and test_attention_varlen_by_sample_rows (forward 3.0e-3, dq / dk / dv 3.6e-3, lse 1.3e-6;
+# lse with RoPE applied on load 7.3e-4).
+# A zeroed head scores 1.0 on either rel-L2 and one swapped with an independent head ~1.4: 100x the bound.  RoPE applied on load
+# (pos given) rounds the rotated q / k to bf16 inside the kernel: the reference rounds them too, and lse gets its own bound.
+ATTN_PROBLEM_BOUNDS = (1e-2, 4e-6, 1e-2)
+ATTN_LSE_BOUND_ROPE = 2e-3
+
+
+def _check_attn_problems(case, out, lse, qkv, allow, rows, B, S, H, pos=None, dmask=None, dout=None, dqkv=None, grad_map=None,
+                         bounds=ATTN_PROBLEM_BOUNDS):
+    """Per-(sample, head) rel-L2 of the forward output (real query rows) and - given dout / dqkv - of dq, dk, dv, against fp64 autograd on
+    the same bf16 inputs (pos: q / k rotated by RoPE first, gradients taken w.r.t. the un-rotated ones; grad_map: applied to the fp64
+    gradient before the comparison); lse per element on the real query rows.  Every (sample, head) is checked on its own."""
+    bo, bl, bg = bounds
+    xl = qkv.double().view(B, S, 3, H, 64).detach().requires_grad_(True)
+    x64 = xl
+    if pos is not None:
+        x64 = torch.stack((_rope_ref(xl[:, :, 0], pos), _rope_ref(xl[:, :, 1], pos), xl[:, :, 2]), dim=2)
+        x64 = x64 + (x64.to(torch.bfloat16).double() - x64).detach()      # (the kernel's bf16 rounding; gradient straight through)
+        bl = ATTN_LSE_BOUND_ROPE
+    ref, ref_lse = _attn64(x64, allow, dmask)
+    e = _per_problem_rel(out.view(B, S, H, 64), ref.detach(), rows)
+    record_error(case, "fwd_per_head", float(e.max()), bo)
+    assert float(e.max()) < bo, f"{case}: forward rel-L2 of (sample, head) {divmod(int(e.argmax()), H)} = {float(e.max()):.3g}"
+    qrows = rows[:, None, :].expand(B, H, S)
+    le = (lse.view(B, H, S).double() - ref_lse.detach())[qrows].abs()
+    record_error(case, "lse_abs", float(le.max()), bl)
+    assert float(le.max()) < bl, f"{case}: lse off by {float(le.max()):.3g}"
+    if dout is None:
+        return
+    (ref * dout.double().view(B, S, H, 64)).sum().backward()
+    g = dqkv.view(B, S, 3, H, 64)
+    want = xl.grad if grad_map is None else grad_map(xl.grad)
+    for i, nm in enumerate("qkv"):
+        eg = _per_problem_rel(g[:, :, i], want[:, :, i])
+        record_error(case, f"d{nm}_per_head", float(eg.max()), bg)
+        assert float(eg.max()) < bg, f"{case}: d{nm} rel-L2 of (sample, head) {divmod(int(eg.argmax()), H)} = {float(eg.max()):.3g}"
+
+
 @pytest.mark.parametrize("causal", [0, 1])
 @pytest.mark.parametrize("rope", [False, True])
 @pytest.mark.parametrize("B,S,H", [(3, 24, 2), (2, 32, 12), (2, 72, 2), (1, 160, 3), (2, 520, 2), (1, 2048, 1), (171, 32, 12), (700, 24, 3)])   # the last two: thousands of one-wave problems (the headline shape's launch geometry)
@@ -397,6 +460,13 @@ def test_attention_fwd_bwd(lib, B, S, H, causal, rope):
     for i, nm in enumerate("qkv"):
         e = rel_l2(g[:, :, i].cpu().numpy(), w[:, :, i].cpu().numpy())
         assert e < 2e-2, f"attn bwd d{nm} rel-L2 {e}"
+    # every (sample, head) on its own against fp64, lse per element; causal row 0 attends to key 0 alone: its output is v, bit for bit
+    allow = valid[:, None, :].expand(B, S, S)
+    if causal:
+        allow = allow & torch.ones(S, S, dtype=torch.bool, device="cuda").tril()[None]
+        assert torch.equal(out.view(B, S, d)[:, 0], qkv.view(B, S, 3, d)[:, 0, 2]), "causal row 0 is not its v row"
+    _check_attn_problems(f"attn_problems/fwd_bwd_{B}x{S}x{H}_c{causal}_r{int(rope)}", out, lse, qkv, allow, valid, B, S, H,
+                         pos=pos if rope else None, dout=dout, dqkv=dqkv)
 
 
 def _drop_mask(seed, B, H, S, p):
@@ -531,13 +601,30 @@ def test_attention_varlen_by_sample_rows(lib, B, S, H, causal, p, rope):
         e = rel_l2(g[:, i].cpu().numpy(), want[sel][:, i].cpu().numpy())
         assert e < 2e-2, f"var-len attention backward d{nm} rel-L2 {e}"
     # per-sample check of the long samples alone (5 % of a real batch: a slip there would drown in the batch-wide norm)
-    for b in range(min(B, 12)):
+    for b in range(B):
         if int(lens[b]) > 32:
             r0, r1 = int(cu[b]), int(cu[b + 1])
             ws = want[b * S: b * S + int(lens[b])]
             for i, nm in enumerate("qkv"):
                 e = rel_l2(g[r0:r1, i].cpu().numpy(), ws[:, i].cpu().numpy())
                 assert e < 2.5e-2, f"sample {b} ({int(lens[b])} rows) d{nm} rel-L2 {e}"
+    # every (sample, head) on its own against fp64 (q / k as rotated in memory; gradients rotated back), lse per element; a 1-row sample
+    # and causal row 0 attend to one key: their output is that key's v row, bit for bit
+    allow = valid[:, None, :].expand(B, S, S)
+    if causal:
+        allow = allow & torch.ones(S, S, dtype=torch.bool, device="cuda").tril()[None]
+    dq_pad = torch.zeros(B * S, 3 * d, dtype=torch.bfloat16, device="cuda")
+    dq_pad[sel] = dqkv_c[:T]
+    unrot = None
+    if rope:
+        unrot = lambda gr: torch.stack((_rope_ref_signed(gr[:, :, 0], pos, -1.0), _rope_ref_signed(gr[:, :, 1], pos, -1.0), gr[:, :, 2]), dim=2)   # noqa: E731
+    _check_attn_problems(f"attn_problems/varlen_{B}x{S}x{H}_c{causal}_p{p}_r{int(rope)}", out_p, lse_p, qkv_mem, allow, valid, B, S, H,
+                         dmask=_drop_mask(seed, B, H, S, p).cuda() if p > 0 else None, dout=dout, dqkv=dq_pad, grad_map=unrot)
+    if p == 0:
+        for b in range(B):
+            if int(lens[b]) == 1 or causal:
+                r0 = int(cu[b])
+                assert torch.equal(out_c[r0], qkv_c[r0, 2 * d:]), f"sample {b}: row 0 of a one-key problem is not its v row"
 
 
 def _rope_ref_signed(x, pos, sign, theta=10000.0):
