@@ -2,6 +2,7 @@
 library is missing or does not load, importing the engine raises."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -75,6 +76,7 @@ SIGNATURES = {
     "gget_op_gemm_streamk": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "gget_op_gemm_streamk_bytes": (u64, []),
     "gget_debug_set": (i32, [i32, i32]),
+    "gget_debug_get": (i32, [i32, C.POINTER(i32)]),
     "gget_debug_occupy": (i32, [vp, u64, i32, i32, i32, vp]),
     "gget_op_gemm_grouped": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gget_op_rmsnorm_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, vp]),
@@ -105,6 +107,7 @@ SIGNATURES = {
     "gget_set_auc": (i32, [vp, i32, C.c_uint32]),
     "gget_set_token_count": (i32, [vp, C.c_int64]),
     "gget_set_option": (i32, [vp, i32, i32]),
+    "gget_set_dp_menu": (i32, [vp, i32, i32]),
     "gget_varlen_status": (i32, [vp, vp, vp]),
     "gget_position_status": (i32, [vp, vp, vp]),
     "gget_deferred_status": (i32, [vp, vp, vp]),
@@ -129,6 +132,34 @@ SHARD_CHUNK = 4096   # include/gget.h GGET_SHARD_CHUNK: the sharded norm's chunk
 SHARD_PARAMS, SHARD_MASTER, SHARD_ADAM_M, SHARD_ADAM_V, SHARD_SLOTS = 0, 1, 2, 3, 4   # gget_shard_allgather_async arenas
 TOKENS_AUTO = -2   # gget_set_token_count: count the real tokens on the device (include/gget.h GGET_TOKENS_AUTO)
 EPI_NONE, EPI_RESIDUAL, EPI_ATOMIC_F32, EPI_SLAB_F32 = 0, 1, 2, 3
+
+# gget_debug_set / gget_debug_get keys of the process launch menu (csrc/menu.h kMenuRows, INTEGRATION.md "Kernel-selection knobs")
+KEY_GEMM_VARIANT, KEY_GEMM_LDS_HEADROOM, KEY_GEMM_SPLIT_LAST, KEY_DETERMINISTIC, KEY_GEMM_STAGGER = 1, 2, 3, 4, 5
+KEY_GEMM_ABLATE, KEY_HEAD_DENSE, KEY_HEAD_TILE, KEY_ATTN_OPROJ_OFF, KEY_LS_NORM_BWD_WIDE = 7, 8, 9, 10, 11
+KEY_RMS_WIDE, KEY_CE_PARTS, KEY_GEMM_CU_RESERVE, KEY_OCCUPY_FAT = 13, 14, 15, 16
+MENU_KEYS = (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 13, 14, 15, 16)
+# KEY_GEMM_VARIANT bits (csrc/menu.h kGemm*): the first six switch a variant OFF, the last two switch one ON
+GEMM_NO_KSPLIT_ND, GEMM_NO_KSPLIT_WGRAD, GEMM_NO_192_ROWS, GEMM_NO_SPLIT_LAST, GEMM_KSPLIT_128_ONLY, GEMM_ONE_BLOCK_PER_CU = 1, 2, 4, 8, 16, 32
+GEMM_KSPLIT_DMA8, GEMM_AREA_RULE = 128, 512
+
+
+def debug_get(key: int) -> int:
+    v = i32()
+    check(load().gget_debug_get(int(key), C.byref(v)))
+    return int(v.value)
+
+
+@contextlib.contextmanager
+def debug_menu(keys):
+    """Set process launch-menu keys ({key: value}) for the body and restore the values they had before."""
+    saved = {k: debug_get(k) for k in keys}
+    try:
+        for k, v in keys.items():
+            check(load().gget_debug_set(int(k), int(v)))
+        yield
+    finally:
+        for k, v in saved.items():
+            check(load().gget_debug_set(k, v))
 
 
 def gemm_grouped(lib, mode, problems, stream):

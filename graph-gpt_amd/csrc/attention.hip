@@ -3165,10 +3165,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_fused64_kernel(const bf16_t* 
 // waves (= 32-row tiles) per block: long sequences share each K/V (or Q/dO) tile among 4 waves through LDS
 int attn_waves(int S) { return S >= 128 ? 4 : (S >= 64 ? 2 : 1); }
 // GGET_ATTN_BY_SAMPLE=0: the S-keyed launches of rounds 1 - 5 for 32 < S <= 64 (A/B switch of the per-sample dispatch)
-bool attn_by_sample_rows() {
-  static const int on = getenv("GGET_ATTN_BY_SAMPLE") ? atoi(getenv("GGET_ATTN_BY_SAMPLE")) : 1;
-  return on != 0;
-}
+bool attn_by_sample_rows() { return menu().attn_by_sample != 0; }
 constexpr int kLongGrid = 32;      // sample slots of a list-driven long launch (a block walks the list with this stride)
 
 Drop make_drop(float p, unsigned seed) {
@@ -3198,19 +3195,11 @@ int k_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, i
     GGET_LAUNCH_CHECK();
     return 0;
   }
-  static int big = -1;
-  if (big < 0) { const char* e = getenv("GGET_ATTN_BIG"); big = e ? atoi(e) : 1; }
-  if (S >= 256 && !cos_tab && big) {   // long sequences with q / k already rotated (the engine's layout): 64-row DMA stages
-    static int dense = -1;
-    if (dense < 0) { const char* e = getenv("GGET_ATTN_DENSE"); dense = e ? atoi(e) : 1; }
+  if (S >= 256 && !cos_tab && menu().attn_big) {   // long sequences with q / k already rotated (the engine's layout): 64-row DMA stages
 #define GGET_FWD64(PK) hipLaunchKernelGGL((attn_fwd64_kernel<PK, 1, 8>), dim3((S + 255) / 256, H, B), dim3(512), 0, st, (const bf16_t*)qkv, KR, \
                                           (bf16_t*)out, lse, B, S, H, causal, D)
-    if (dense && !key_lo && !causal && S >= 512) {   // (shorter rows: the pipeline's fill and drain cost more than it hides)
-      static int nwb4 = -1;
-      if (nwb4 < 0) { const char* e = getenv("GGET_ATTN_FWD_NWB4"); nwb4 = e ? atoi(e) : 0; }
-      if (D.thresh && nwb4) hipLaunchKernelGGL((attn_fwd_dense_kernel<true, 4>), dim3((S + 127) / 128, H, B), dim3(256), 0, st, (const bf16_t*)qkv, key_len,
-                                               (bf16_t*)out, lse, B, S, H, D, row_base);
-      else if (D.thresh) hipLaunchKernelGGL((attn_fwd_dense_kernel<true, 8>), dim3((S + 255) / 256, H, B), dim3(512), 0, st, (const bf16_t*)qkv, key_len,
+    if (menu().attn_dense && !key_lo && !causal && S >= 512) {   // (shorter rows: the pipeline's fill and drain cost more than it hides)
+      if (D.thresh) hipLaunchKernelGGL((attn_fwd_dense_kernel<true, 8>), dim3((S + 255) / 256, H, B), dim3(512), 0, st, (const bf16_t*)qkv, key_len,
                                        (bf16_t*)out, lse, B, S, H, D, row_base);
       else hipLaunchKernelGGL((attn_fwd_dense_kernel<false, 8>), dim3((S + 255) / 256, H, B), dim3(512), 0, st, (const bf16_t*)qkv, key_len,
                               (bf16_t*)out, lse, B, S, H, D, row_base);
@@ -3239,11 +3228,7 @@ int k_pack_wo(const void* w0, size_t layer_stride, void* fwd, void* bwd, int d, 
   GGET_LAUNCH_CHECK();
   return 0;
 }
-int g_attn_oproj_off = 0;   // gget_debug_set key 10: in-process A/B of the fused form
-bool attn_oproj_enabled() {
-  static const int on = getenv("GGET_ATTN_OPROJ") ? atoi(getenv("GGET_ATTN_OPROJ")) : 1;
-  return on && !g_attn_oproj_off;
-}
+bool attn_oproj_enabled() { return menu().attn_oproj && !menu().attn_oproj_off; }   // (attn_oproj_off: in-process A/B of the fused form)
 template <int H>
 static int launch_attn_oproj(const void* qkv, const int32_t* key_len, const int32_t* row_base, void* attn_out, float* lse, const void* wo,
                              const void* x_in, void* x_mid, const void* nw, void* xn, float* rstd, int B, int S, int causal, float eps,
@@ -3313,7 +3298,7 @@ int k_attn_oproj_bwd(const void* dxn, const void* x_mid, const void* nw, const f
   // block b owns row b, and its at most two adds onto zero are exact in either order); the rows are then summed in block order
   float* part = nullptr;
   float* dw_out = dw_accum;
-  if (k_get_deterministic()) {
+  if (menu().deterministic) {
     const int d = H * 64;
     if (int e = k_det_scratch((size_t)(B + (B + 63) / 64) * d, &part)) return e;
     GGET_HIP_CHECK(hipMemsetAsync(part, 0, (size_t)B * d * sizeof(float), st));
@@ -3351,9 +3336,8 @@ int k_attn_bwd(const void* qkv, const void* out, const void* dout, const float* 
   const Rope R{cos_tab, sin_tab, position_ids, S};     // rotation of dq, dk back to the un-rotated projections
   const Rope Rin = qk_rotated ? Rope{nullptr, nullptr, nullptr, S} : R;   // q,k in memory are already rotated?
   const Drop D = make_drop(dropout_p, dropout_seed);
-  static int small = -1;
-  if (small < 0) { const char* e = getenv("GGET_ATTN_SMALL"); small = e ? atoi(e) : 1; }
-  if ((S <= 32 || (S <= 64 && !Rin.cos_tab && attn_by_sample_rows())) && !key_lo && small) {      // every sample by its OWN row count: one 32-row tile, or (33 .. 64 rows) 2 x 2
+  const LaunchMenu& m = menu();
+  if ((S <= 32 || (S <= 64 && !Rin.cos_tab && attn_by_sample_rows())) && !key_lo && m.attn_small) {      // every sample by its OWN row count: one 32-row tile, or (33 .. 64 rows) 2 x 2
     if (S <= 32 || row_base)        // (padded layout with S > 32: every sample owns S rows - nothing for the one-tile kernel)
       hipLaunchKernelGGL(attn_bwd_small_kernel, dim3(1, H, B), dim3(64), 0, st, (const bf16_t*)qkv,
                          (const bf16_t*)dout, lse, key_len, (bf16_t*)dqkv, B, S, H, causal, Rin, R, D, row_base);
@@ -3367,19 +3351,13 @@ int k_attn_bwd(const void* qkv, const void* out, const void* dout, const float* 
     GGET_LAUNCH_CHECK();
     return 0;
   }
-  static int big = -1;
-  if (big < 0) { const char* e = getenv("GGET_ATTN_BIG"); big = e ? atoi(e) : 1; }
   // (q, k rotated in memory - the engine's layout - or no rotation at all: the staged kernels read them as they are and rotate dq / dk
   // back in their epilogues; q, k to be rotated on load, the plain-op form of the tests, stays on the register-prefetch kernels)
-  if (S >= 256 && (!cos_tab || qk_rotated) && big) {
+  if (S >= 256 && (!cos_tab || qk_rotated) && m.attn_big) {
     // fused form (one pass; the caller provides room for the key blocks' dQ partials: bf16 [ceil(S / 256)][dq_slab_stride], dq_slab_stride >=
     // rows x H x 64): see attn_bwd_fused64_kernel.  (S = 256, one key block per row: still ahead of the two-kernel form once the partials are
     // plain stores - C3 step 40.06 -> 39.69 ms, same box; GGET_ATTN_FUSED_MIN_S moves the threshold.)
-    static int fused = -1;
-    if (fused < 0) { const char* e = getenv("GGET_ATTN_FUSED"); fused = e ? atoi(e) : 1; }
-    static int fused_min_s = -1;
-    if (fused_min_s < 0) { const char* e = getenv("GGET_ATTN_FUSED_MIN_S"); fused_min_s = e ? atoi(e) : 256; }
-    if (dq_ws && fused && S >= fused_min_s) {
+    if (dq_ws && m.attn_fused && S >= m.attn_fused_min_s) {
       static bool attr = false;
       if (!attr) {
         GGET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kFusedLds));
@@ -3396,8 +3374,7 @@ int k_attn_bwd(const void* qkv, const void* out, const void* dout, const float* 
       GGET_LAUNCH_CHECK();
       return 0;
     }
-    static int stg128 = -1;
-    if (stg128 < 0) { const char* e = getenv("GGET_ATTN_STG128"); stg128 = e ? atoi(e) : 1; }
+    const int stg128 = m.attn_stg128;
 #define GGET_BWD64(PK)                                                                                                           \
   do {                                                                                                                           \
     hipLaunchKernelGGL((attn_bwd_dq64_kernel<PK, 4>), dim3((S + 127) / 128, H, B), dim3(256), 0, st, (const bf16_t*)qkv,             \

@@ -4,6 +4,8 @@
 #include <type_traits>
 #include <stdint.h>
 
+#include "menu.h"
+
 typedef unsigned short bf16_t;  // raw bfloat16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;

@@ -34,7 +34,6 @@ extern "C" int gget_version(void) { return 101; }
 
 struct PathDropArg { float rate; unsigned seed; int S; const int32_t* row_b; };   // row_b: sample index of every row (var-len token layout) or NULL (row / S)
 
-extern int g_gemm_lds_headroom;   // gemm.hip: >= 2 while a collective's kernel shares the chip (data-parallel runs)
 namespace {
 
 inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
@@ -489,6 +488,9 @@ struct gget_engine {
   void* comm = nullptr;
   bool comm_loopback = false;     // gget_comm_init_loopback: no peers, an all-reduce multiplies by comm_world
   int comm_rank = 0, comm_world = 1;
+  // the data-parallel share of the launch menu (gget_set_dp_menu; CallScope applies it to this handle's calls)
+  int dp_reserve_cus = 0;
+  bool dp_lds_headroom = false;
   float* comm_f32 = nullptr;
   uint64_t comm_f32_elems = 0;
   // sharded optimizer step (ZeRO stage 2, gget_shard_init): the plan per bucket, and one device allocation owned by the handle with the
@@ -510,11 +512,26 @@ struct gget_engine {
   int bucket_of_layer(int layer) const { return bucket_of(layer, cfg.num_layers); }
 };
 
-// the engine's GEMM launches may run stream-K through the handle's workspace slice (zeroed at creation); op-level calls of the same
-// thread afterwards must not see it
-struct StreamKScope {
-  explicit StreamKScope(gget_engine* h) { gget_gemm_streamk_workspace(h->W + h->ws.sk_ws); }
-  ~StreamKScope() { gget_gemm_streamk_workspace(nullptr); }
+// Every forward / backward call of a handle runs inside one CallScope.  It installs (a) the handle's stream-K workspace slice (zeroed at
+// creation), through which the engine's GEMM launches may run stream-K, and (b) the menu the call plans with: the process menu overlaid
+// by the handle's data-parallel fields (gget_set_dp_menu).  Op-level calls of the same thread afterwards see neither.
+struct CallScope {
+  LaunchMenu m;
+  explicit CallScope(gget_engine* h) : m(g_menu) {
+    if (h->dp_reserve_cus > 0) {   // CUs of their own for the collective: the 3-slot rings, the RMSNorm backward in its many-small-blocks form
+      m.gemm_cu_reserve = h->dp_reserve_cus;
+      m.gemm_lds_headroom = 1;
+      m.rms_wide = 0;
+    } else if (h->dp_lds_headroom) {
+      m.gemm_lds_headroom = 2;
+    }
+    t_call_menu = &m;
+    gget_gemm_streamk_workspace(h->W + h->ws.sk_ws);
+  }
+  ~CallScope() {
+    gget_gemm_streamk_workspace(nullptr);
+    t_call_menu = nullptr;
+  }
 };
 
 // ================================================================================================
@@ -724,6 +741,14 @@ extern "C" int gget_set_option(gget_handle_t h, int option, int value) {
   return 2;
 }
 
+extern "C" int gget_set_dp_menu(gget_handle_t h, int reserve_cus, int lds_headroom) {
+  GGET_REQUIRE(h != nullptr, "null handle");
+  GGET_REQUIRE(reserve_cus >= 0, "set_dp_menu: reserve_cus %d < 0", reserve_cus);
+  h->dp_reserve_cus = reserve_cus;
+  h->dp_lds_headroom = lds_headroom != 0;
+  return 0;
+}
+
 extern "C" int gget_deferred_status(gget_handle_t h, int32_t out[2], void* stream) {
   GGET_REQUIRE(h && out, "null argument");
   int32_t* st = h->wsp<int32_t>(h->ws.vl_status);
@@ -785,30 +810,17 @@ int gemm_nn(const void* A, const void* Bw, void* C, int M, int N, int K, int lda
             hipStream_t st, const int* c_rows = nullptr) {
   return gget_gemm_single(GGET_GEMM_NN, GGET_EPI_NONE, A, Bw, C, nullptr, M, N, K, lda, ldb, ldc, m_dev, nullptr, 1, st, false, c_rows);
 }
-// Slot-sorted n_token_proj (kernels.hip: "Slot-sorted SMTP head"): on by default; GGET_HEAD_SORTED=0 / gget_debug_set(8, 1) = the dense
+// Slot-sorted n_token_proj (kernels.hip: "Slot-sorted SMTP head"): on by default; menu head_sorted = 0 or head_dense = 1 = the dense
 // projection of every selected row through all n slots (rounds 1-3)
-int g_head_dense = 0;
-int g_head_tile = 0;   // 0: 256-row tiles when d % 256 == 0, else 128 ; 128 / 256: forced (gget_debug_set key 9)
-inline int head_tile_rows(int d) { return g_head_tile == 128 ? 128 : ((d % 256) == 0 ? 256 : 128); }
-bool head_scatter_fused();
-inline bool head_scatter_fused_decl() { return head_scatter_fused(); }
-bool head_sorted() {
-  static const int off = getenv("GGET_HEAD_SORTED") != nullptr && atoi(getenv("GGET_HEAD_SORTED")) == 0;
-  return !off && !g_head_dense && head_scatter_fused_decl();
-}
-bool head_scatter_fused() {
-  static const int off = getenv("GGET_NO_HEAD_SCATTER_FUSION") != nullptr;
-  return !off;
-}
+inline int head_tile_rows(int d) { return menu().head_tile == 128 ? 128 : ((d % 256) == 0 ? 256 : 128); }
+bool head_scatter_fused() { return !menu().no_head_scatter_fusion; }
+bool head_sorted() { return menu().head_sorted && !menu().head_dense && head_scatter_fused(); }
 
 // Gated-GELU MLP with the activation fused into the GEMMs around it (hf LlamaMLP.forward :174-176):
 //   forward : gu = xn2 W_gu^T (kept for the backward), h = bf16(gelu(gate)) * up, one launch
 //   backward: dgu = geglu'(dy W_down ; gu), one launch - dh is never materialised
 // Available when ff % 128 == 0 (the forward tile holds 128 gate + 128 up columns); otherwise GEMM + element-wise kernel.
-bool geglu_fusable(int d, int ff) {
-  static const int off = getenv("GGET_NO_GEGLU_FUSION") != nullptr;
-  return !off && ff % 128 == 0 && d % 64 == 0;
-}
+bool geglu_fusable(int d, int ff) { return !menu().no_geglu_fusion && ff % 128 == 0 && d % 64 == 0; }
 int gateup_geglu(const bf16_t* x, const bf16_t* wgu, bf16_t* gu, bf16_t* hh, int T, int d, int ff, hipStream_t st) {
   if (!geglu_fusable(d, ff)) {
     if (int e = gemm_nt(x, wgu, gu, nullptr, T, 2 * ff, d, d, d, 2 * ff, nullptr, st)) return e;
@@ -1104,7 +1116,6 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_ls_kernel(const bf16_t* __res
     if (dlam_accum) unsafeAtomicAdd(dlam_accum + off, dl_lds[j] + dl_lds[d + j] + dl_lds[2 * d + j] + dl_lds[3 * d + j]);
   }
 }
-int g_ls_norm_bwd_wide = getenv("GGET_LS_NORM_BWD_WIDE") ? atoi(getenv("GGET_LS_NORM_BWD_WIDE")) : 0;
 // The same pass for d = 256 PCH with every lane busy and a third of the registers: lane l owns the 4 channels [256 p + 4 l, +4) of each of
 // the PCH pieces of a row (8-byte loads, 512 contiguous bytes per wave instruction), norm weight and LayerScale vector stay packed, the
 // residual / branch operands are unpacked where they are used, and there is no software prefetch - ~100 registers = 5 waves per SIMD keep
@@ -1226,7 +1237,7 @@ int rmsnorm_bwd_ls(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const flo
   const int grid = (int)std::min<long>(4096, ((long)T + 15) / 16);
   const size_t lds = (size_t)8 * d * sizeof(float);
   const uint64_t cs = align_up((uint64_t)d, 128);
-  if (!g_ls_norm_bwd_wide && (d == 512 || d == 768 || d == 1024)) {   // (gget_debug_set(11, 1): the 16-byte-chunk form for every width)
+  if (!menu().ls_norm_bwd_wide && (d == 512 || d == 768 || d == 1024)) {   // (ls_norm_bwd_wide: the 16-byte-chunk form for every width)
     // 5 workgroups of 4 waves per CU in one round; every wave walks rows with a grid stride (fewer partial-sum atomics per row as well)
     const int g4 = (int)std::min<long>(1280, ((long)T + 15) / 16);
 #define GGET_LS4(P) hipLaunchKernelGGL(rmsnorm_bwd_ls4_kernel<P>, dim3(g4), dim3(256), lds, st, dy, x, w, rstd, dres, dx, dw_accum, y, lam, dsc, \
@@ -1246,10 +1257,7 @@ int rmsnorm_bwd_ls(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const flo
   return 0;
 }
 
-bool ls_norm_fused() {
-  static const int off = getenv("GGET_NO_LS_NORM_FUSION") != nullptr;
-  return !off;
-}
+bool ls_norm_fused() { return !menu().no_ls_norm_fusion; }
 int layer_forward(gget_engine* h, int i, hipStream_t st) {
   const gget_config_t& c = h->cfg;
   const int T = h->T, d = c.hidden_size, ff = c.intermediate_size, H = c.num_heads;
@@ -1343,10 +1351,7 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
   return 0;
 }
 
-bool varlen_enabled() {
-  static const int off = getenv("GGET_NO_VARLEN") != nullptr;
-  return !off;
-}
+bool varlen_enabled() { return !menu().no_varlen; }
 int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, const int64_t* mask, const int64_t* pos, int B, int S,
                      hipStream_t st, bool mask_is_3d = false, const int64_t* labels = nullptr, bool allow_varlen = true) {
   const gget_config_t& c = h->cfg;
@@ -1432,7 +1437,7 @@ int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, 
       // Round 6: sum_lengths_kernel stores the count into the pinned word itself (system-scope release) and the host POLLS the word -
       // no device-to-host copy packet and no event in the stream (a 4 us blit kernel plus a 5.7 us bubble behind the event's barrier
       // packet in every step before).  GGET_COUNT_COPY=1: the copy + event of rounds 3 - 5.
-      static const bool count_copy = getenv("GGET_COUNT_COPY") && atoi(getenv("GGET_COUNT_COPY")) != 0;
+      const bool count_copy = menu().count_copy != 0;
       constexpr int32_t kNoCount = INT32_MIN;
       if (!count_copy) __atomic_store_n(h->host_word, kNoCount, __ATOMIC_RELEASE);     // (before the launch: the launch orders it)
       if (int e = k_sum_lengths(h->wsp<int32_t>(h->ws.key_len), B, dst, st, count_copy ? nullptr : h->host_word_dev)) return e;
@@ -1538,7 +1543,7 @@ static int forward_pretrain_impl(gget_handle_t h, const int64_t* input_ids_dev, 
   GGET_REQUIRE(h->cfg.kind == GGET_KIND_PRETRAIN, "handle was not created as a pre-train model");
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
-  StreamKScope sk_scope(h);
+  CallScope scope(h);
   h->fwd_valid = false;
   const Ws& w = h->ws;
   const int d = c.hidden_size, n = c.next_n_token, V = c.vocab_size;
@@ -1650,7 +1655,7 @@ extern "C" int gget_forward_task(gget_handle_t h, const int64_t* input_ids_dev, 
   GGET_REQUIRE(h->cfg.kind == GGET_KIND_TASK, "handle was not created as a task model");
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
-  StreamKScope sk_scope(h);
+  CallScope scope(h);
   h->fwd_valid = false;
   if (int e = backbone_forward(h, tc_hint, input_ids_dev, c.stacked_feat, attention_mask_dev, position_ids_dev, B, S, st, false, nullptr))
     return e;
@@ -1766,14 +1771,14 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
   } else if (int e = down_dgrad_geglu(dy_down, h->P + lo.wdown, h->wsp<bf16_t>(lw.gu), dgu, dh, T, d, ff, st)) return e;
   if (int e = gemm_nn(dgu, h->P + lo.wgu, dxn, T, d, 2 * ff, 2 * ff, d, d, nullptr, st)) return e;
   bool front_fused = false;
-  // (g_gemm_lds_headroom >= 2: a collective's kernel shares the chip with the backward - data-parallel runs.  The per-sample backward kernel
+  // (gemm_lds_headroom >= 2: a collective's kernel shares the chip with the backward - data-parallel runs.  The per-sample backward kernel
   //  fills 151 of the 160 KiB of a CU's LDS with ONE workgroup per sample: a foreign workgroup on a CU would push the sample's workgroup into
   //  a second round, the mechanism behind the GEMM launch menu's headroom rule.  The three-launch form runs then; the
   //  forward - which never overlaps a collective - stays fused.)
   // (Both rules are opt-in since round 5 - GGET_DP_LDS_HEADROOM, GGET_DP_RESERVE_CUS; a data-parallel rank keeps the single-GPU menu by
-  //  default, this kernel included: tools/dp_standin.py.  With CUs RESERVED for the collective - g_gemm_cu_reserve - the collective's
+  //  default, this kernel included: tools/dp_standin.py.  With CUs RESERVED for the collective - gemm_cu_reserve - the collective's
   //  workgroups have their own CUs: the kernel may run whenever its one-workgroup-per-sample grid fits the CUs that are left.)
-  const bool ao_bwd_ok = g_gemm_cu_reserve > 0 ? h->B <= gget_gemm_num_cu() : g_gemm_lds_headroom < 2;
+  const bool ao_bwd_ok = menu().gemm_cu_reserve > 0 ? h->B <= gget_gemm_num_cu() : menu().gemm_lds_headroom < 2;
   if (!h->plan.has_res && !h->klo() && h->wo_packed && ao_bwd_ok) {
     // S <= 32, or S <= 64 on the var-len layout (every sample by its own row count): RMSNorm backward of post_attention_layernorm, the o
     // projection's dgrad and the attention backward of a sample in ONE workgroup (attention.hip: attn_oproj_bwd_kernel); dattn is never
@@ -1827,13 +1832,13 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
   // weight gradients of the layer (dW = dY^T X, K = T).  All four dY / X pairs are still alive here.
   const GemmProblem wg_gu{dgu, h->wsp<bf16_t>(lw.xn2), h->G + lo.wgu, nullptr, 2 * ff, d, T, 2 * ff, d, d, nullptr, nullptr, 0, 0};
   const GemmProblem wg_dn{dy_down, h->wsp<bf16_t>(lw.h), h->G + lo.wdown, nullptr, d, ff, T, d, ff, ff, nullptr, nullptr, 0, 0};
-  // Data-parallel runs leave CUs to their collectives (g_gemm_cu_reserve): the 256 tiles of the grouped launch below would then need a second
+  // Data-parallel runs leave CUs to their collectives (gemm_cu_reserve): the 256 tiles of the grouped launch below would then need a second
   // round for a few of them (twice the time).  As many problems as fit the CUs that are left stay in the one-tile-per-CU group (in the order
   // gate|up 128, down 64, q|k|v 48, o 16 tiles at d = 768); the rest - q|k|v and o, contiguous in the gradient array - take the split-K slab
   // path (128 x 128 or 256 x 128 tiles x K slices fitted to one round, fp32 slabs summed by slab_reduce).
   const long t192[4] = {(long)2 * ff * d / (192 * 192), (long)d * ff / (192 * 192), (long)3 * d * d / (192 * 192), (long)d * d / (192 * 192)};
   int n_grouped = 4;
-  if (d % 192 == 0 && ff % 192 == 0 && g_gemm_cu_reserve > 0) {
+  if (d % 192 == 0 && ff % 192 == 0 && menu().gemm_cu_reserve > 0) {
     long acc_t = 0;
     n_grouped = 0;
     for (int q = 0; q < 4 && acc_t + t192[q] <= gget_gemm_num_cu(); ++q) { acc_t += t192[q]; ++n_grouped; }
@@ -1925,8 +1930,7 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
 // which form of the embedding backward runs (embed_bwd below): the count-matrix product, or the sorted scatter-add
 // (embedding dropout masks every (cell, channel) on its own: the count-matrix product cannot express it)
 static bool embed_dense_path(int T, int d, int V, bool gated, const ElemDropArg& E) {
-  static const bool sorted_only = getenv("GGET_EMBED_SORTED") != nullptr;   // A/B knob
-  return !sorted_only && E.thresh == 0 && k_embed_dense_ok(V, gated) && T > 0 && ((long)V * d) % 4 == 0;
+  return !menu().embed_sorted && E.thresh == 0 && k_embed_dense_ok(V, gated) && T > 0 && ((long)V * d) % 4 == 0;
 }
 
 extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stream) {
@@ -1934,7 +1938,7 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
   GGET_REQUIRE(h->fwd_valid && h->have_labels, "backward needs a preceding forward with labels");
   GGET_REQUIRE(loss_scale == 1.0f, "loss scaling is not used on the bf16 path (pass 1.0)");
   h->sq_layers = 0;
-  StreamKScope sk_scope(h);
+  CallScope scope(h);
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
   const Ws& w = h->ws;
@@ -2069,7 +2073,7 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
 extern "C" int gget_backward_layer(gget_handle_t h, int layer, void* stream) {
   GGET_REQUIRE(h && h->fwd_valid && h->dx_cur, "backward_layer before backward_begin");
   GGET_REQUIRE(layer >= 0 && layer < h->cfg.num_layers, "layer %d out of range", layer);
-  StreamKScope sk_scope(h);
+  CallScope scope(h);
   return layer_backward(h, layer, (hipStream_t)stream);
 }
 
@@ -2104,7 +2108,7 @@ int embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* g
 
 extern "C" int gget_backward_end(gget_handle_t h, void* stream) {
   GGET_REQUIRE(h && h->fwd_valid && h->dx_cur, "backward_end before backward_begin");
-  StreamKScope sk_scope(h);
+  CallScope scope(h);
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
   float* s32 = h->wsp<float>(h->ws.scratch32);
@@ -2348,7 +2352,7 @@ __global__ void __launch_bounds__(256) occupy_kernel(float* buf, size_t n, long 
   }
   if (acc == 1.2345e-30f) buf[0] = acc;
 }
-// ... with the REGISTER footprint of RCCL's kernel (gget_debug_set(16, 1)): rcclGenericKernel allocates 261 - 280 registers per lane (its
+// ... with the REGISTER footprint of RCCL's kernel (menu key 16, occupy_fat): rcclGenericKernel allocates 261 - 280 registers per lane (its
 // gfx950 code object) - one wave of it per SIMD leaves no room for the two waves of a GEMM workgroup, whatever LDS is
 // free.  The clobbers make the compiler allocate 256 vector + 8 accumulation registers; the loop is the same.
 __global__ void __launch_bounds__(256) occupy_fat_kernel(float* buf, size_t n, long long ticks) {
@@ -2364,7 +2368,6 @@ __global__ void __launch_bounds__(256) occupy_fat_kernel(float* buf, size_t n, l
   }
   if (acc == 1.2345e-30f) buf[0] = acc;
 }
-int g_occupy_fat = 0;
 extern "C" int gget_debug_occupy(void* scratch, uint64_t scratch_bytes, int blocks, int lds_bytes, int microseconds, void* stream) {
   GGET_REQUIRE(scratch && scratch_bytes >= 4096 && blocks > 0 && lds_bytes >= 4 && lds_bytes <= 160 * 1024, "debug_occupy: bad arguments");
   static bool attr = false;
@@ -2373,7 +2376,7 @@ extern "C" int gget_debug_occupy(void* scratch, uint64_t scratch_bytes, int bloc
     GGET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&occupy_fat_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
-  if (g_occupy_fat) {
+  if (menu().occupy_fat) {
     hipLaunchKernelGGL(occupy_fat_kernel, dim3(blocks), dim3(256), lds_bytes, (hipStream_t)stream, (float*)scratch, scratch_bytes / 4,
                        (long long)microseconds * 100);
     GGET_LAUNCH_CHECK();
@@ -2385,12 +2388,6 @@ extern "C" int gget_debug_occupy(void* scratch, uint64_t scratch_bytes, int bloc
   return 0;
 }
 
-extern int g_attn_oproj_off;
-extern int g_gemm_variant;
-extern int g_gemm_lds_headroom;
-extern int g_gemm_split_last;
-extern int g_gemm_stagger_ticks;
-extern int g_gemm_ablate_set;
 extern "C" int gget_debug_probe(gget_handle_t h, int enable, float* avg_ms_out /* [2] or NULL */) {
   GGET_REQUIRE(h != nullptr, "null handle");
   if (avg_ms_out) {   // mean launch duration over the layers of the last forward / backward that ran with the probe on
@@ -2409,26 +2406,6 @@ extern "C" int gget_debug_probe(gget_handle_t h, int enable, float* avg_ms_out /
   }
   h->probe = enable != 0;
   return 0;
-}
-extern "C" int gget_debug_set(int key, int value) {
-  switch (key) {
-    case 1: g_gemm_variant = value; return 0;
-    case 2: g_gemm_lds_headroom = value; return 0;
-    case 4: k_set_deterministic(value); return 0;
-    case 3: g_gemm_split_last = value; return 0;
-    case 5: g_gemm_stagger_ticks = value; return 0;
-    case 7: g_gemm_ablate_set = value > 0 ? value : -1; return 0;
-    case 8: g_head_dense = value; return 0;
-    case 9: g_head_tile = value; return 0;
-    case 10: g_attn_oproj_off = value; return 0;
-    case 11: g_ls_norm_bwd_wide = value; return 0;
-    case 13: k_set_rms_wide(value); return 0;
-    case 14: k_set_ce_parts(value); return 0;
-    case 15: g_gemm_cu_reserve = value > 0 ? value : 0; return 0;
-    case 16: g_occupy_fat = value; return 0;
-  }
-  gget_set_error("debug_set: unknown key %d", key);
-  return 2;
 }
 extern "C" int gget_op_gemm(int mode, int epilogue, const void* A, const void* B, void* C, const void* R, int M, int N, int K,
                             int lda, int ldb, int ldc, int split_k, void* stream) {
@@ -2732,8 +2709,6 @@ extern "C" int gget_comm_init(gget_handle_t h, int rank, int world, const void* 
   h->comm = c;
   h->comm_rank = rank;
   h->comm_world = world;
-  // a collective's kernel will share the chip with the compute stream: keep LDS headroom on every CU
-  if (world > 1 && g_gemm_cu_reserve == 0 && g_gemm_lds_headroom < 2 && getenv("GGET_DP_LDS_HEADROOM") && atoi(getenv("GGET_DP_LDS_HEADROOM"))) g_gemm_lds_headroom = 2;   // (opt-in since round 5: DESIGN.md section 6)
   return 0;
 }
 
@@ -2783,7 +2758,6 @@ extern "C" int gget_comm_init_loopback(gget_handle_t h, int world) {
   h->comm_loopback = true;
   h->comm_rank = 0;
   h->comm_world = world;
-  if (world > 1 && g_gemm_cu_reserve == 0 && g_gemm_lds_headroom < 2 && getenv("GGET_DP_LDS_HEADROOM") && atoi(getenv("GGET_DP_LDS_HEADROOM"))) g_gemm_lds_headroom = 2;   // (opt-in since round 5: DESIGN.md section 6)   // (the launch menu of a data-parallel run, as gget_comm_init)
   return 0;
 }
 

@@ -74,9 +74,8 @@ constexpr size_t kStreamKFlagBytes = (kStreamKBlocks + 64) * sizeof(unsigned);
 inline size_t gget_gemm_streamk_bytes() { return kStreamKFlagBytes + kStreamKBlocks * kStreamKSlotBytes; }
 void gget_gemm_streamk_workspace(void* ws);
 
-// CUs the launcher plans for: the device's, minus g_gemm_cu_reserve (gget_debug_set key 15: CUs left free for a collective's workgroups in
-// data-parallel runs - gemm.hip has the reason), or GGET_GEMM_NUM_CU.  Every tile plan, persistent grid and split-K fit uses it.
-extern int g_gemm_cu_reserve;
+// CUs the launcher plans for: the device's (or menu().gemm_num_cu), minus menu().gemm_cu_reserve (CUs left free for a collective's
+// workgroups in data-parallel runs - gemm.hip has the reason).  Every tile plan, persistent grid and split-K fit uses it.
 int gget_gemm_num_cu();
 
 // mode: GGET_GEMM_NT/NN/TN, epi: GGET_EPI_*; problems of one group share mode and epilogue.

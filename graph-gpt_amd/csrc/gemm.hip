@@ -36,25 +36,17 @@
 
 #define LDS_AS __attribute__((address_space(3)))
 
-int g_gemm_lds_headroom = 1;   // 1 (default): the 128x192 / 192x128 tile kernels run a 3-slot ring and leave 40 KiB of LDS free, 0: 4 slots = all 160 KiB,
-                               // 2 (set when a communicator is attached: world > 1): also no launch with two LDS-filling blocks per CU
-                               // (gget_debug_set key 2, env GGET_GEMM_LDS_HEADROOM; measured in profiles/r02_coresidency.txt)
-int g_gemm_split_last = 0;   // split the K range of the last, partial round's tiles among the idle blocks (gget_debug_set key 3, env
-                            // GGET_GEMM_SPLIT_LAST).  Off by default: on the C1 shapes the hand-over of the partial tiles costs more than the
-                            // shorter last round returns (profiles/r03_gemm_varlen_shapes.txt); correct and tested (tests/test_gpu_ops.py)
-int g_gemm_variant = 0;   // measurement knob (gget_debug_set key 1): selects experimental kernel variants for in-process A/B timing
-int g_gemm_ablate_set = -1;     // >= 0: replaces GGET_GEMM_ABLATE at run time (gget_debug_set key 7; in-process A/B of the experiment bits)
-int g_gemm_stagger_ticks = 0;   // MODE 2 launches (two workgroups per CU): start delay of a CU's second workgroup in 100 MHz ticks (gget_debug_set
-                                // key 5, env GGET_GEMM_STAGGER); 0 = both start together (round 3)
-
-
-// CUs the GEMM launches leave FREE (gget_debug_set key 15; data-parallel runs set it to the number of channels they allow the collective
+// The launch plans below read their knobs from menu() (menu.h).  gemm_lds_headroom: measured in profiles/r02_coresidency.txt;
+// gemm_split_last: off because on the C1 shapes the hand-over of the partial tiles costs more than the shorter last round returns
+// (profiles/r03_gemm_varlen_shapes.txt; correct and tested: tests/test_gpu_ops.py); gemm_stagger_ticks: 0 = both workgroups of a CU
+// start together (round 3).
+//
+// gemm_cu_reserve: CUs the GEMM launches leave FREE (data-parallel runs set it to the number of channels they allow the collective
 // library).  Why: an RCCL workgroup (rcclGenericKernel: 256 threads, 261 - 280 registers per lane, 19.7 KiB of LDS - read from the library's
 // gfx950 code object) cannot share a CU with ANY 8-wave GEMM workgroup of this file (2 waves x 130 - 216 registers per SIMD), and these
 // launches assign their tiles statically: one workgroup that finds its CU taken starts when the others exit and the launch takes twice as
 // long (profiles/r02_coresidency.txt measured exactly that with one foreign workgroup).  With R CUs left free the collective's <= R
 // workgroups and the GEMM's (CUs - R) never compete.
-int g_gemm_cu_reserve = 0;
 int gget_gemm_num_cu() {
   static int dev_cus = 0;
   if (!dev_cus) {
@@ -62,10 +54,10 @@ int gget_gemm_num_cu() {
     hipDeviceProp_t prop;
     dev_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
                   ? prop.multiProcessorCount : 256;
-    if (const char* e = getenv("GGET_GEMM_NUM_CU")) dev_cus = atoi(e);   // measurement knob: pretend the chip has fewer CUs (tools/halfchip.py)
   }
-  int n = dev_cus - (g_gemm_cu_reserve > 0 ? g_gemm_cu_reserve : 0);
-  if (g_gemm_cu_reserve > 0) n &= ~7;      // (the XCD permutation of the persistent kernels wants a multiple of 8)
+  const LaunchMenu& m = menu();
+  int n = (m.gemm_num_cu > 0 ? m.gemm_num_cu : dev_cus) - (m.gemm_cu_reserve > 0 ? m.gemm_cu_reserve : 0);   // (gemm_num_cu: tools/halfchip.py)
+  if (m.gemm_cu_reserve > 0) n &= ~7;      // (the XCD permutation of the persistent kernels wants a multiple of 8)
   return n < 8 ? 8 : n;
 }
 
@@ -1137,7 +1129,7 @@ __global__ void __launch_bounds__(WM * WN * 64, MODE == 2 ? 4 : ((WM * WN) >= 8 
 // four never enter the vector-memory queue during the K-loop and keep issuing MFMAs while the first four sit in DMA issue (a DMA piece
 // costs its wave 60-180 cycles of issue when the queue is busy).  Bit-identical results, C1 step -1.0 ... -1.2 % on two boxes (7.173 ->
 // 7.100, 7.402 -> 7.314 ms, same process, alternated: profiles/r04_step_experiments.txt item 5).  8 = every wave its own share
-// (rounds 2-3; g_gemm_variant bit 7).
+// (rounds 2-3; menu key 1 bit kGemmKsplitDma8).
 template <int BM, int BN, bool A_MC, bool B_MC, int EPI, int NSLOT_ = 0, int DW = 8>
 __global__ void __launch_bounds__(512, 2) gemm_ks_kernel(const GemmGroup g, int total_tiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1315,232 +1307,10 @@ __global__ void __launch_bounds__(512, 2) gemm_ks_kernel(const GemmGroup g, int 
   }
 }
 
-// ---- the same in-block K split on v_mfma_f32_32x32x16_bf16 (round 4; weight gradients: both operands M/N-contiguous) -----------------
-// A wave owns (BM/2) x (BN/2) of the block tile as 32x32 accumulator blocks (192x192: 3 x 3 blocks = 144 accumulator registers) and the
-// two 16-deep k-steps [32 wk, 32 wk + 32) of every 64-deep K-tile: per k-step 3 + 3 fragments (two transposing LDS reads each - the
-// window rotation of TileIO<192, MC> is conflict-free for this lane pattern as well: the 32 lanes of an LDS cycle read 2 windows x 4
-// k-rows, (4 kr + window + rotation) mod 8 all distinct) feed 9 MFMAs of 32 cycles - the same LDS bytes per FLOP as the 16x16x32 form,
-// half the matrix instructions, and the 32x32 shape issues back to back at the pipe's full rate (32 cycles for 32 K FLOP; 16x16x32
-// measures ~17 for 16 K).  MEASURED (profiles/r04_step_experiments.txt item 1): same bits out, 15 % slower launch - kept as an
-// experiment behind g_gemm_variant bit 6, not the default.  Fragment of block `sb` (32 rows), k-step `ks` (of the K-tile): lane l holds row l % 32, k = 8 (l / 32) .. + 7.
-template <int ROWS>
-__device__ __forceinline__ bf16x8_t frag32_mc(const unsigned char* lds, int sb, int ks, int lane) {
-  using T = TileIO<ROWS, true, 512, 64>;
-  const int l15 = lane & 15, g = lane >> 4;
-  const int w = sb * 2 + (g & 1);
-  const int kr0 = ks * 16 + (g >> 1) * 8 + (l15 >> 2), kr1 = kr0 + 4;
-  const int inw = (l15 & 3) * 8;
-  const unsigned char* p0 = lds + kr0 * T::ROWB + (T::mc_lds_win(kr0, w) << 5) + inw;
-  const unsigned char* p1 = lds + kr1 * T::ROWB + (T::mc_lds_win(kr1, w) << 5) + inw;
-  const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS bf16x4_t*)(p0));
-  const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS bf16x4_t*)(p1));
-  bf16x8_t out;
-  out[0] = lo[0]; out[1] = lo[1]; out[2] = lo[2]; out[3] = lo[3];
-  out[4] = hi[0]; out[5] = hi[1]; out[6] = hi[2]; out[7] = hi[3];
-  return out;
-}
-// bf16 store of one 32x32 accumulator block (operands swapped: lane l holds row m = l % 32 and, in register quad q, the columns
-// 8 q + 4 (l / 32) .. + 3): v_permlane32_swap between the two lanes of a row pairs the quads so that every lane owns 8 consecutive
-// columns (16 bytes) of two 16-column groups
-__device__ __forceinline__ void store32_block(const f32x16_t& a, bf16_t* C, int ldc, int M, int N, int mrow, int ncol, int lane) {
-  const int m = mrow + (lane & 31);
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const u32x2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[8 * p + e]), __float_as_uint(a[8 * p + 4 + e]), false, false);
-      v[e] = __uint_as_float(r[0]);
-      v[4 + e] = __uint_as_float(r[1]);
-    }
-    const int n = ncol + 16 * p + 8 * (lane >> 5);
-    if (m < M && n + 8 <= N) stc16(C + (size_t)m * ldc + n, pack8(v));
-    else if (m < M && n < N) {
-      const uint4 pk = pack8(v);
-      *reinterpret_cast<uint2*>(C + (size_t)m * ldc + n) = make_uint2(pk.x, pk.y);   // (N % 8 == 4: the first half of the chunk)
-    }
-  }
-}
-template <int BM, int BN, int NSLOT_ = 0>
-__global__ void __launch_bounds__(512, 2) gemm_ks32_kernel(const GemmGroup g, int total_tiles) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int BK = 64, NT = 512;
-  using TA = TileIO<BM, true, NT, BK>;
-  using TB = TileIO<BN, true, NT, BK>;
-  constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
-  constexpr int STAGE = A_BYTES + B_BYTES;
-  constexpr int NSLOT = NSLOT_ > 0 ? NSLOT_ : persist_slots(STAGE);
-  constexpr int PIECES = TA::PIECES + TB::PIECES;
-  constexpr int MI = BM / 2 / 32, NJ = BN / 2 / 32, H0 = (MI + 1) / 2, H1 = MI - H0;
-  static_assert(BM % 64 == 0 && BN % 64 == 0 && H1 >= 1, "wave tile = whole 32x32 blocks, at least two row blocks");
-  static_assert(!TA::WRAP && !TB::WRAP, "piece lists");
-  // accumulator exchange: the wk = 1 waves hand over H0 row blocks, the wk = 0 waves H1 (float4 units of 1 KiB per wave)
-  constexpr int SEND1 = H0 * NJ * 4, SEND0 = H1 * NJ * 4;
-  static_assert(4 * (SEND0 + SEND1) * 1024 <= NSLOT * STAGE, "accumulator exchange fits in the ring");
-
-  const int G = gridDim.x;
-  const int tile = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);   // XCD-contiguous
-  if (tile >= total_tiles) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wk = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < GGET_MAX_GROUP; ++i)
-    if (i < g.count && tile >= g.p[i].tile_begin) pi = i;
-  const GemmProblem& P = g.p[pi];
-  int m0, n0;
-  tile_origin(P, P.M, tile - P.tile_begin, BM, BN, g.super, m0, n0);
-  const int nk = P.K >> 6;
-
-  f32x16_t acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(LDS_AS const void*)smem) + (unsigned)wave * 1024u;
-  const unsigned char* kA = reinterpret_cast<const unsigned char*>(P.A);
-  const unsigned char* kB = reinterpret_cast<const unsigned char*>(P.B);
-  const long strideA = (long)BK * P.lda * 2, strideB = (long)BK * P.ldb * 2;
-  unsigned offA[TA::PIECES], offB[TB::PIECES];
-#pragma unroll
-  for (int i = 0; i < TA::PIECES; ++i) offA[i] = TA::piece_off(P.lda, m0, P.M, wave, lane, i);
-#pragma unroll
-  for (int i = 0; i < TB::PIECES; ++i) offB[i] = TB::piece_off(P.ldb, n0, P.N, wave, lane, i);
-  int islot = 0, cslot = 0, issued = 0;
-  unsigned islot_off = lds0;
-  auto issue_piece = [&](int q) {
-    if (q < TA::PIECES) glds16m(kA, offA[q < TA::PIECES ? q : 0], islot_off + (unsigned)(q * TA::NWAVES * 1024));
-    else glds16m(kB, offB[q >= TA::PIECES ? q - TA::PIECES : 0], islot_off + (unsigned)(A_BYTES + (q - TA::PIECES) * TB::NWAVES * 1024));
-  };
-  auto issue_advance = [&]() {
-    islot = islot == NSLOT - 1 ? 0 : islot + 1;
-    islot_off = islot == 0 ? lds0 : islot_off + (unsigned)STAGE;
-    kA += strideA;
-    kB += strideB;
-    ++issued;
-  };
-#pragma unroll
-  for (int i = 0; i < NSLOT - 1; ++i) {
-    if (issued < nk) {
-#pragma unroll
-      for (int q = 0; q < PIECES; ++q) issue_piece(q);
-      issue_advance();
-    }
-  }
-  for (int t = 0; t < nk; ++t) {
-    if (issued - t == NSLOT - 1) vm_wait<(NSLOT - 2) * PIECES>();
-    else vm_wait<0>();
-    __syncthreads();
-    const bool did = issued < nk;
-    const unsigned char* a_l = smem + cslot * STAGE;
-    const unsigned char* b_l = a_l + A_BYTES;
-    bf16x8_t af[2][MI], bf[2][NJ];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[s][i] = frag32_mc<BM>(a_l, wm * MI + i, wk * 2 + s, lane);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[s][j] = frag32_mc<BN>(b_l, wn * NJ + j, wk * 2 + s, lane);
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[s][j], af[s][i], acc[i][j], 0, 0, 0);
-        if (did) {
-          constexpr int NG = 2 * MI;
-          const int grp = s * MI + i;
-#pragma unroll
-          for (int q = grp * PIECES / NG; q < (grp + 1) * PIECES / NG; ++q) issue_piece(q);
-        }
-      }
-    if (did) issue_advance();
-    cslot = cslot == NSLOT - 1 ? 0 : cslot + 1;
-  }
-  // ---- add the two K halves: wave (wk = 0) keeps row blocks [0, H0), its partner (wave ^ 4) the blocks [H0, MI)
-  __syncthreads();
-  float4* xch = reinterpret_cast<float4*>(smem);
-  // 1 KiB units: the wk = 1 waves' sends first (SEND1 units each), then the wk = 0 waves' (SEND0 each)
-  auto unit_of = [&](int w, int u) { return (w >= 4 ? (w - 4) * SEND1 : 4 * SEND1 + w * SEND0) + u; };
-  if (wk == 0) {
-#pragma unroll
-    for (int ii = 0; ii < H1; ++ii)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x16_t& v = acc[H0 + ii][j];
-          xch[(size_t)unit_of(wave, (ii * NJ + j) * 4 + q) * 64 + lane] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        }
-  } else {
-#pragma unroll
-    for (int ii = 0; ii < H0; ++ii)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x16_t& v = acc[ii][j];
-          xch[(size_t)unit_of(wave, (ii * NJ + j) * 4 + q) * 64 + lane] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        }
-  }
-  __syncthreads();
-  const int partner = wave ^ 4;
-  bf16_t* C = reinterpret_cast<bf16_t*>(P.C);
-  const int Nst = (P.N + 3) & ~3;
-  if (wk == 0) {
-#pragma unroll
-    for (int ii = 0; ii < H0; ++ii)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        f32x16_t own = acc[ii][j];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 o = xch[(size_t)unit_of(partner, (ii * NJ + j) * 4 + q) * 64 + lane];
-          own[4 * q] += o.x; own[4 * q + 1] += o.y; own[4 * q + 2] += o.z; own[4 * q + 3] += o.w;
-        }
-        store32_block(own, C, P.ldc, P.M, Nst, m0 + wm * (MI * 32) + ii * 32, n0 + wn * (NJ * 32) + j * 32, lane);
-      }
-  } else {
-#pragma unroll
-    for (int ii = 0; ii < H1; ++ii)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        f32x16_t own = acc[H0 + ii][j];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 o = xch[(size_t)unit_of(partner, (ii * NJ + j) * 4 + q) * 64 + lane];
-          own[4 * q] += o.x; own[4 * q + 1] += o.y; own[4 * q + 2] += o.z; own[4 * q + 3] += o.w;
-        }
-        store32_block(own, C, P.ldc, P.M, Nst, m0 + wm * (MI * 32) + (H0 + ii) * 32, n0 + wn * (NJ * 32) + j * 32, lane);
-      }
-  }
-}
-
-template <int BM, int BN, int NSLOT_ = 0>
-int launch_ks32_cfg(GemmGroup& g, int total, hipStream_t st) {
-  constexpr int STG = (BM + BN) * 64 * 2;
-  constexpr int SM = (NSLOT_ > 0 ? NSLOT_ : persist_slots(STG)) * STG;
-  const int G = (total + 7) & ~7;
-  static bool attr0 = false;
-  if (!attr0) {
-    GGET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ks32_kernel<BM, BN, NSLOT_>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SM));
-    attr0 = true;
-  }
-  hipLaunchKernelGGL((gemm_ks32_kernel<BM, BN, NSLOT_>), dim3(G), dim3(512), SM, st, g, total);
-  GGET_LAUNCH_CHECK();
-  return 0;
-}
-
 template <int BM, int BN, bool A_MC, bool B_MC, int EPI, int NSLOT_ = 0, int DW = 8>
 int launch_ks_cfg(GemmGroup& g, int total, hipStream_t st) {
   if constexpr (DW == 8 && BM != 64) {
-    if (!(g_gemm_variant & 128)) return launch_ks_cfg<BM, BN, A_MC, B_MC, EPI, NSLOT_, 4>(g, total, st);
+    if (!(menu().gemm_variant & kGemmKsplitDma8)) return launch_ks_cfg<BM, BN, A_MC, B_MC, EPI, NSLOT_, 4>(g, total, st);
   }
   constexpr int STG = (BM + BN) * 64 * 2;
   constexpr int SM = (NSLOT_ > 0 ? NSLOT_ : persist_slots(STG)) * STG + (A_MC && B_MC && EPI == GGET_EPI_NONE ? 64 : 0);   // (+ the norm partials' scratch)
@@ -1567,12 +1337,13 @@ int launch_persist_cfg(GemmGroup& g, int total, int num_cu, hipStream_t st) {
   static_assert(!SK || (size_t)BM * BN * 4 <= kStreamKSlotBytes, "stream-K slot");
   if constexpr (MODE == 2) {
     static unsigned* cu_slots = nullptr;   // 8 XCC x 256 hardware CU ids, zeroed once (the counters only ever count up)
-    if (!cu_slots && g_gemm_stagger_ticks > 0) {
+    const int stagger = menu().gemm_stagger_ticks;
+    if (!cu_slots && stagger > 0) {
       GGET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cu_slots), 2048 * sizeof(unsigned)));
       GGET_HIP_CHECK(hipMemset(cu_slots, 0, 2048 * sizeof(unsigned)));
     }
     g.cu_slots = cu_slots;
-    g.stagger_ticks = cu_slots ? g_gemm_stagger_ticks : 0;
+    g.stagger_ticks = cu_slots ? stagger : 0;
   }
   int G = total < num_cu && !SK ? total : num_cu;
   G = (G + 7) & ~7;  // the XCD permutation needs a multiple of 8 (idle blocks exit at once)
@@ -1592,7 +1363,7 @@ int launch_persist_cfg(GemmGroup& g, int total, int num_cu, hipStream_t st) {
 thread_local void* t_streamk_ws = nullptr;
 unsigned g_streamk_epoch = 0;
 inline bool streamk_plan(GemmGroup& g, int tiles, int num_cu, int bk) {
-  if (!g_gemm_split_last || !t_streamk_ws || g.count != 1 || (g_gemm_variant & 8)) return false;
+  if (!menu().gemm_split_last || !t_streamk_ws || g.count != 1 || (menu().gemm_variant & kGemmNoSplitLast)) return false;
   const GemmProblem& p = g.p[0];
   if (p.m_dev || p.k_dev || num_cu > 256 || num_cu % 8 != 0) return false;
   const int nk = p.K / bk, G = num_cu;
@@ -1630,10 +1401,12 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
   }
   if (total == 0) return 0;
   constexpr int SMEM = kStages * (BM + BN) * 128;
-  bool persist = split_k <= 1 && EPI != GGET_EPI_ATOMIC_F32 && EPI != GGET_EPI_SLAB_F32 && (!g.ablate || g.ablate >= 8) && getenv("GGET_GEMM_NO_PERSIST") == nullptr;
+  const LaunchMenu& menu = ::menu();
+  const int variant = menu.gemm_variant;
+  bool persist = split_k <= 1 && EPI != GGET_EPI_ATOMIC_F32 && EPI != GGET_EPI_SLAB_F32 && (!g.ablate || g.ablate >= 8) && !menu.gemm_no_persist;
   for (int i = 0; i < g.count; ++i)
-    persist = persist && (g.p[i].m_dev == nullptr || (g.count == 1 && !A_MC && getenv("GGET_GEMM_NO_DYN") == nullptr)) &&
-              (g.p[i].k_dev == nullptr || (g.count == 1 && g.p[i].k_pad_zero && getenv("GGET_GEMM_NO_DYN") == nullptr)) &&
+    persist = persist && (g.p[i].m_dev == nullptr || (g.count == 1 && !A_MC && !menu.gemm_no_dyn)) &&
+              (g.p[i].k_dev == nullptr || (g.count == 1 && g.p[i].k_pad_zero && !menu.gemm_no_dyn)) &&
               (g.p[i].K % 64) == 0 && g.p[i].K >= 64;
   if (persist) {
     const int num_cu = gget_gemm_num_cu();
@@ -1641,7 +1414,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
     // FLOP of the 256x128 tile
     if constexpr (WM == 4 && WN == 2 && !A_MC && EPI != GGET_EPI_SLAB_F32 && EPI != GGET_EPI_ATOMIC_F32 && EPI != GGET_EPI_GEGLU_FWD) {
       long t256 = 0;
-      bool ok256 = getenv("GGET_GEMM_NO_256") == nullptr;
+      bool ok256 = !menu.gemm_no_256;
       for (int i = 0; i < g.count; ++i) {
         t256 += (long)((g.p[i].M + 255) / 256) * ((g.p[i].N + 255) / 256);
         ok256 = ok256 && (g.p[i].N % 256) == 0;
@@ -1652,15 +1425,9 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
       // against 972 = four rounds of 256x128: dxn2 386 -> 343 us, down 216 -> 198, dxn1 143 -> 134, o 70 -> 64; tools/gemm_bench.py)
       const long r256 = (t256 + num_cu - 1) / num_cu, r_cur = (total + num_cu - 1) / num_cu;
       const bool near = 2 * t256 >= 3L * num_cu && r256 * 256 * 256 * 9 <= r_cur * BM * BN * 10;
-      // Round 5 experiment (OFF by default; GGET_GEMM_ONE_ROUND=1 or g_gemm_variant bit 8 turns it on): ONE partial round of 256x256 tiles
-      // instead of two rounds of the default tile when they are the same work per CU - the q|k|v projection on the var-len rows, 5696 x
-      // 2304, is 207 tiles of 256x256 = 81 % of the CUs once, against 414 of 256x128 = two rounds, the second 62 % full.  Measured in the
-      // C1 step, alternated in one process: +0.22 ms (7.000 -> 7.223 ms; profiles/r05_step_experiments.txt item 2) - a 256x256 tile with the
-      // RoPE epilogue (128 accumulator registers per lane rotated and stored behind a 12-K-tile loop) costs more than the second round.
-      static const int one_round_on = getenv("GGET_GEMM_ONE_ROUND") ? atoi(getenv("GGET_GEMM_ONE_ROUND")) : 0;
-      const bool one_round = (one_round_on || (g_gemm_variant & 256)) && t256 <= num_cu && t256 * 10 >= (long)num_cu * 7 && r_cur >= 2 &&
-                             (long)256 * 256 <= r_cur * BM * BN;
-      if (ok256 && ((EPI != GGET_EPI_ROPE && (t256 >= (5 * num_cu) / 2 || near)) || one_round)) {
+      // (not for the RoPE epilogue: one partial round of 256x256 tiles instead of two rounds of the default tile for the q|k|v projection
+      //  measured +0.22 ms in the C1 step - profiles/r05_step_experiments.txt item 2)
+      if (ok256 && EPI != GGET_EPI_ROPE && (t256 >= (5 * num_cu) / 2 || near)) {
         int tot2 = 0;
         for (int i = 0; i < g.count; ++i) {
           GemmProblem& p = g.p[i];
@@ -1671,8 +1438,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
         // row-major B (NT): 64-deep K-tiles through a 2-slot ring (2 x 64 KiB) - half as many barriers / waits / DMA
         // bookkeeping rounds per FLOP as 32-deep tiles through 4 slots (gate|up 91 -> 86 us); the NN form would spill
         if constexpr (!B_MC) {
-          static const int bk64 = getenv("GGET_GEMM_BK64") ? atoi(getenv("GGET_GEMM_BK64")) : 1;
-          if (bk64) return launch_persist_cfg<256, 256, 64, 2, 4, A_MC, B_MC, EPI, 2>(g, tot2, num_cu, st);
+          if (menu.gemm_bk64) return launch_persist_cfg<256, 256, 64, 2, 4, A_MC, B_MC, EPI, 2>(g, tot2, num_cu, st);
         }
         return launch_persist_cfg<256, 256, 32, 2, 4, A_MC, B_MC, EPI>(g, tot2, num_cu, st);
       }
@@ -1680,9 +1446,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
     // 128x192 tile for the N = d outputs (o/down projections and the dgrads into the residual stream): M/128 x N/192
     // tiles fill the chip where 256x128 leaves a quarter of the CUs idle (8192 x 768: 256 tiles vs 192)
     if constexpr (!A_MC && (EPI == GGET_EPI_NONE || EPI == GGET_EPI_RESIDUAL || EPI == GGET_EPI_ROPE)) {
-      static int use192 = -1;
-      if (use192 < 0) { const char* e = getenv("GGET_GEMM_192"); use192 = e ? atoi(e) : 1; }
-      bool ok = use192 != 0;
+      bool ok = menu.gemm_192 != 0;
       long t192 = 0;
       for (int i = 0; i < g.count; ++i) {
         // a ragged last column of tiles only for row-major B (NT: its DMA clamps the B rows) and plain stores
@@ -1701,7 +1465,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
       // small launches keep the tiling they were validated with).
       bool ks_first = false;
       if constexpr (EPI != GGET_EPI_ROPE) {
-        if (ok && !(g_gemm_variant & 1) && cur_rounds == 1 && total * 10 >= (long)num_cu * 3 && !(g_gemm_variant & 512)) {
+        if (ok && !(variant & kGemmNoKsplitNd) && cur_rounds == 1 && total * 10 >= (long)num_cu * 3 && !(variant & kGemmAreaRule)) {
           bool can = true;
           for (int i = 0; i < g.count; ++i) can = can && !g.p[i].m_dev && !g.p[i].k_dev && (g.p[i].N % 192) == 0 && g.p[i].K >= 1536;
           if (can)
@@ -1721,8 +1485,8 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
           tot3 += ((p.M + 127) / 128) * p.tiles_n;
         }
         if constexpr (EPI != GGET_EPI_ROPE) {
-          // one tile per CU, nothing device-sized: the K-split arrangement of the tile (g_gemm_variant bit 0 turns it off)
-          bool ks = tot3 <= num_cu && !(g_gemm_variant & 1);
+          // one tile per CU, nothing device-sized: the K-split arrangement of the tile (kGemmNoKsplitNd turns it off)
+          bool ks = tot3 <= num_cu && !(variant & kGemmNoKsplitNd);
           // (K >= 1536: with only 12 K-tiles the accumulator exchange costs what the lighter fragment traffic saves - measured again in
           //  round 3 with the 96-row tiles: K = 768 launches through this kernel left the C1 step unchanged, 7.44-7.48 ms either way)
           for (int i = 0; i < g.count; ++i)
@@ -1730,10 +1494,10 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
           if (ks) {
             // Rows per tile: the smallest of 64 / 96 / 128 whose tiles still fit in ONE round - more, smaller tiles keep more CUs
             // busy for a shorter time (var-len token layout: 5 696 x 768 is 180 tiles of 128 rows = 70 % of the CUs, 240 tiles of 96
-            // rows = 94 % at 3/4 of the work each; the padded 8 192 x 768 stays at 256 tiles of 128 rows).  g_gemm_variant bit 4:
+            // rows = 94 % at 3/4 of the work each; the padded 8 192 x 768 stays at 256 tiles of 128 rows).  kGemmKsplit128Only:
             // 128 rows only.
             int bm = 128;
-            if (!(g_gemm_variant & 16))
+            if (!(variant & kGemmKsplit128Only))
               for (int cand : {64, 96}) {
                 long t = 0;
                 for (int i = 0; i < g.count; ++i) t += (long)((g.p[i].M + cand - 1) / cand) * (g.p[i].N / 192);
@@ -1746,11 +1510,11 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
               p.tile_begin = tot;
               tot += ((p.M + bm - 1) / bm) * p.tiles_n;
             }
-            // g_gemm_lds_headroom (gget_debug_set key 2 / GGET_GEMM_LDS_HEADROOM): 3 ring slots instead of 4, so that a
+            // gemm_lds_headroom (menu key 2): 3 ring slots instead of 4, so that a
             // collective's workgroup (a few KiB of LDS) can share the CU with the GEMM block
             if (bm == 64) return launch_ks_cfg<64, 192, A_MC, B_MC, EPI, 3>(g, tot, st);
             if (bm == 96) return launch_ks_cfg<96, 192, A_MC, B_MC, EPI, 3>(g, tot, st);
-            if (g_gemm_lds_headroom) return launch_ks_cfg<128, 192, A_MC, B_MC, EPI, 3>(g, tot, st);
+            if (menu.gemm_lds_headroom) return launch_ks_cfg<128, 192, A_MC, B_MC, EPI, 3>(g, tot, st);
             return launch_ks_cfg<128, 192, A_MC, B_MC, EPI>(g, tot, st);
           }
         }
@@ -1759,7 +1523,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
             return launch_persist_cfg<128, 192, 64, 4, 2, A_MC, B_MC, EPI, 3, true>(g, tot3, num_cu, st);
           }
         }
-        if (g_gemm_lds_headroom) return launch_persist_cfg<128, 192, 64, 4, 2, A_MC, B_MC, EPI, 3>(g, tot3, num_cu, st);
+        if (menu.gemm_lds_headroom) return launch_persist_cfg<128, 192, 64, 4, 2, A_MC, B_MC, EPI, 3>(g, tot3, num_cu, st);
         return launch_persist_cfg<128, 192, 64, 4, 2, A_MC, B_MC, EPI>(g, tot3, num_cu, st);
       }
     }
@@ -1767,9 +1531,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
     // (gate|up 6144x768, down 768x3072, q|k|v 2304x768, o 768x768) are exactly 256 such tiles - one per CU, full K,
     // no split-K slabs.  Taken whenever it needs less per-CU work than the 256x128 tiling.
     if constexpr (A_MC && B_MC && EPI == GGET_EPI_NONE) {
-      static int use192 = -1;
-      if (use192 < 0) { const char* e = getenv("GGET_GEMM_192"); use192 = e ? atoi(e) : 1; }
-      bool ok = use192 != 0;
+      bool ok = menu.gemm_192 != 0;
       long t192 = 0;
       for (int i = 0; i < g.count; ++i) {
         ok = ok && (g.p[i].N % 192) == 0 && (g.p[i].M % 192) == 0;
@@ -1784,12 +1546,11 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
           p.tile_begin = tot4;
           tot4 += (p.M / 192) * p.tiles_n;
         }
-        if (tot4 <= num_cu && !(g_gemm_variant & 2)) {
+        if (tot4 <= num_cu && !(variant & kGemmNoKsplitWgrad)) {
           bool ks = true;
           for (int i = 0; i < g.count; ++i) ks = ks && !g.p[i].m_dev && !g.p[i].k_dev;
-          // g_gemm_variant bit 6: the 32x32x16 MFMA form (gemm_ks32_kernel, round 4) - bit-identical results, measured SLOWER in the step
-          // (7.285 against 7.119 ms, same box, alternated: profiles/r04_step_experiments.txt item 1), so the 16x16x32 form stays the default
-          if (ks && (g_gemm_variant & 64)) return launch_ks32_cfg<192, 192>(g, tot4, st);
+          // (a 32x32x16 MFMA form of this kernel gave the same bits and ran SLOWER in the step - 7.285 against 7.119 ms, same box,
+          //  alternated: profiles/r04_step_experiments.txt item 1 - and was removed)
           if (ks) {
             g.sq_written = g.sq_partials != nullptr;
             return launch_ks_cfg<192, 192, true, true, EPI>(g, tot4, st);
@@ -1802,7 +1563,7 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
     // - the var-len token layout: M = real tokens, e.g. 5 696 instead of 8 192 - leaves the last round of 256-row tiles mostly
     // empty; rounds x rows decides (8192 x 3072: 3 x 256 against 5 x 192 -> 256; 5696 x 3072: 3 x 256 against 3 x 192 -> 192)
     if constexpr (WM == 4 && WN == 2 && !A_MC && (EPI == GGET_EPI_GEGLU_BWD || EPI == GGET_EPI_NONE || EPI == GGET_EPI_RESIDUAL)) {
-      bool ok = !(g_gemm_variant & 4);
+      bool ok = !(variant & kGemmNo192Rows);
       long t192 = 0;
       for (int i = 0; i < g.count; ++i) {
         ok = ok && !g.p[i].m_dev && !g.p[i].k_dev && (g.p[i].N % BN) == 0;
@@ -1819,13 +1580,13 @@ int launch_t(GemmGroup& g, int split_k, hipStream_t st) {
           p.tile_begin = tot5;
           tot5 += ((p.M + 191) / 192) * p.tiles_n;
         }
-        // the GEGLU' launch: two blocks per CU (kernel comment, MODE 2); g_gemm_variant bit 5: one block per CU as everywhere else
-        // (g_gemm_lds_headroom 2 = a collective's kernel shares the chip, data-parallel runs: the two blocks fill a CU's LDS and a foreign
+        // the GEGLU' launch: two blocks per CU (kernel comment, MODE 2); kGemmOneBlockPerCu: one block per CU as everywhere else
+        // (gemm_lds_headroom 2 = a collective's kernel shares the chip, data-parallel runs: the two blocks fill a CU's LDS and a foreign
         //  workgroup on a CU would push one of them into a second round - one block per CU with a 3-slot ring then)
         if constexpr (EPI == GGET_EPI_GEGLU_BWD && BN == 128) {
-          if (!(g_gemm_variant & 32) && g_gemm_lds_headroom < 2) return launch_persist_cfg<192, BN, 64, WM, WN, A_MC, B_MC, EPI, 2, false, 2>(g, tot5, num_cu, st);
+          if (!(variant & kGemmOneBlockPerCu) && menu.gemm_lds_headroom < 2) return launch_persist_cfg<192, BN, 64, WM, WN, A_MC, B_MC, EPI, 2, false, 2>(g, tot5, num_cu, st);
         }
-        if (g_gemm_lds_headroom) return launch_persist_cfg<192, BN, 64, WM, WN, A_MC, B_MC, EPI, 3>(g, tot5, num_cu, st);
+        if (menu.gemm_lds_headroom) return launch_persist_cfg<192, BN, 64, WM, WN, A_MC, B_MC, EPI, 3>(g, tot5, num_cu, st);
         return launch_persist_cfg<192, BN, 64, WM, WN, A_MC, B_MC, EPI>(g, tot5, num_cu, st);
       }
     }
@@ -1883,7 +1644,7 @@ int launch_mode(GemmGroup& g, int epi, int split_k, hipStream_t st) {
         // (192-row tiles when they need fewer rounds x rows than 256-row tiles - see launch_t)
         long t192 = 0;
         for (int i = 0; i < g.count; ++i) t192 += (long)((g.p[i].M + 191) / 192) * (g.p[i].N / 256);
-        if (!(g_gemm_variant & 4) && ((t192 + num_cu - 1) / num_cu) * 192 * 100 < ((total + num_cu - 1) / num_cu) * 256 * 92) {   // (margin: see launch_t)
+        if (!(menu().gemm_variant & kGemmNo192Rows) && ((t192 + num_cu - 1) / num_cu) * 192 * 100 < ((total + num_cu - 1) / num_cu) * 256 * 92) {   // (margin: see launch_t)
           int tot2 = 0;
           for (int i = 0; i < g.count; ++i) {
             GemmProblem& p = g.p[i];
@@ -1914,19 +1675,9 @@ int gget_gemm_launch(int mode, int epi, GemmGroup& g, int split_k, hipStream_t s
   g.sk_rounds = g.sk_rem = g.sk_a = 0; g.sk_parts = 1;
   g.cu_slots = nullptr; g.stagger_ticks = 0;
   g.sq_written = 0;
-  static int ablate = -1;
-  if (ablate < 0) {
-    const char* e = getenv("GGET_GEMM_ABLATE");
-    ablate = e ? atoi(e) : 0;
-    if (const char* v = getenv("GGET_GEMM_VARIANT")) g_gemm_variant = atoi(v);
-    if (const char* v = getenv("GGET_GEMM_LDS_HEADROOM")) g_gemm_lds_headroom = atoi(v);
-    if (const char* v = getenv("GGET_GEMM_SPLIT_LAST")) g_gemm_split_last = atoi(v);   // same knob as gget_debug_set(1, .), for whole-step A/B
-    if (const char* v = getenv("GGET_GEMM_STAGGER")) g_gemm_stagger_ticks = atoi(v);
-  }
-  g.ablate = g_gemm_ablate_set >= 0 ? g_gemm_ablate_set : ablate;
-  static int super = -1;
-  if (super < 0) { const char* e = getenv("GGET_GEMM_SUPER"); super = e ? atoi(e) : 0; }
-  g.super = super > 0 ? super : (mode == GGET_GEMM_TN ? 1 : kSuper);
+  const LaunchMenu& m = menu();
+  g.ablate = m.gemm_ablate > 0 ? m.gemm_ablate : 0;
+  g.super = m.gemm_super > 0 ? m.gemm_super : (mode == GGET_GEMM_TN ? 1 : kSuper);
   GGET_REQUIRE(split_k <= 1 || epi == GGET_EPI_ATOMIC_F32 || epi == GGET_EPI_SLAB_F32,
                "gemm: split-K needs the fp32 atomic or slab epilogue");
   for (int i = 0; i < g.count; ++i) {

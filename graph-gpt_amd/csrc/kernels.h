@@ -42,10 +42,6 @@ inline bool k_embed_dense_ok(int V, bool gated) { return !gated && ((V + 63) / 6
 constexpr int kEmbDenseSplit = 8;   // K slices (fp32 slabs of V*d each) of that GEMM
 int k_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int T, int d, float eps, hipStream_t st);
 // dw_accum: fp32 [copies][copy_stride] accumulators (see GgetSegment); copies = 1 for a plain vector
-void k_set_deterministic(int on);   // reproducible summation order of the RMSNorm weight gradients (gget_debug_set key 4)
-void k_set_rms_wide(int on);   // 1 (default): short RMSNorm backward launches run one 16-wave block per CU (kernels.hip rmsnorm_bwd_kernel)
-void k_set_ce_parts(int on);    // 1 (default): ce_rows_kernel leaves one partial loss sum per block where the caller has the slots (no same-address atomics)
-int k_get_deterministic();
 // reproducible mode: the scratch of the block-ordered weight-gradient sums (grown on demand; its users run in stream order)
 int k_det_scratch(size_t floats, float** out);
 // dst[j] += part[0][j] + part[1][j] + ... + part[nblk - 1][j] in a fixed order (two launches); part holds nblk rows of d floats followed by

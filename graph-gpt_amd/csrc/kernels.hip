@@ -5,9 +5,6 @@
 #include "common.h"
 #include "kernels.h"
 
-static int g_deterministic = getenv("GGET_DETERMINISTIC") ? atoi(getenv("GGET_DETERMINISTIC")) : 0;   // k_set_deterministic
-static int g_rms_bwd_wide = getenv("GGET_RMS_WIDE") ? atoi(getenv("GGET_RMS_WIDE")) : 1;   // k_set_rms_wide (gget_debug_set key 13)
-static int g_ce_parts = getenv("GGET_CE_PARTS") ? atoi(getenv("GGET_CE_PARTS")) : 1;         // k_set_ce_parts (gget_debug_set key 14)
 static float* g_det_scratch = nullptr;
 static size_t g_det_bytes = 0;
 
@@ -650,7 +647,7 @@ __global__ void __launch_bounds__(NW * 64) rmsnorm_bwd_wide_kernel(const bf16_t*
   }
 }
 
-// reproducible mode (k_set_deterministic): dst[j] += part[0][j] + part[1][j] + ... in block order (one thread per column)
+// reproducible mode (menu().deterministic): dst[j] += part[0][j] + part[1][j] + ... in block order (one thread per column)
 // A fixed order, not the sequential one: the rows are cut into segments of `per` (one block each), the four waves of a block interleave a
 // segment's rows and every lane keeps 8 running sums (32 coalesced row reads in flight per block); lane sums, wave sums and - in a
 // second launch over the segment sums - the segments are folded in fixed trees.
@@ -2308,16 +2305,16 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
   GGET_REQUIRE(d % 8 == 0 && d <= 64 * 8 * kMaxChunksPerLane, "rmsnorm: d=%d unsupported", d);
   if (T == 0) return 0;
   if (copies < 1) copies = 1;
-  static int rpw = 0;
-  if (!rpw) { const char* e = getenv("GGET_RMS_ROWS"); rpw = e ? atoi(e) : 4; }
+  const LaunchMenu& m = menu();
+  const int rpw = m.rms_rows;
   const int grid = grid_for(T, 4 * rpw, 4096);  // rows per wave: amortises the dw atomics, pipelined row loads
   // Reproducible mode: the per-block partials of the weight gradient go to a scratch matrix and are summed in block order (the
   // fp32 atomics into the replicated accumulators are the one unordered sum of the pre-train gradient path: DESIGN.md section 5).
   float* part = nullptr;
-  if (g_deterministic) {     // per-block partials [4096][d] + segment sums [64][d]
+  if (m.deterministic) {     // per-block partials [4096][d] + segment sums [64][d]
     if (int e = k_det_scratch((size_t)(4096 + 64) * d, &part)) return e;
   }
-  // short launches (<= 4 rows per wave of a 16-wave block per CU): the one-block-per-CU form (kernel comment); GGET_RMS_WIDE=0 / gget_debug_set(13, 0)
+  // short launches (<= 4 rows per wave of a 16-wave block per CU): the one-block-per-CU form (kernel comment); menu().rms_wide = 0
   // = the 4-wave blocks everywhere
   static int n_cu = 0;
   if (!n_cu) {
@@ -2328,7 +2325,7 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
     n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
   int wgrid = grid;
-  if (d <= 1024 && g_rms_bwd_wide && T <= n_cu * 16 * 4) {
+  if (d <= 1024 && m.rms_wide && T <= n_cu * 16 * 4) {
     wgrid = (T + 15) / 16 < n_cu ? (T + 15) / 16 : n_cu;
     static bool attr_done = false;
     if (!attr_done) {
@@ -2347,8 +2344,6 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
   if (part) return k_ordered_colsum(part, wgrid, d, dw_accum, st);
   return 0;
 }
-
-void k_set_deterministic(int on) { g_deterministic = on; }
 
 int k_det_scratch(size_t floats, float** out) {
   if (g_det_bytes < floats * sizeof(float)) {
@@ -2371,9 +2366,6 @@ int k_ordered_colsum(float* part, int nblk, int d, float* dst, hipStream_t st) {
   GGET_LAUNCH_CHECK();
   return 0;
 }
-void k_set_rms_wide(int on) { g_rms_bwd_wide = on; }
-void k_set_ce_parts(int on) { g_ce_parts = on; }
-int k_get_deterministic() { return g_deterministic; }
 
 int k_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H,
            int inverse, hipStream_t st) {
@@ -2685,11 +2677,11 @@ int k_gather_rows_remap(const void* src, int32_t* idx, const int32_t* count, con
 int k_ce_fwd_bwd(const void* logits, int ld, const int32_t* labels, const int32_t* sel_tok, const float* sample_wgt, int S,
                  const int32_t* n_rows_dev, int n_rows_cap, int V, float* loss_sum, void* dlogits, float scale_base,
                  int mean_over_rows, float* loss_out, hipStream_t st, float focal_gamma, float* loss_part, int loss_part_cap) {
-  const bool vec = (ld % 8) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dlogits & 15) == 0 && getenv("GGET_CE_GENERIC") == nullptr;
+  const bool vec = (ld % 8) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dlogits & 15) == 0 && !menu().ce_generic;
   const dim3 grid(grid_for(n_rows_cap, 4 * 8, 2048));
   // per-block partial sums instead of same-address atomics: the row-in-registers kernels, when the caller has a slot per block
-  // (gget_debug_set(14, 0): atomics everywhere)
-  const bool parts = g_ce_parts && loss_part && n_rows_cap > 0 && vec && ld <= 2048 && (int)grid.x <= loss_part_cap;
+  // (menu().ce_parts = 0: atomics everywhere)
+  const bool parts = menu().ce_parts && loss_part && n_rows_cap > 0 && vec && ld <= 2048 && (int)grid.x <= loss_part_cap;
   if (!parts) GGET_HIP_CHECK(hipMemsetAsync(loss_sum, 0, sizeof(float), st));
   if (n_rows_cap > 0) {
     float* lp = parts ? loss_part : nullptr;

@@ -269,6 +269,10 @@ class Engine:
         self._raw_keep = raw_embeds.to(device=self.device, dtype=torch.float32).contiguous()
         L.check(self.lib.gget_set_raw_embeds(self.h, _ptr(self._raw_keep), int(bool(first_label_only))))
 
+    def set_dp_menu(self, reserve_cus: int = 0, lds_headroom: bool = False):
+        """The data-parallel share of the launch menu, carried by this handle (gget_set_dp_menu): (0, False) = the single-GPU selection."""
+        L.check(self.lib.gget_set_dp_menu(self.h, int(reserve_cus), int(bool(lds_headroom))))
+
     def set_rope_range(self, rope_range: float):
         """config.rope_range: > 0 rescales the position ids of a forward to [0, rope_range) per row (per-token rotary angles)."""
         L.check(self.lib.gget_set_rope_range(self.h, float(rope_range)))

@@ -199,6 +199,7 @@ class _GgetModel(nn.Module):
         self.dropout_seed, self._drop_step = seed, 0
         self.materialize_grads = True   # fill nn.Parameter.grad (fp32) after backward, like autograd would
         self._token_layout = "auto"
+        self._dp_menu = (0, False)      # (reserve_cus, lds_headroom) of every handle this model creates: set_dp_menu
         self._dirty = False             # master weights changed behind the engine's back (external optimizer)
         state = make_state_dict(self.spec, seed=seed, std=config.initializer_range)
         # module tree with the reference's attribute paths: model.embed_tokens / model.layers[i].* / model.norm ...
@@ -249,6 +250,12 @@ class _GgetModel(nn.Module):
         self._token_layout = value
         if self._engine is not None:
             self._engine.varlen_mode = self._LAYOUTS[value]
+
+    def set_dp_menu(self, reserve_cus: int = 0, lds_headroom: bool = False):
+        """The data-parallel share of the launch menu (Engine.set_dp_menu) for the live handle and every one created after it."""
+        self._dp_menu = (max(0, int(reserve_cus)), bool(lds_headroom))
+        if self._engine is not None:
+            self._engine.set_dp_menu(*self._dp_menu)
 
     def gradient_checkpointing_enable(self, *a, **k):
         return None  # activations for 288 GB HBM are kept; recompute is never needed on this path
@@ -315,6 +322,7 @@ class _GgetModel(nn.Module):
             new.sync_params()
         new.set_stack_method(getattr(self.config, "stack_method", None) == "long")
         new.set_rope_range(float(getattr(self.config, "rope_range", 0) or 0))
+        new.set_dp_menu(*self._dp_menu)
         new.varlen_mode = self._LAYOUTS[self._token_layout]
         self._engine = new
         self._anchor = torch.zeros(1, device=new.device, requires_grad=True)

@@ -259,8 +259,10 @@ class GgetEngine:
         # measurement switch (bench.py `dp.exposed_comm_ms`): False runs the same staged backward WITHOUT issuing the collectives -
         # the ranks then drift apart, so it is only ever set for a few untimed-for-throughput diagnostic steps
         self.exchange = True
+        # the data-parallel share of the launch menu, carried by the model's handle (set_dp_menu below):
+        # GGET_DP_LDS_HEADROOM=1 opts in to the LDS-headroom menu of rounds 2 - 4, GGET_DP_RESERVE_CUS=R leaves R CUs to the collective
+        self._dp_lds_headroom = bool(int(os.environ.get("GGET_DP_LDS_HEADROOM", "0")))
         self.reserved_cus = 0
-        self._dp_menu_set = False      # this engine switched the process-wide GEMM launch menu (gget_debug_set keys 2 / 13 / 15): close() restores it
         # gradient accumulation (DeepSpeed branch, conf_utils.py:59-66 -> the DS engine steps at the boundary only): the micro-batches'
         # gradients are summed in an fp32 copy of the flat gradient array; step() k - 1 times out of k only does that
         self.micro_steps = 0
@@ -270,50 +272,20 @@ class GgetEngine:
         self.skip_nonfinite = False
         self.skipped_steps = 0
         if self.world > 1 and torch.cuda.is_available():
-            # a collective's kernel shares the chip with the compute stream from now on: the GEMM launcher keeps LDS headroom on every
-            # CU (no launch with two LDS-filling workgroups per CU; gget_debug_set key 2)
-            from . import _lib as L
-            # (rounds 2 - 4 set this for every multi-rank job; round 5's stand-in with RCCL's real register footprint - tools/dp_standin.py -
-            #  shows the rule buys nothing against such a kernel and costs 0.08 ms alone, 0.2 ms beside it: opt-in now, GGET_DP_LDS_HEADROOM=1)
-            if bool(int(os.environ.get("GGET_DP_LDS_HEADROOM", "0"))):
-                L.check(L.load().gget_debug_set(2, 2))
-                self._dp_menu_set = True
-            # (superseded below, in a real multi-process job, by the stronger rule: CUs of their own for the collective - the two-per-CU launch
-            #  returns then, and the per-sample backward runs whenever its grid fits the CUs that are left)
-            # ... and, in a real multi-process job that asks for it, the GEMM launches leave GGET_DP_RESERVE_CUS CUs (default 0 = off) FREE for the
-            # collective's workgroups, which are held to as many channels (NCCL_MAX_NCHANNELS, unless the user set it): an RCCL workgroup
-            # (256 threads x 261 - 280 registers, 19.7 KiB LDS) cannot share a CU with any 8-wave GEMM workgroup, and a GEMM launch that finds
-            # one of "its" CUs taken runs a second round (csrc/gemm.hip g_gemm_cu_reserve).  The RMSNorm backward goes
-            # back to its many-small-blocks form for the same reason.
+            # a collective's kernel shares the chip with the compute stream from now on.  (Rounds 2 - 4 kept LDS headroom on every CU for
+            # every multi-rank job; round 5's stand-in with RCCL's real register footprint - tools/dp_standin.py - shows the rule buys
+            # nothing against such a kernel and costs 0.08 ms alone, 0.2 ms beside it: opt-in now.)  In a real multi-process job that asks
+            # for it, the GEMM launches leave GGET_DP_RESERVE_CUS CUs (default 0 = off) FREE for the collective's workgroups, which are held
+            # to as many channels (NCCL_MAX_NCHANNELS, unless the user set it; dp_env_defaults() sets it ahead of init_process_group): an
+            # RCCL workgroup (256 threads x 261 - 280 registers, 19.7 KiB LDS) cannot share a CU with any 8-wave GEMM workgroup, and a GEMM
+            # launch that finds one of "its" CUs taken runs a second round (csrc/gemm.hip).  That rule supersedes the
+            # LDS headroom; the RMSNorm backward goes back to its many-small-blocks form for the same reason.
             real_world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
             if real_world > 1:
                 self.reserved_cus = max(0, int(os.environ.get("GGET_DP_RESERVE_CUS", "0")))
-                if self.reserved_cus:
-                    # (NCCL_MAX_NCHANNELS is read when the communicator is created - before this constructor runs: dp_env_defaults()
-                    #  sets it, from the same variable, ahead of init_process_group; bench.py and set_dist_env call it)
-                    L.check(L.load().gget_debug_set(15, self.reserved_cus))
-                    L.check(L.load().gget_debug_set(13, 0))
-                    L.check(L.load().gget_debug_set(2, 1))
-                    self._dp_menu_set = True
+            model.set_dp_menu(self.reserved_cus, self._dp_lds_headroom)
         model.materialize_grads = False  # fused path: gradients stay in the flat bf16 arena
         model._managed_by_engine = True  # the bucketed exchange below replaces the all-reduce of _autograd_backward
-
-    def close(self):
-        """Give back what this engine changed process-wide: the data-parallel GEMM launch menu (keys 2 / 13 / 15 of gget_debug_set are
-        globals of the library, not of a handle - ADVICE r5) goes back to the single-GPU defaults.  Idempotent; also run when the object dies."""
-        if getattr(self, "_dp_menu_set", False):
-            self._dp_menu_set = False
-            try:
-                from . import _lib as L
-                lib = L.load()
-                lib.gget_debug_set(15, 0)
-                lib.gget_debug_set(13, 1)
-                lib.gget_debug_set(2, 0)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self.close()
 
     @property
     def device(self):
@@ -514,15 +486,9 @@ class GgetEngine:
         of GGET_DP_RESERVE_CUS; the collective library's channel count is fixed when its communicator is created - dp_env_defaults)."""
         if overlap is not None:
             self.overlap = bool(overlap)
-        if reserve_cus is not None and torch.cuda.is_available():
-            from . import _lib as L
-            lib = L.load()
-            r = max(0, int(reserve_cus))
-            L.check(lib.gget_debug_set(15, r))
-            L.check(lib.gget_debug_set(13, 0 if r else 1))
-            L.check(lib.gget_debug_set(2, 1 if r else (2 if bool(int(os.environ.get("GGET_DP_LDS_HEADROOM", "0"))) else 0)))
-            self.reserved_cus = r
-            self._dp_menu_set = self._dp_menu_set or r > 0
+        if reserve_cus is not None:
+            self.reserved_cus = max(0, int(reserve_cus))
+            self.module.set_dp_menu(self.reserved_cus, self._dp_lds_headroom)
 
     def probe_dp_menu(self, step_fn: Callable[[], Any], steps: int = 10, warm: int = 2, menus=None) -> Dict[str, Any]:
         """No 1 -> 8 GPU curve of this engine has been measured: instead of a default chosen from a model, a
@@ -1016,7 +982,7 @@ def dp_env_defaults() -> int:
     """Environment a multi-process job wants BEFORE its process group / communicator exists: the collective library is held to as many
     channels (= workgroups) as the GEMM launches leave CUs free - GGET_DP_RESERVE_CUS = R, OFF by default (0: tools/dp_standin.py measured that
     16 free CUs do not protect the exact-fit launches and that 32 cost more than the collisions they prevent at the 8-GPU residency of the
-    collectives); an NCCL_MAX_NCHANNELS the user set wins.  Returns R (GgetEngine applies the GEMM side: gget_debug_set(15, R))."""
+    collectives); an NCCL_MAX_NCHANNELS the user set wins.  Returns R (GgetEngine applies the GEMM side: the handle's data-parallel menu)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     r = max(0, int(os.environ.get("GGET_DP_RESERVE_CUS", "0"))) if world > 1 else 0
     if r:

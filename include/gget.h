@@ -265,6 +265,14 @@ int gget_backward_end(gget_handle_t h, void* stream);
  *   1-based step count for the skipped step).  Off by default: DeepSpeed's bf16 optimizer, the path the engine reproduces, has no such guard. */
 #define GGET_OPT_SKIP_NONFINITE_STEP 2
 int gget_set_option(gget_handle_t h, int option, int value);
+/* The data-parallel share of the launch menu, carried by the handle: during this handle's forward / backward calls its launches plan with
+ * the process menu (gget_debug_set) overlaid by these fields.  reserve_cus = R > 0: every GEMM plan counts the device's CUs minus R
+ * (rounded down to a multiple of 8), which leaves R CUs to the collective library's workgroups (these cannot share a CU with a GEMM
+ * workgroup); the 128x192 / 192x128 tiles keep their 3-slot rings and the short RMSNorm backward launches take the 4-wave blocks.
+ * lds_headroom != 0 with reserve_cus = 0: no GEMM launch with two LDS-filling workgroups per CU and the three-launch S <= 32 backward,
+ * so that a collective's workgroup can share a CU.  (0, 0), the state of a new handle: the process menu as it is,
+ * i.e. the single-GPU selection.  Op-level entries (gget_op_*) always see the process menu. */
+int gget_set_dp_menu(gget_handle_t h, int reserve_cus, int lds_headroom);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange.  replaces: the DDP gradient all-reduce (src/utils/opt_utils.py:13),
@@ -396,23 +404,33 @@ uint64_t gget_op_gemm_streamk_bytes(void);
  * exactly 256 tiles of 192x192 for d = 768, one per CU */
 int gget_op_gemm_grouped(int mode, int count, const void* const* A, const void* const* B, void* const* C, const int* M,
                          const int* N, const int* K, const int* lda, const int* ldb, const int* ldc, void* stream);
-/* measurement knob (tools/ and tests; no reference counterpart).  key 1 = bit mask that switches GEMM kernel variants OFF, so that
- * two selections can be timed interleaved in one process or pinned to the same summation order (0 = the shipped selection): 1 K-split
- * kernel for one-round N = d launches, 2 K-split kernel for the grouped weight gradients, 4 the 192-row tiles, 8 the split of the
- * last round, 16 the 64- / 96-row tiles of the K-split kernel, 32 two co-resident workgroups per CU for the dh + GEGLU' launch.  key 2 = LDS headroom of the 128x192 tile (0: 4-slot ring).
+/* measurement knobs (tools/ and tests; no reference counterpart): the process launch menu, one row per knob in csrc/menu.h kMenuRows
+ * (INTEGRATION.md "Kernel-selection knobs" lists them).  The environment sets the initial values when the library loads; these two read and
+ * write a knob by its key afterwards, and a value written before the first launch holds.  Both return 2 and set gget_last_error for a key
+ * that is not in the table.
+ * key 1 = bit mask of GEMM kernel variants, 0 = the shipped selection.  Bits that switch a variant OFF: 1 kGemmNoKsplitNd (the K-split
+ *   kernel for one-round N = d launches), 2 kGemmNoKsplitWgrad (the K-split kernel for the grouped weight gradients), 4 kGemmNo192Rows (the
+ *   192-row tiles), 8 kGemmNoSplitLast (the split of the last round), 16 kGemmKsplit128Only (the 64- / 96-row tiles of the K-split kernel),
+ *   32 kGemmOneBlockPerCu (two co-resident workgroups per CU for the dh + GEGLU' launch).  Bits that switch a variant ON: 128
+ *   kGemmKsplitDma8 (all eight waves of the K-split kernel issue its LDS-DMA), 512 kGemmAreaRule (N = d launches keep the default tiling
+ *   whenever its rounds x area is the smaller one).
+ * key 2 = LDS headroom of the 128x192 / 192x128 tiles: 1 (default) 3-slot rings, 0 4-slot rings, 2 also no launch with two LDS-filling
+ *   workgroups per CU.
  * key 3 = 1: split the K range of the last, partial round's tiles among the idle workgroups (off by default).
  * key 4 = 1 (also env GGET_DETERMINISTIC=1): reproducible mode of the pre-train step - the RMSNorm weight gradients, the one sum of that
- * gradient path added with fp32 atomics, are summed in block order instead (same kernel selection, the per-sample kernels included); two
- * runs then produce bit-identical parameters.
+ *   gradient path added with fp32 atomics, are summed in block order instead (same kernel selection, the per-sample kernels included); two
+ *   runs then produce bit-identical parameters.
+ * key 5 = start delay, in 100 MHz ticks, of a CU's second workgroup in the two-per-CU GEMM launches.  key 7 = GEMM ablation bits (timing
+ *   only; 0 = none).  key 8 = 1: the dense SMTP head.  key 9 = 128 / 256: its slot tile rows.
  * key 10 = 1: the per-sample kernels of S <= 32 off (the three launches each replaces run).  key 11 = 1: the fused RMSNorm + LayerScale
- * backward in its 16-byte-chunk form for every width (0: the 8-byte, all-lanes form for d = 512 / 768 / 1024).
+ *   backward in its 16-byte-chunk form for every width (0: the 8-byte, all-lanes form for d = 512 / 768 / 1024).
  * key 13 = 0: the RMSNorm backward of short launches (<= 64 rows per CU) in 4-wave blocks as everywhere else (1, default: one 16-wave block
- * per CU, same bits).  key 14 = 0: the engine's cross-entropy launch adds its loss with one atomic per block (1, default: one partial sum
- * per block, summed in block order by the finalising launch).  key 15 = R: every GEMM launch plan (tile shapes, persistent grids, split-K
- * fits) counts the device's CUs minus R - data-parallel runs leave R CUs to the collective library's workgroups, which cannot share a CU
- * with a GEMM workgroup (0, default: the whole chip).  key 16 = 1: gget_debug_occupy's stand-in takes the register footprint of RCCL's
- * kernel (264 registers per lane) besides the LDS asked for. */
+ *   per CU, same bits).  key 14 = 0: the engine's cross-entropy launch adds its loss with one atomic per block (1, default: one partial sum
+ *   per block, summed in block order by the finalising launch).  key 15 = R: every GEMM launch plan counts the device's CUs minus R (0,
+ *   default: the whole chip; a data-parallel handle sets its own with gget_set_dp_menu).  key 16 = 1: gget_debug_occupy's stand-in takes
+ *   the register footprint of RCCL's kernel (264 registers per lane) besides the LDS asked for. */
 int gget_debug_set(int key, int value);
+int gget_debug_get(int key, int* value);
 /* measurement aid: with enable != 0 the engine brackets, with HIP events on the launch stream, the grouped weight-gradient launch
  * (avg_ms_out[0]) and the gate|up + GEGLU launch (avg_ms_out[1]) of every layer of the following forward / backward calls;
  * avg_ms_out (may be NULL) receives the mean durations recorded so far.  bench.py uses it for the roofline of the dominant kernel

@@ -87,3 +87,27 @@ def test_lr_schedule_host_logic():
                             schedule="onecycle")
         got = [oc.lr_at(s) for s in range(int(total))]
         np.testing.assert_allclose(got, z["onecycle_" + tag], rtol=1e-9, atol=1e-15)
+
+
+def test_launch_menu_keys_round_trip(lib):
+    """gget_debug_set / gget_debug_get: every key of the menu table (csrc/menu.h kMenuRows) reads back what was written and is restored;
+    a key that is not in the table is refused with an error, not ignored."""
+    src = open(os.path.join(ROOT, "graph-gpt_amd", "csrc", "menu.h")).read()
+    keys = sorted({int(k) for k in re.findall(r"\{&LaunchMenu::\w+, (\d+),", src)} - {0})
+    assert keys == sorted(L.MENU_KEYS)
+    for key in keys:
+        v0 = L.debug_get(key)
+        with L.debug_menu({key: v0 + 3}):
+            assert L.debug_get(key) == v0 + 3
+        assert L.debug_get(key) == v0
+    v = C.c_int32(-7)
+    for key in (0, 6, 12, 17, -1):
+        assert lib.gget_debug_set(key, 1) == 2 and b"unknown key" in lib.gget_last_error()
+        assert lib.gget_debug_get(key, C.byref(v)) == 2 and v.value == -7
+    # the defaults where the environment is silent: the shipped selection
+    env = {"GGET_GEMM_VARIANT": 1, "GGET_GEMM_LDS_HEADROOM": 2, "GGET_RMS_WIDE": 13, "GGET_CE_PARTS": 14}
+    want = {1: 0, 2: 1, 13: 1, 14: 1, 15: 0}
+    for name, key in env.items():
+        if name in os.environ:
+            want.pop(key, None)
+    assert {k: L.debug_get(k) for k in want} == want

@@ -1,9 +1,8 @@
 """GEMM kernels bit for bit, in every element: exact operands (tests/_util.py: exact_operands) make fp32 accumulation exact in any
 summation order, so every tile shape, K split, stream-K partial and grouped launch the launcher (csrc/gemm.hip launch_t / launch_mode)
-can pick must return bf16_rne(fp64 product) exactly - under every launch menu the process can select (gget_debug_set keys 1, 2, 3, 15).
+can pick must return bf16_rne(fp64 product) exactly - under every launch menu the process can select (menu keys 1, 2, 3, 15: csrc/menu.h).
 Random-normal operands are held element-wise to the fp32 accumulation + bf16 rounding bound (assert_elementwise).  Output buffers are
 surrounded by sentinels (columns in [N, ldc), rows past M)."""
-import contextlib
 import ctypes as C
 import importlib
 
@@ -22,15 +21,15 @@ EPI_NONE, EPI_RES, EPI_ATOMIC, EPI_SLAB = L.EPI_NONE, L.EPI_RESIDUAL, L.EPI_ATOM
 SENT16 = 0x7FC1                      # bf16 NaN payload no kernel writes
 SENT32 = 0x7FC01234                  # fp32 NaN payload
 PAD_ROWS = 64
-DEFAULT_KEYS = {1: 0, 2: 1, 3: 0, 15: 0}
+VAR, HEADROOM, RESERVE = L.KEY_GEMM_VARIANT, L.KEY_GEMM_LDS_HEADROOM, L.KEY_GEMM_CU_RESERVE
 
-# Launch menus (gget_debug_set key -> value) whose kernel selection differs from the default somewhere in the cases below.  key 1 bits
-# (csrc/gemm.hip): 1 K-split kernel of one-round N = d launches off, 2 K-split kernel of the grouped weight gradients off (persistent
-# 192x192), 4 the 192-row tiles off, 16 the 64- / 96-row K-split tiles off, 32 one block per CU for the dh + GEGLU' launch, 64 the
-# 32x32x16 K-split kernel for the grouped launch, 128 the 8-wide epilogue of the K-split kernel, 256 one round of 256x256 tiles, 512
-# ks_first off.  key 2: 0 the 4-slot rings, 2 no two-blocks-per-CU launch.  key 15: CUs held back for a collective.
-MENUS = [{}, {1: 1}, {1: 2}, {1: 4}, {1: 16}, {1: 32}, {1: 64}, {1: 128}, {1: 256}, {1: 512}, {1: 1 | 4}, {2: 0}, {2: 2},
-         {15: 16}, {15: 32}, {15: 64}, {15: 16, 2: 2}, {15: 64, 2: 0}, {15: 32, 1: 128}]
+# Launch menus (key -> value) whose kernel selection differs from the default somewhere in the cases below: the KEY_GEMM_VARIANT bits
+# (csrc/menu.h kGemm*), KEY_GEMM_LDS_HEADROOM 0 (the 4-slot rings) and 2 (no two-blocks-per-CU launch), KEY_GEMM_CU_RESERVE (CUs held
+# back for a collective).
+MENUS = [{}, {VAR: L.GEMM_NO_KSPLIT_ND}, {VAR: L.GEMM_NO_KSPLIT_WGRAD}, {VAR: L.GEMM_NO_192_ROWS}, {VAR: L.GEMM_KSPLIT_128_ONLY},
+         {VAR: L.GEMM_ONE_BLOCK_PER_CU}, {VAR: L.GEMM_KSPLIT_DMA8}, {VAR: L.GEMM_AREA_RULE}, {VAR: L.GEMM_NO_KSPLIT_ND | L.GEMM_NO_192_ROWS},
+         {HEADROOM: 0}, {HEADROOM: 2}, {RESERVE: 16}, {RESERVE: 32}, {RESERVE: 64}, {RESERVE: 16, HEADROOM: 2}, {RESERVE: 64, HEADROOM: 0},
+         {RESERVE: 32, VAR: L.GEMM_KSPLIT_DMA8}]
 D, FF = 768, 3072
 ROWS = [1408, 2880, 5184, 5376, 5696, 6144, 8192, 12032, 41472]   # tools/rows_sweep.py / seq_sweep.py batches, the headline, ogbl-ppa rows
 
@@ -46,17 +45,6 @@ def ST():
 @pytest.fixture(scope="module")
 def lib():
     return L.load()
-
-
-@contextlib.contextmanager
-def menu(lib, keys):
-    try:
-        for k, v in keys.items():
-            L.check(lib.gget_debug_set(k, v))
-        yield
-    finally:
-        for k, v in DEFAULT_KEYS.items():
-            L.check(lib.gget_debug_set(k, v))
 
 
 def name(keys):
@@ -126,7 +114,7 @@ def check_single(lib, mode, epi, M, N, K, ldc=None, split_k=1, menus=MENUS, seed
     live = (ktiles + per - 1) // per          # slices that own K-tiles (gemm_kernel: 64-aligned slices of `per` tiles)
     for keys in menus:
         what = f"{case} mode {mode} epi {epi} {M}x{N}x{K} ldc {ldc} split {split_k} [{name(keys)}]"
-        with menu(lib, keys):
+        with L.debug_menu(keys):
             buf = run_gemm(lib, mode, epi, A, B, R, M, N, K, ldc, split_k)
         assert_sentinels(buf, M, ldc, nw, what, slabs, range(live, slabs) if epi == EPI_SLAB else ())
         body = buf[:slabs * M * ldc].view(slabs, M, ldc)[:, :, :N]
@@ -180,7 +168,7 @@ def test_exact_gemm_residual_atomic_slab(lib):
     for split in (2, 4):                               # K = 320: 5 K-tiles -> split 4 leaves slice 3 empty
         check_single(lib, NT, EPI_SLAB, M, N, K, split_k=split, menus=[{}], case="epilogues")
     for M, N, K, split in ((768, 768, 5696, 8), (2304, 768, 5184, 6), (1000, 760, 700, 5)):   # the weight-gradient slab shapes (TN, K = T)
-        check_single(lib, TN, EPI_SLAB, M, N, K, split_k=split, menus=[{}, {15: 32}], case="wgrad_slab")
+        check_single(lib, TN, EPI_SLAB, M, N, K, split_k=split, menus=[{}, {RESERVE: 32}], case="wgrad_slab")
         check_single(lib, TN, EPI_ATOMIC, M, N, K, split_k=split, menus=[{}], case="wgrad_atomic")
 
 
@@ -206,12 +194,13 @@ def test_exact_gemm_stream_k(lib, mode, M, N, K, res):
     """The split of the last round (key 3) moves fp32 partial tiles between workgroups: with exact operands the result must be the
     plain launch's and the expected bits exactly, launch after launch on the same workspace, under the menus that change its plan."""
     epi = EPI_RES if res else EPI_NONE
-    want16 = check_single(lib, mode, epi, M, N, K, menus=[{}, {15: 32}], case="stream_k")
+    want16 = check_single(lib, mode, epi, M, N, K, menus=[{}, {RESERVE: 32}], case="stream_k")
     A, B, R = exact_operands(M, N, K, 0, mode=mode, residual=res, device="cuda")
     ws = torch.zeros(int(lib.gget_op_gemm_streamk_bytes()), dtype=torch.uint8, device="cuda")
-    for keys in ({3: 1, 1: 1}, {3: 1, 1: 1, 2: 0}, {3: 1, 1: 1, 15: 32}, {3: 1}):
+    SPLIT, NO_KS = L.KEY_GEMM_SPLIT_LAST, L.GEMM_NO_KSPLIT_ND
+    for keys in ({SPLIT: 1, VAR: NO_KS}, {SPLIT: 1, VAR: NO_KS, HEADROOM: 0}, {SPLIT: 1, VAR: NO_KS, RESERVE: 32}, {SPLIT: 1}):
         what = f"stream-K mode {mode} {M}x{N}x{K} res {res} [{name(keys)}]"
-        with menu(lib, keys):
+        with L.debug_menu(keys):
             for it in range(2):
                 buf = run_gemm(lib, mode, epi, A, B, R, M, N, K, N, ws=ws)
                 assert_sentinels(buf, M, N, N, what)
@@ -253,7 +242,7 @@ def layer_forward_fused(lib, T, d, ff, menus, seed):
     for keys in menus:
         what = f"qkv_rope T {T} [{name(keys)}]"
         qkv = out_buf(T, 3 * d)
-        with menu(lib, keys):
+        with L.debug_menu(keys):
             L.check(lib.gget_op_qkv_rope(P(x), P(w), P(qkv), P(cos), P(sin), P(pos), T, 32, d, ST()))
             torch.cuda.synchronize()
         assert_sentinels(qkv, T, 3 * d, 3 * d, what)
@@ -276,7 +265,7 @@ def layer_forward_fused(lib, T, d, ff, menus, seed):
         what = f"gateup_geglu T {T} [{name(keys)}]"
         gu, h = out_buf(T, 2 * ff), out_buf(T, ff)
         dgu = out_buf(T, 2 * ff)
-        with menu(lib, keys):
+        with L.debug_menu(keys):
             L.check(lib.gget_op_gateup_geglu(P(xn), P(wgu), P(gu), P(h), T, d, ff, ST()))
             L.check(lib.gget_op_down_dgrad_geglu(P(dy), P(wdn), P(gu16), P(dgu), None, T, d, ff, ST()))
             torch.cuda.synchronize()
@@ -322,7 +311,7 @@ def check_grouped(lib, probs, menus, what0):
     for keys in menus:
         what = f"{what0} {[(M, N, K) for _, _, M, N, K in probs]} [{name(keys)}]"
         bufs = [out_buf(M, N) for _, _, M, N, K in probs]
-        with menu(lib, keys):
+        with L.debug_menu(keys):
             L.check(L.gemm_grouped(lib, TN, [(A, B, c, M, N, K, M, N, N) for (A, B, M, N, K), c in zip(probs, bufs)], ST()))
             torch.cuda.synchronize()
         for j, ((A, B, M, N, K), c, want) in enumerate(zip(probs, bufs, wants)):

@@ -424,7 +424,7 @@ def test_generation_loop(case):
 
 
 def test_reproducible_mode_gives_bit_identical_parameters():
-    """gget_debug_set(4, 1): the RMSNorm weight gradients - the one sum of the pre-train gradient path that is added with fp32 atomics -
+    """L.KEY_DETERMINISTIC = 1: the RMSNorm weight gradients - the one sum of the pre-train gradient path that is added with fp32 atomics -
     are summed in block order.  Two engines started from the same state then hold BIT-IDENTICAL fp32 master parameters and Adam moments
     after several clip + AdamW steps on the var-len layout (attention dropout on), and the same loss to the last bits of its own
     (atomic) sum; the default mode must stay within tolerance of it."""
@@ -440,7 +440,7 @@ def test_reproducible_mode_gives_bit_identical_parameters():
     n_real = int(batch["attention_mask"].sum())
 
     def run(det):
-        LL.check(lib.gget_debug_set(4, det))
+        LL.check(lib.gget_debug_set(LL.KEY_DETERMINISTIC, det))
         e = make_engine(spec, batch)
         e.load_state_dict(state)
         e.set_dropout(0.1, 0.0, 1234)
@@ -453,12 +453,10 @@ def test_reproducible_mode_gives_bit_identical_parameters():
         out = (e.master.clone(), e.adam_m.clone(), e.adam_v.clone(), losses)
         del e
         return out
-    try:
+    with LL.debug_menu({LL.KEY_DETERMINISTIC: 0}):
         a = run(1)
         c = run(1)
         d = run(0)
-    finally:
-        LL.check(lib.gget_debug_set(4, 0))
     for k in range(3):
         assert torch.equal(a[k], c[k]), ("master", "adam_m", "adam_v")[k] + " differs between two reproducible-mode runs"
     assert a[3] == pytest.approx(c[3], rel=1e-5)      # (the REPORTED loss is still an atomic sum over blocks: equal to its last bits only)
@@ -1112,8 +1110,7 @@ def test_ls_norm_backward_lean_form_matches_the_wide_form(width):
     b = tb(batch)
     runs = []
     for wide in (1, 0):
-        L.check(L.load().gget_debug_set(11, wide))
-        try:
+        with L.debug_menu({L.KEY_LS_NORM_BWD_WIDE: wide}):
             e = make_engine(spec, batch)
             e.load_state_dict(state)
             e.set_dropout(0.1, 0.2, 99)
@@ -1123,8 +1120,6 @@ def test_ls_norm_backward_lean_form_matches_the_wide_form(width):
             e.backward()
             torch.cuda.synchronize()
             runs.append((float(loss), {k: v.float().cpu().numpy().copy() for k, v in e.grads().items()}))
-        finally:
-            L.check(L.load().gget_debug_set(11, 0))
     (lw, gw), (ll, gl) = runs
     assert lw == ll
     gmax = max(float(np.linalg.norm(v)) for v in gw.values())
@@ -1775,9 +1770,9 @@ def test_gradient_norm_from_backward_partials_matches_full_pass(monkeypatch):
 
 @pytest.mark.gpu
 def test_reserved_cus_launch_menu_gives_the_same_step():
-    """Data-parallel runs leave CUs free for the collective's workgroups (gget_debug_set(15, R): every GEMM tile plan, persistent grid and
+    """Data-parallel runs leave CUs free for the collective's workgroups (L.KEY_GEMM_CU_RESERVE = R: every GEMM tile plan, persistent grid and
     split-K fit counts CUs - R; the o projection's weight gradient leaves the grouped 256-tile launch for the split-K slab path so that the
-    rest is one tile per CU again; csrc/gemm.hip g_gemm_cu_reserve).  Same arithmetic in other tilings: loss bit-equal is not promised,
+    rest is one tile per CU again; csrc/gemm.hip gemm_cu_reserve).  Same arithmetic in other tilings: loss bit-equal is not promised,
     but loss and every gradient must agree to bf16 rounding with the full-chip menu - at the headline width, where the menus differ."""
     from _util import spec_mod, weights_mod, synth
     lib = L.load()
@@ -1789,17 +1784,15 @@ def test_reserved_cus_launch_menu_gives_the_same_step():
     b = tb(batch)
     n_tok = int(batch["attention_mask"].sum())
     out = {}
-    try:
+    with L.debug_menu({L.KEY_GEMM_CU_RESERVE: 0}):
         for name, r in (("full", 0), ("reserved", 16), ("reserved32", 32)):
-            L.check(lib.gget_debug_set(15, r))
+            L.check(lib.gget_debug_set(L.KEY_GEMM_CU_RESERVE, r))
             e = eng_mod.Engine(spec, max_tokens=B * S, max_batch=B)
             e.load_state_dict(state)
             loss = float(e.forward_pretrain(b["input_ids"], b["attention_mask"], b["labels"], num_tokens=n_tok))
             e.backward()
             torch.cuda.synchronize()
             out[name] = (loss, {k: v.float().cpu().numpy().copy() for k, v in e.grads().items()})
-    finally:
-        L.check(lib.gget_debug_set(15, 0))
     lf, gf = out["full"]
     gmax = max(float(np.linalg.norm(g)) for g in gf.values())
     for name in ("reserved", "reserved32"):      # 16: the o weight gradient leaves the group; 32: q|k|v and o do
@@ -1817,7 +1810,7 @@ def test_reserved_cus_launch_menu_gives_the_same_step():
 def test_cross_entropy_block_partials_match_the_atomic_sum(weighted):
     """The engine's cross-entropy launch leaves ONE partial loss sum per block in its workspace and the finalising launch adds them in block
     order (kernels.hip ce_rows_kernel / finalize_loss_kernel; 2048 same-address atomics cost the headline launch a third of its time);
-    gget_debug_set(14, 0) = the atomic form.  Same row losses, two summation orders: the loss equal to fp32 rounding, the lm_head gradient -
+    L.KEY_CE_PARTS = 0 = the atomic form.  Same row losses, two summation orders: the loss equal to fp32 rounding, the lm_head gradient -
     dlogits - untouched (the plain and the dLM-weighted normalisation, modeling_pretrain.py:210-236)."""
     from _util import spec_mod, weights_mod, synth
     lib = L.load()
@@ -1827,17 +1820,15 @@ def test_cross_entropy_block_partials_match_the_atomic_sum(weighted):
     state = weights_mod.make_state_dict(spec, seed=5, std=0.05, head_std=0.1)
     b = tb(synth.make_pretrain_batch(B=B, S=S, F=F, V=V, seed=31, dlm_wgt=weighted))
     out = []
-    try:
+    with L.debug_menu({L.KEY_CE_PARTS: 1}):
         for form in (0, 1, 1):
-            L.check(lib.gget_debug_set(14, form))
+            L.check(lib.gget_debug_set(L.KEY_CE_PARTS, form))
             e = eng_mod.Engine(spec, max_tokens=B * S, max_batch=B)
             e.load_state_dict(state)
             loss = float(e.forward_pretrain(b["input_ids"], b["attention_mask"], b["labels"], b.get("wgt")))
             e.backward()
             torch.cuda.synchronize()
             out.append((loss, e.grads()["lm_head.weight"].float().cpu().numpy().copy()))
-    finally:
-        L.check(lib.gget_debug_set(14, 1))
     assert out[0][0] > 0.5
     assert abs(out[0][0] - out[1][0]) <= 2e-6 * abs(out[0][0]), (out[0][0], out[1][0])
     assert out[1][0] == out[2][0], "the block-ordered sum must reproduce itself"
@@ -1866,9 +1857,9 @@ def test_slot_sorted_head_matches_dense_head(mode, d):
     b = tb(batch)
     n_tok = int(batch["attention_mask"].sum()) if mode == "labels_varlen" else None
     out = {}
-    try:
+    with L.debug_menu({L.KEY_HEAD_DENSE: 0}):
         for name, dense in (("sorted", 0), ("dense", 1)):
-            L.check(lib.gget_debug_set(8, dense))
+            L.check(lib.gget_debug_set(L.KEY_HEAD_DENSE, dense))
             e = eng_mod.Engine(spec, max_tokens=B * S, max_batch=B)
             e.load_state_dict(state)
             labels = None if mode == "inference" else b["labels"]
@@ -1880,8 +1871,6 @@ def test_slot_sorted_head_matches_dense_head(mode, d):
                 torch.cuda.synchronize()
                 grads = {k: v.float().cpu().numpy().copy() for k, v in e.grads().items()}
             out[name] = (None if loss is None else float(loss), logits, grads, e.head_counts())
-    finally:
-        L.check(lib.gget_debug_set(8, 0))
     (ls, gs, grs, cs), (ld, gd, grd, cd) = out["sorted"], out["dense"]
     assert cs == cd and gs.shape == gd.shape and gs.shape[0] == cs[1]
     if mode == "inference":

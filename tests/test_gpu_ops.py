@@ -104,7 +104,7 @@ def test_gemm_tile_128x192(lib, mode, M, N, K):
 def test_gemm_stream_k(lib, mode, M, N, K, res):  # (name kept: the split of the last round grew out of a stream-K schedule)
     """Row counts that are no multiple of the tile grid - the shapes the var-len token layout produces (M = a batch's real tokens).
     (a) plain entry point: one-round N = d launches take the K-split kernel with 64 / 96 / 128 rows per tile, whichever fills the CUs
-    best (csrc/gemm.hip launch_t), ragged last tile included; (b) gget_op_gemm_streamk with the split of the last round switched on (gget_debug_set key 3): the last,
+    best (csrc/gemm.hip launch_t), ragged last tile included; (b) gget_op_gemm_streamk with the split of the last round switched on (L.KEY_GEMM_SPLIT_LAST): the last,
     partial round splits its tiles' K range among the idle workgroups (fp32 partial tiles through the workspace, agent-scope
     release / acquire) - the result must be the plain kernel's up to fp32 summation order, repeatedly (the workspace is reused launch
     after launch: the flag epochs keep the launches apart), and exact against an fp32 matmul within the bf16 output rounding."""
@@ -119,17 +119,13 @@ def test_gemm_stream_k(lib, mode, M, N, K, res):  # (name kept: the split of the
     assert rel_l2(plain.float().cpu().numpy(), ref.cpu().numpy()) < 4e-3
     ws = torch.zeros(int(lib.gget_op_gemm_streamk_bytes()), dtype=torch.uint8, device="cuda")
     outs = []
-    L.check(lib.gget_debug_set(3, 1))            # split the last round (off by default)
-    L.check(lib.gget_debug_set(1, 1))            # ... on the plain 128-row persistent tile (the K-split kernel takes one-round launches otherwise)
-    try:
+    # split the last round (off by default) on the plain 128-row persistent tile (the K-split kernel takes one-round launches otherwise)
+    with L.debug_menu({L.KEY_GEMM_SPLIT_LAST: 1, L.KEY_GEMM_VARIANT: L.GEMM_NO_KSPLIT_ND}):
         for it in range(3):
             Cm = torch.full((M, N), 7.0, dtype=torch.bfloat16, device="cuda")
             L.check(lib.gget_op_gemm_streamk(mode, epi, P(A), P(B), P(Cm), P(R) if res else None, M, N, K, K, ldb, N, P(ws), ST()))
             outs.append(Cm)
         torch.cuda.synchronize()
-    finally:
-        L.check(lib.gget_debug_set(3, 0))
-        L.check(lib.gget_debug_set(1, 0))
     err_flag = int(ws[512 * 4: 512 * 4 + 4].view(torch.int32)[0])
     assert err_flag == 0, "a stream-K owner gave up waiting for its contributor"
     for Cm in outs:
@@ -201,28 +197,29 @@ def test_rmsnorm(lib, T, d):
 @pytest.mark.parametrize("T,d", [(5696, 768), (8320, 768), (777, 512), (4097, 1024), (23, 768)])
 def test_rmsnorm_bwd_short_launch_form_is_bit_equal(lib, T, d):
     """Short launches (<= 64 rows per CU) run one 16-wave block per CU with the rows dealt in contiguous ranges (rmsnorm_bwd_wide_kernel);
-    gget_debug_set(13, 0) selects the 4-wave blocks every other launch uses.  Same expressions: dx bit-equal, the weight gradient equal up to
+    L.KEY_RMS_WIDE = 0 selects the 4-wave blocks every other launch uses.  Same expressions: dx bit-equal, the weight gradient equal up to
     the order of its fp32 partial sums."""
     x, w, dy, dres = rnd(T, d, seed=1), (rnd(d, seed=2) * 0.1 + 1).to(torch.bfloat16), rnd(T, d, seed=3), rnd(T, d, seed=4)
     rstd = torch.rsqrt(x.float().pow(2).mean(-1) + 1e-6)
     out = []
+    rms_wide = L.debug_get(L.KEY_RMS_WIDE)
     for form in (0, 1):
-        lib.gget_debug_set(13, form)
+        L.check(lib.gget_debug_set(L.KEY_RMS_WIDE, form))
         dx = torch.full((T, d), 5.0, dtype=torch.bfloat16, device="cuda")
         dw = torch.zeros(d, dtype=torch.float32, device="cuda")
         L.check(lib.gget_op_rmsnorm_bwd(P(dy), P(x), P(w), P(rstd), P(dres), P(dx), P(dw), T, d, ST()))
         torch.cuda.synchronize()
         out.append((dx, dw))
-    lib.gget_debug_set(13, 1)
+    L.check(lib.gget_debug_set(L.KEY_RMS_WIDE, rms_wide))
     assert torch.equal(out[0][0], out[1][0]), "dx of the 16-wave form differs from the 4-wave form"
     assert rel_l2(out[1][1].cpu().numpy(), out[0][1].cpu().numpy()) < 2e-6
     # without a residual gradient
     dx0 = torch.empty(T, d, dtype=torch.bfloat16, device="cuda")
     dx1 = torch.empty(T, d, dtype=torch.bfloat16, device="cuda")
     dw = torch.zeros(d, dtype=torch.float32, device="cuda")
-    lib.gget_debug_set(13, 0)
+    L.check(lib.gget_debug_set(L.KEY_RMS_WIDE, 0))
     L.check(lib.gget_op_rmsnorm_bwd(P(dy), P(x), P(w), P(rstd), None, P(dx0), P(dw), T, d, ST()))
-    lib.gget_debug_set(13, 1)
+    L.check(lib.gget_debug_set(L.KEY_RMS_WIDE, rms_wide))
     L.check(lib.gget_op_rmsnorm_bwd(P(dy), P(x), P(w), P(rstd), None, P(dx1), P(dw), T, d, ST()))
     torch.cuda.synchronize()
     assert torch.equal(dx0, dx1)

@@ -299,18 +299,19 @@ def test_varlen_c1_full_size_matches_padded():
     state = weights_mod.make_state_dict(spec, seed=0)
     batch = {k: v for k, v in synth.make_pretrain_batch(B=256, S=32, F=13, V=756, seed=1234).items() if k != "lengths"}
     lib = L.load()
+    variant = L.debug_get(L.KEY_GEMM_VARIANT)
     try:
-        # (i) both layouts on the SAME summation orders (no in-block K split, no stream-K, 256-row tiles only: gget_debug_set key 1):
+        # (i) both layouts on the SAME summation orders (no in-block K split, no stream-K, 256-row tiles only: L.KEY_GEMM_VARIANT):
         # every real row then goes through identical arithmetic, so the forward must agree bit for bit - any difference would be an
         # indexing error of the compact layout, not rounding
-        L.check(lib.gget_debug_set(1, 1 | 2 | 4 | 8))
+        L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, L.GEMM_NO_KSPLIT_ND | L.GEMM_NO_KSPLIT_WGRAD | L.GEMM_NO_192_ROWS | L.GEMM_NO_SPLIT_LAST))
         pad = _run(spec, state, batch, "pt", "", varlen=False, dropout=(0.1, 0.0))
         vl = _run(spec, state, batch, "pt", "", varlen=True, dropout=(0.1, 0.0))
         assert vl["varlen"] and vl["rows"] < 0.8 * 256 * 32
         assert np.array_equal(pad["logits"], vl["logits"]), "head logits of the two layouts differ with identical kernels"
         _compare("varlen_c1_full_size_same_kernels", pad, vl, loss_tol=2e-6, logit_tol=1e-9, grad_tol=2e-3)
     finally:
-        L.check(lib.gget_debug_set(1, 0))
+        L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, variant))
     # (ii) the shipped kernel selection (192-row tiles, stream-K, K-split kernels differ between the layouts): bf16-class agreement - at
     # the standard init the logits carry ~1e-2 of bf16 noise against fp32 in EITHER layout (tests/test_gpu_model.py holds the padded
     # path to max(2.5 x reference bf16 error, 1.5e-2)), and two summation orders draw two noise patterns

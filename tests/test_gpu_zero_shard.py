@@ -43,10 +43,8 @@ def _state(e):
 
 @pytest.fixture
 def reproducible():
-    lib = L.load()
-    L.check(lib.gget_debug_set(4, 1))
-    yield
-    L.check(lib.gget_debug_set(4, 0))
+    with L.debug_menu({L.KEY_DETERMINISTIC: 1}):
+        yield
 
 
 def test_abi_sharded_step_world1_equals_replicated_step(reproducible):
@@ -154,7 +152,7 @@ def _worker(rank, world, port, q, overlap, layout, runs, tmp):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", init_method="env://")
     modeling, tr, synth = _mods()
-    L.check(L.load().gget_debug_set(4, 1))
+    L.check(L.load().gget_debug_set(L.KEY_DETERMINISTIC, 1))
     out = {}
     for zero, clip in runs:
         model = modeling.GraphGPTPretrainBase(_cfg(modeling), seed=1)

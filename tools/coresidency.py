@@ -12,6 +12,7 @@ training = importlib.import_module("graph-gpt_amd.training")
 synth = importlib.import_module("graph-gpt_amd.synth")
 spec_mod = importlib.import_module("graph-gpt_amd.spec")
 lib = L.load()
+headroom0 = L.debug_get(L.KEY_GEMM_LDS_HEADROOM)   # (restored at the end)
 B, S, F, V = 256, 32, 13, 756
 sz = spec_mod.MODEL_SIZES["base"]
 cfg = modeling.GraphGPTConfig(hidden_act="gelu", vocab_size=V, hidden_size=sz["hidden_size"], intermediate_size=4 * sz["hidden_size"],
@@ -47,7 +48,7 @@ def run(blocks, lds, steps=12, warm=3):
 
 base = base2 = None
 for headroom in (0, 1):
-    L.check(lib.gget_debug_set(2, headroom))
+    L.check(lib.gget_debug_set(L.KEY_GEMM_LDS_HEADROOM, headroom))
     b0 = run(0, 4)
     base = base if base is not None else b0
     print(f"[128x192 ring {'3 slots = 120 KiB' if headroom else '4 slots = 160 KiB'}] no side-stream kernel: {b0:.3f} ms/step")
@@ -56,7 +57,7 @@ for headroom in (0, 1):
             ms = run(blocks, lds)
             rows.append({"lds_headroom": headroom, "blocks": blocks, "lds_bytes": lds, "ms_per_step": ms, "slowdown_vs_same_config": ms / b0})
             print(f"  side kernel {blocks:4d} workgroups x {lds // 1024:3d} KiB LDS: {ms:.3f} ms/step  ({(ms / b0 - 1) * 100:+.1f} %)", flush=True)
-L.check(lib.gget_debug_set(2, 0))
+L.check(lib.gget_debug_set(L.KEY_GEMM_LDS_HEADROOM, headroom0))
 base2 = run(0, 4)
 print(f"no side-stream kernel (again): {base2:.3f} ms/step")
 json.dump({"baseline_ms": [base, base2], "rows": rows, "note": "step includes waiting for the ~9 ms stand-in at its end, so ms/step >= ~9.0 when blocks > 0; compare against max(baseline, 9.0)"},

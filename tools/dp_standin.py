@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Does a data-parallel rank's launch menu survive a collective's workgroups?  ONE GPU, the C1 training step; while the BACKWARD runs on the
 compute stream, a stand-in for RCCL's kernel sits on a side stream: N workgroups of 256 threads with the footprint read from librccl's
-gfx950 code object (rcclGenericKernel: 264 registers per lane - gget_debug_set(16, 1) - and 19.7 KiB of LDS), resident for the length of the
-backward the way the bucketed all-reduce is.  Menus (gget_debug_set):
+gfx950 code object (rcclGenericKernel: 264 registers per lane - L.KEY_OCCUPY_FAT = 1 - and 19.7 KiB of LDS), resident for the length of the
+backward the way the bucketed all-reduce is.  Menus (process launch-menu keys, graph-gpt_amd/_lib.py KEY_*):
 
   single   the single-GPU menu                                   (what a rank would run if nothing were done)
-  r4       rounds 2-4: LDS headroom on every CU        (2, 2)
-  r5       round 5: 16 CUs left to the collective      (15, 16), (13, 0), (2, 1)
-  r5_32    ... 32 CUs left                              (15, 32)
-  r5_64    ... 64 CUs left                              (15, 64)
+  r4       rounds 2-4: LDS headroom on every CU        GEMM_LDS_HEADROOM 2
+  r5       round 5: 16 CUs left to the collective      GEMM_CU_RESERVE 16, RMS_WIDE 0, GEMM_LDS_HEADROOM 1
+  r5_32    ... 32 CUs left                              GEMM_CU_RESERVE 32
+  r5_64    ... 64 CUs left                              GEMM_CU_RESERVE 64
 
 prints ms/step (forward + backward + clip + AdamW, HIP events) without the stand-in and with N = 16 / 32 workgroups of it.
 DP_STANDIN_SCHEDULE=300,150,60: instead, the bucketed exchange SCHEDULE of a rank - the staged backward with a stand-in behind every
@@ -37,14 +37,16 @@ side = torch.cuda.Stream()
 scratch = torch.zeros(64 << 20, dtype=torch.uint8, device="cuda")
 RCCL_LDS = 19744
 BWD_US = 4300          # the stand-in stays for about the length of the backward
-MENUS = {"single": [(15, 0), (13, 1), (2, 1)], "r4": [(15, 0), (13, 1), (2, 2)], "r5": [(15, 16), (13, 0), (2, 1)],
-         "r5_32": [(15, 32), (13, 0), (2, 1)], "r5_64": [(15, 64), (13, 0), (2, 1)]}
+RES, RMS, HEAD = L.KEY_GEMM_CU_RESERVE, L.KEY_RMS_WIDE, L.KEY_GEMM_LDS_HEADROOM
+MENUS = {"single": [(RES, 0), (RMS, 1), (HEAD, 1)], "r4": [(RES, 0), (RMS, 1), (HEAD, 2)], "r5": [(RES, 16), (RMS, 0), (HEAD, 1)],
+         "r5_32": [(RES, 32), (RMS, 0), (HEAD, 1)], "r5_64": [(RES, 64), (RMS, 0), (HEAD, 1)]}
+MENU0 = [(k, L.debug_get(k)) for k in (RES, RMS, HEAD, L.KEY_OCCUPY_FAT)]   # (restored at the end)
 
 
 def run(menu, blocks, steps=12, warm=4):
     for k, v in MENUS[menu]:
         L.check(lib.gget_debug_set(k, v))
-    L.check(lib.gget_debug_set(16, 1))
+    L.check(lib.gget_debug_set(L.KEY_OCCUPY_FAT, 1))
 
     def step():
         out = eng(input_ids=dev["input_ids"], attention_mask=dev["attention_mask"], labels=dev["labels"], num_tokens=n_tok)
@@ -73,7 +75,7 @@ def run_schedule(menu, blocks, gbps, world=8, steps=12, warm=4):
     that stays as long as a ring all-reduce of the bucket would at `gbps` GB/s of bus bandwidth (+ 30 us of latency) over `world` ranks."""
     for k, v in MENUS[menu]:
         L.check(lib.gget_debug_set(k, v))
-    L.check(lib.gget_debug_set(16, 1))
+    L.check(lib.gget_debug_set(L.KEY_OCCUPY_FAT, 1))
     e = model._engine
     nl = e.spec.num_layers
     main = torch.cuda.current_stream()
@@ -124,7 +126,7 @@ if os.environ.get("DP_STANDIN_SCHEDULE"):      # "gbps[,gbps...]": the bucketed 
                 ms = [run_schedule(menu, blocks, gbps) for _ in range(2)]
                 rows.append({"schedule_gbps": gbps, "menu": menu, "standin_workgroups": blocks, "ms_per_step": ms})
                 print(f"schedule at {gbps:.0f} GB/s bus bandwidth, 8 ranks: menu {menu:6s} stand-in workgroups {blocks:3d}: {ms[0]:.3f} / {ms[1]:.3f} ms/step", flush=True)
-    for k, v in MENUS["single"] + [(16, 0)]:
+    for k, v in MENU0:
         L.check(lib.gget_debug_set(k, v))
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "dp_standin_schedule.json")
     json.dump({"rows": rows, "buckets_mib": mb}, open(out, "w"), indent=1)
@@ -138,7 +140,7 @@ for rnd in range(2):
             ms = run(menu, blocks)
             rows.append({"round": rnd, "menu": menu, "standin_workgroups": blocks, "ms_per_step": ms})
             print(f"round {rnd} menu {menu:6s} stand-in workgroups {blocks:3d}: {ms:.3f} ms/step", flush=True)
-for k, v in MENUS["single"] + [(16, 0)]:
+for k, v in MENU0:
     L.check(lib.gget_debug_set(k, v))
 out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "dp_standin.json")
 os.makedirs(os.path.dirname(out), exist_ok=True)

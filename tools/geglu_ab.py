@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""A/B timing of the two fused GEGLU GEMMs (and plain gate|up / dh / q|k|v) under gget_debug_set variants, interleaved."""
+"""A/B timing of the two fused GEGLU GEMMs (and plain gate|up / dh / q|k|v) under L.KEY_GEMM_VARIANT bit masks (L.GEMM_*), interleaved."""
 import ctypes as C, importlib, os, statistics, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 L = importlib.import_module("graph-gpt_amd._lib")
 lib = L.load()
+menu0 = L.debug_get(L.KEY_GEMM_VARIANT)   # (restored at the end)
 P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 variants = [int(x, 0) for x in sys.argv[1:]] or [0]
@@ -26,11 +27,11 @@ for name, fn in ops.items():
     times = {v: [] for v in variants}
     for r in range(5):
         for v in variants:
-            L.check(lib.gget_debug_set(1, v))
+            L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, v))
             L.check(fn())
             e0.record()
             for _ in range(10): L.check(fn())
             e1.record(); torch.cuda.synchronize()
             times[v].append(e0.elapsed_time(e1) * 100)
     print(f"{name:18s} " + " | ".join(f"v={v:#x} {statistics.median(times[v]):6.1f} us" for v in variants), flush=True)
-L.check(lib.gget_debug_set(1, 0))
+L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, menu0))

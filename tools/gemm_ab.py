@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of GEMM kernel variants in ONE process (cdna guide rule 24): for every C1 shape the variants
-selected through gget_debug_set(1, mask) are run in alternating rounds on the same random operands, HIP-event timed,
+selected through gget_debug_set(L.KEY_GEMM_VARIANT, mask) (bits: L.GEMM_*, csrc/menu.h) are run in alternating rounds on the same random operands, HIP-event timed,
 median and min reported, each checked once against torch (fp32 matmul of the same bf16 inputs).
 usage: gemm_ab.py [mask ...]   (default masks: 0 and 15)"""
 import ctypes as C, importlib, os, statistics, sys
@@ -8,6 +8,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 L = importlib.import_module("graph-gpt_amd._lib")
 lib = L.load()
+menu0 = L.debug_get(L.KEY_GEMM_VARIANT)   # (restored at the end)
 P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 masks = [int(x) for x in sys.argv[1:] if x.lstrip("-").isdigit()] or [0, 15]
@@ -44,14 +45,14 @@ def run(name, mode, M, N, K, epi):
     want = ref(mode, A, B, R)
     errs, times = {}, {m: [] for m in masks}
     for m in masks:
-        L.check(lib.gget_debug_set(1, m))
+        L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, m))
         Cm.zero_()
         L.check(lib.gget_op_gemm(*args))
         errs[m] = float((Cm.float() - want).norm() / want.norm())
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for r in range(ROUNDS):
         for m in masks:
-            L.check(lib.gget_debug_set(1, m))
+            L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, m))
             L.check(lib.gget_op_gemm(*args))
             if FLUSH is not None:
                 tot = 0.0
@@ -87,7 +88,7 @@ print(f"rounds {ROUNDS} x iters {ITERS}, flush {'on' if FLUSH is not None else '
 bad = []
 for s in shapes:
     bad += [(s[0], m) for m in run(*s)]
-L.check(lib.gget_debug_set(1, 0))
+L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, menu0))
 if bad:
     print("WRONG RESULTS:", bad)
     sys.exit(1)

@@ -1,9 +1,10 @@
 """dh + GEGLU' launch (two workgroups per CU, gemm_persist_kernel MODE 2) against the start delay of a CU's second workgroup
-(gget_debug_set key 5, 100 MHz ticks): cold cache (flushed before every launch, like the step sees it) - median / min us, and the
+(L.KEY_GEMM_STAGGER, 100 MHz ticks): cold cache (flushed before every launch, like the step sees it) - median / min us, and the
 output compared with the un-staggered launch (must be bit-equal).  GGET_T rows (default 5696), GGET_TICKS comma list."""
 import ctypes as C, importlib, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 L = importlib.import_module("graph-gpt_amd._lib"); lib = L.load()
+menu0 = L.debug_get(L.KEY_GEMM_STAGGER)   # (restored at the end)
 P = lambda t: C.c_void_p(t.data_ptr()); st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 d, ff = 768, 3072
 ticks = [int(x) for x in os.environ.get("GGET_TICKS", "0,200,400,600,800,1000,1300,1600,2000").split(",")]
@@ -15,7 +16,7 @@ for T in [int(x) for x in os.environ.get("GGET_T", "5696").split(",")]:
     ref = None
     for rnd in range(2):
         for tk in ticks:
-            L.check(lib.gget_debug_set(5, tk))
+            L.check(lib.gget_debug_set(L.KEY_GEMM_STAGGER, tk))
             ts = []
             for it in range(12):
                 flush.zero_()
@@ -29,4 +30,4 @@ for T in [int(x) for x in os.environ.get("GGET_T", "5696").split(",")]:
                 ref = dgu.clone()
             same = bool(torch.equal(ref, dgu))
             print(f"T={T} stagger={tk * 0.01:5.1f} us: median {ts[len(ts)//2]:7.1f} us  min {ts[0]:7.1f} us  bit-equal {same}", flush=True)
-    L.check(lib.gget_debug_set(5, 0))
+    L.check(lib.gget_debug_set(L.KEY_GEMM_STAGGER, menu0))

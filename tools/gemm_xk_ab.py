@@ -8,6 +8,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 L = importlib.import_module("graph-gpt_amd._lib")
 lib = L.load()
+menu0 = L.debug_get(L.KEY_GEMM_VARIANT)   # (restored at the end)
 P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 lib.gget_op_gemm_streamk_bytes.restype = C.c_uint64
@@ -33,20 +34,20 @@ def run(name, mode, epi, M, N, K):
         return out
     res, times = {}, {}
     for var in (0, 2048):
-        L.check(lib.gget_debug_set(1, var))
+        L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, var))
         res[var] = launch(0).float().clone()
     A, B, R, _ = ops[0]
     want = A.float() @ (B.float().t() if mode == L.GEMM_NT else B.float()) + (R.float() if R is not None else 0)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for r in range(ROUNDS + 1):
         for var in (0, 2048):
-            L.check(lib.gget_debug_set(1, var))
+            L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, var))
             e0.record()
             for i in range(ITERS):
                 launch(i)
             e1.record(); torch.cuda.synchronize()
             if r: times.setdefault(var, []).append(e0.elapsed_time(e1) / ITERS * 1e3)
-    L.check(lib.gget_debug_set(1, 0))
+    L.check(lib.gget_debug_set(L.KEY_GEMM_VARIANT, menu0))
     rel = lambda x: float((x - want).norm() / want.norm())
     print(f"{name:10s} {M}x{N}x{K}: shipped {statistics.median(times[0]):7.1f} us  K halves on two blocks {statistics.median(times[2048]):7.1f} us | "
           f"rel-L2 vs fp32 {rel(res[0]):.2e} / {rel(res[2048]):.2e}  max |diff| between the two {float((res[0] - res[2048]).abs().max()):.3g}", flush=True)

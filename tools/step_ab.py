@@ -61,9 +61,11 @@ def main():
     keys = sorted({k for _, ps in variants for k, _ in ps if isinstance(k, int)})
     envs = sorted({k[4:] for _, ps in variants for k, _ in ps if not isinstance(k, int)})
 
+    base = {k: L.debug_get(k) for k in keys}      # every variant starts from the menu the process had
+
     def apply(pairs):
         for k in keys:
-            L.check(lib.gget_debug_set(k, 0 if k != 2 else 1))      # defaults (key 2 = LDS headroom: 1)
+            L.check(lib.gget_debug_set(k, base[k]))
         for k in envs:
             os.environ.pop(k, None)
         for k, v in pairs:
