@@ -5,10 +5,7 @@
 ds_config2_pt.json:20-28) and a lean `TrainingPipeline` / `TrainingMode` (reference
 src/training/pipeline.py:60-95, mode.py:46-89) that drives them from any iterable of collated batches.
 
-Data parallelism: one process per GPU; gradients live in ONE flat bf16 array cut into
-L+2 buckets in the order backward completes them; each bucket is all-reduced (RCCL, sum) on a side HIP
-stream as soon as its backward stage is enqueued, so communication overlaps the remaining backward;
-1/world is folded into the fused AdamW.  No DeepSpeed, no DDP hooks.
+Data parallelism: GgetEngine.backward is the exchange schedule; the collectives, transports and rank rules are in dp.py.
 """
 from __future__ import annotations
 
@@ -22,6 +19,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .dp import (DpOptions, _check_zero_stage, _Fp32Reduce, _host_staged, all_gather_bucket, all_gather_varlen,  # noqa: F401  (re-exported)
+                 all_reduce_bucket, dist_ready, dp_env_defaults, eval_rank_sampler, exchange_groups, finetune_rank_sampler,
+                 pick_transport, pretrain_rank_sampler, reduce_scatter_bucket, set_dist_env, shard_seed)
 from .modeling import GraphGPTPretrainBase, GraphGPTTaskModel, _GgetModel
 
 
@@ -49,14 +49,6 @@ def warmup_decay_lr(step: int, max_lr: float, min_lr: float, warmup: int, total:
     else:
         gamma = max(0.0, (total - step) / max(1.0, total - warmup))
     return min_lr + (max_lr - min_lr) * gamma
-
-
-def _check_zero_stage(stage) -> int:
-    stage = int(stage)
-    if stage not in (0, 1, 2):
-        raise ValueError(f"zero_stage {stage}: only 0 (replicated optimizer step) and 1 / 2 (sharded optimizer step) exist; stage 3 "
-                         "(partitioned parameters) is not implemented")
-    return stage
 
 
 class OptimConfig:
@@ -88,118 +80,6 @@ class OptimConfig:
         return self.lr
 
 
-# ----------------------------------------------------------------------------- DP exchange step
-class _Fp32Reduce:
-    """Handle of an fp32-accumulated bucket reduction: wait() finishes the collective and rounds the sum back into the bf16
-    gradient slice (one rounding instead of the world-1 a bf16 ring sum applies)."""
-
-    def __init__(self, work, wide, dst):
-        self.work, self.wide, self.dst = work, wide, dst
-
-    def wait(self):
-        if self.work is not None:
-            self.work.wait()
-        self.dst.copy_(self.wide)
-
-
-def all_reduce_bucket(flat: torch.Tensor, bucket, group=None, async_op: bool = True, fp32_accumulate: bool = False):
-    """Sum-all-reduce ONE gradient bucket (a contiguous [offset, offset+count) slice of the flat gradient array).
-    Device-agnostic: RCCL on GPU tensors, gloo on CPU tensors (the CPU tests drive exactly this function).
-    fp32_accumulate: widen the slice to fp32 for the reduction (twice the wire bytes, a single final rounding)."""
-    off, cnt = bucket
-    sl = flat[off: off + cnt]
-    if not fp32_accumulate:
-        return dist.all_reduce(sl, op=dist.ReduceOp.SUM, group=group, async_op=async_op)
-    wide = sl.to(torch.float32)
-    work = dist.all_reduce(wide, op=dist.ReduceOp.SUM, group=group, async_op=async_op)
-    h = _Fp32Reduce(work if async_op else None, wide, sl)
-    if not async_op:
-        h.wait()
-        return None
-    return h
-
-
-def _host_staged(flat: torch.Tensor, group) -> bool:
-    # gloo's reduce-scatter / all-gather are fed host tensors: a device arena is staged through host memory (NCCL takes device tensors)
-    return flat.is_cuda and dist.get_backend(group) == "gloo"
-
-
-def reduce_scatter_bucket(flat: torch.Tensor, plan, rank: int, world: int, group=None, fp32_accumulate: bool = False):
-    """Sharded exchange of ONE gradient bucket (ZeRO-2): the body [off, off + world * slice) reduce-scattered (SUM; rank r's slice
-    [off + r slice, off + (r + 1) slice) receives the sum) and the tail [tail_off, tail_off + tail_cnt) all-reduced.  `plan` = the bucket's
-    (offset, count, slice, tail_offset, tail_count) of gget_shard_plan.  Synchronous; device-agnostic like all_reduce_bucket (the CPU tests
-    drive it on gloo).  Outside the rank's slice the body keeps its local values."""
-    off, _, sl, toff, tcnt = plan
-    body, mine, tail = flat[off: off + world * sl], flat[off + rank * sl: off + (rank + 1) * sl], flat[toff: toff + tcnt]
-    wide = torch.float32 if fp32_accumulate else flat.dtype
-    dev = torch.device("cpu") if _host_staged(flat, group) else flat.device
-    if sl:
-        src = body.to(device=dev, dtype=wide)
-        out = torch.empty(sl, dtype=wide, device=dev)
-        dist.reduce_scatter_tensor(out, src, op=dist.ReduceOp.SUM, group=group)
-        mine.copy_(out)
-    if tcnt:
-        t = tail.to(device=dev, dtype=wide)
-        if t.data_ptr() == tail.data_ptr():
-            t = t.clone()
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        tail.copy_(t)
-
-
-def all_gather_bucket(flat: torch.Tensor, plan, rank: int, world: int, group=None):
-    """The inverse of reduce_scatter_bucket's partition: every rank's body slice of `flat` (any dtype: the bf16 weights, the fp32 master /
-    Adam arenas) gathered into the body on every rank.  Tails are not touched (every rank holds the same).  Synchronous."""
-    off, _, sl, _, _ = plan
-    if not sl:
-        return
-    body, mine = flat[off: off + world * sl], flat[off + rank * sl: off + (rank + 1) * sl]
-    dev = torch.device("cpu") if _host_staged(flat, group) else flat.device
-    out = torch.empty(world * sl, dtype=flat.dtype, device=dev)
-    dist.all_gather_into_tensor(out, mine.to(dev).clone(), group=group)
-    body.copy_(out)
-
-
-def shard_seed(base_seed: int, rank: int) -> int:
-    """Per-rank data seed: ranks draw independent batches (reference misc_utils.py:536-538 seeds with
-    `initial_seed - rank`; the synthetic generator uses base + rank)."""
-    return int(base_seed) + int(rank)
-
-
-def pretrain_rank_sampler(sample_idx, epochs: int, seed: int, rank: int):
-    """Pre-training partition rule (reference get_pt_train_valid_test_sampler loader_utils.py:328-333, reset_pt_train_sampler
-    :412-442, seeding misc_utils.py:536-538): every rank keeps the FULL index list repeated `epochs` times and shuffles it
-    with its own generator seeded `seed - rank` - ranks draw independently, not disjointly (the token budget, not the
-    epoch, bounds the run).  Python's `random` module like the reference, so the order is the reference's order."""
-    import random
-    idx = [int(i) for i in sample_idx] * max(1, int(epochs))
-    random.Random(int(seed) - int(rank)).shuffle(idx)
-    return idx
-
-
-def finetune_rank_sampler(sample_idx, world_size: int, rank: int, seed: int, epoch: int = 0):
-    """Fine-tune partition rule (reference distribute_sampler_with_rnd_seed loader_utils.py:78-90, called with
-    seed = finetune.seed + epoch at :622-627): one permutation per epoch shared by all ranks, truncated to a multiple of the
-    world size, rank r takes positions r, r + world, ...  -> disjoint shards of equal length that change every epoch."""
-    sample_idx = torch.as_tensor(sample_idx)
-    g = torch.Generator()
-    g.manual_seed(int(seed) + int(epoch))
-    indices = torch.randperm(len(sample_idx), generator=g).tolist()
-    total = (len(sample_idx) // world_size) * world_size
-    return sample_idx[indices[rank:total:world_size]].tolist()
-
-
-def eval_rank_sampler(sample_idx, world_size: int, rank: int, shuffle_seed: Optional[int] = None):
-    """Evaluation partition rule (reference distribute_sampler loader_utils.py:70-75, used for the valid / test samplers at
-    :256, :270): indices sorted, rank r keeps those at sorted positions i with i % world == r (every sample exactly once
-    across ranks, shard sizes differ by at most one), then shuffled locally (order is irrelevant to the metrics)."""
-    import random
-    vec = sorted(int(i) for i in sample_idx)
-    out = [vec[i] for i in range(len(vec)) if i % world_size == rank]
-    if shuffle_seed is not None:
-        random.Random(shuffle_seed).shuffle(out)
-    return out
-
-
 def schedule_steps(total_tokens: float, tokens_per_sample: float, batch_size: int, world_size: int) -> int:
     """Optimizer steps of a token-budgeted run (reference base_configs.py:54-60): the global batch is world * batch_size."""
     return int(total_tokens // (tokens_per_sample * batch_size * world_size))
@@ -222,46 +102,28 @@ class GgetEngine:
         self.optim = optim or OptimConfig()
         self.global_steps = 0
         self.pg = process_group
-        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        real_world = dist.get_world_size(process_group) if dist_ready() else 1
+        self.world = real_world
         self._comm_stream = None
         self._pending = []
-        self.force_staged = bool(int(os.environ.get("GGET_FORCE_STAGED", "0")))  # run the bucketed path at world 1
-        # GGET_DP_OVERLAP=0: one all-reduce of the whole flat gradient array after the monolithic backward instead of the
-        # bucketed exchange overlapped with it (to be decided by measurement on a multi-GPU node)
-        self.overlap = bool(int(os.environ.get("GGET_DP_OVERLAP", "1")))
-        # GGET_DP_FP32_REDUCE=1: reduce every bucket in fp32 (see all_reduce_bucket).  GGET_DP_BACKEND=abi: issue the
-        # collectives through the C ABI (gget_comm_init / gget_allreduce_grads_async = RCCL on a HIP side stream, no
-        # torch.distributed on the data path; the unique id travels once over the existing process group).
-        self.fp32_reduce = bool(int(os.environ.get("GGET_DP_FP32_REDUCE", "0")))
-        self.abi_comm = os.environ.get("GGET_DP_BACKEND", "torch") == "abi"
-        # GGET_DP_LOOPBACK_WORLD=W (with GGET_DP_BACKEND=abi, single process): the C-ABI exchange runs as rank 0 of W ranks that all hold
-        # this rank's gradients (gget_comm_init_loopback) - the schedule of a W-rank job (bucket ranges, side-stream waits, 1/W folded
-        # into AdamW) on a one-GPU box; the step must equal the single-rank step
-        self.loopback_world = int(os.environ.get("GGET_DP_LOOPBACK_WORLD", "0")) if self.abi_comm else 0
+        # the DP environment (dp.DpOptions describes every knob), copied into attributes that callers may rewrite afterwards
+        o = DpOptions()
+        self.force_staged, self.overlap, self.fp32_reduce, self.bucket_mb = o.force_staged, o.overlap, o.fp32_reduce, o.bucket_mb
+        self.abi_comm, self.loopback_world = o.abi, o.loopback_world
+        self._dp_lds_headroom, self._norm_from_backward = o.lds_headroom, o.norm_from_backward
         if self.loopback_world > 0:
             assert self.world == 1, "the loopback communicator replaces the process group: run it in a single process"
             self.world = self.loopback_world
             self.force_staged = True
-        # GGET_DP_BUCKET_MB=N: consecutive buckets (completion order) are exchanged in ONE collective once they add up to >= N MiB -
-        # fewer, larger messages (14 buckets of ~19 MB for the base model; 60 -> 4-5 collectives).  0 (default) = one per bucket.
-        self.bucket_mb = float(os.environ.get("GGET_DP_BUCKET_MB", "0"))
-        self._groups = None
-        # sharded optimizer step (ZeRO stage 1 / 2 = one path; OptimConfig.zero_stage, GGET_ZERO_STAGE overrides): gradients are
-        # reduce-scattered per bucket, every rank runs clip + AdamW over its 1/world of the fp32 state (gget_adamw_step_sharded) and the
-        # bf16 weights are all-gathered behind the step.  Taken only when the exchange is live: world > 1, a loopback world, or
-        # GGET_FORCE_STAGED=1 with a process group or the C-ABI communicator; otherwise the replicated step runs, unchanged.
-        self.zero_stage = _check_zero_stage(os.environ.get("GGET_ZERO_STAGE", getattr(self.optim, "zero_stage", 0)))
-        live = self.world > 1 or (self.force_staged and (self.abi_comm or (dist.is_available() and dist.is_initialized())))
-        self.sharded = self.zero_stage > 0 and live
-        self.rank = dist.get_rank(process_group) if dist.is_available() and dist.is_initialized() and self.loopback_world == 0 else 0
+        self.zero_stage = o.zero_stage if o.zero_stage is not None else _check_zero_stage(getattr(self.optim, "zero_stage", 0))
+        self.rank = dist.get_rank(process_group) if dist_ready() and self.loopback_world == 0 else 0
+        # the sharded optimizer step is taken only when the exchange is live (not the single-rank shortcut, and a transport behind it)
+        self.sharded = self.zero_stage > 0 and (self.world > 1 or self.force_staged) and pick_transport(self).live
         if self.sharded:
             model.register_state_dict_pre_hook(_refuse_stale_state)
         # measurement switch (bench.py `dp.exposed_comm_ms`): False runs the same staged backward WITHOUT issuing the collectives -
         # the ranks then drift apart, so it is only ever set for a few untimed-for-throughput diagnostic steps
         self.exchange = True
-        # the data-parallel share of the launch menu, carried by the model's handle (set_dp_menu below):
-        # GGET_DP_LDS_HEADROOM=1 opts in to the LDS-headroom menu of rounds 2 - 4, GGET_DP_RESERVE_CUS=R leaves R CUs to the collective
-        self._dp_lds_headroom = bool(int(os.environ.get("GGET_DP_LDS_HEADROOM", "0")))
         self.reserved_cus = 0
         # gradient accumulation (DeepSpeed branch, conf_utils.py:59-66 -> the DS engine steps at the boundary only): the micro-batches'
         # gradients are summed in an fp32 copy of the flat gradient array; step() k - 1 times out of k only does that
@@ -271,18 +133,9 @@ class GgetEngine:
         # skipped (weights and Adam state untouched, Adam's step count not advanced) while the LR schedule still advances
         self.skip_nonfinite = False
         self.skipped_steps = 0
-        if self.world > 1 and torch.cuda.is_available():
-            # a collective's kernel shares the chip with the compute stream from now on.  (Rounds 2 - 4 kept LDS headroom on every CU for
-            # every multi-rank job; round 5's stand-in with RCCL's real register footprint - tools/dp_standin.py - shows the rule buys
-            # nothing against such a kernel and costs 0.08 ms alone, 0.2 ms beside it: opt-in now.)  In a real multi-process job that asks
-            # for it, the GEMM launches leave GGET_DP_RESERVE_CUS CUs (default 0 = off) FREE for the collective's workgroups, which are held
-            # to as many channels (NCCL_MAX_NCHANNELS, unless the user set it; dp_env_defaults() sets it ahead of init_process_group): an
-            # RCCL workgroup (256 threads x 261 - 280 registers, 19.7 KiB LDS) cannot share a CU with any 8-wave GEMM workgroup, and a GEMM
-            # launch that finds one of "its" CUs taken runs a second round (csrc/gemm.hip).  That rule supersedes the
-            # LDS headroom; the RMSNorm backward goes back to its many-small-blocks form for the same reason.
-            real_world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        if self.world > 1 and torch.cuda.is_available():     # (DpOptions.reserve_cus: a real multi-process job only, not a loopback world)
             if real_world > 1:
-                self.reserved_cus = max(0, int(os.environ.get("GGET_DP_RESERVE_CUS", "0")))
+                self.reserved_cus = o.reserve_cus
             model.set_dp_menu(self.reserved_cus, self._dp_lds_headroom)
         model.materialize_grads = False  # fused path: gradients stay in the flat bf16 arena
         model._managed_by_engine = True  # the bucketed exchange below replaces the all-reduce of _autograd_backward
@@ -303,30 +156,12 @@ class GgetEngine:
     def eval(self):
         return self.train(False)
 
-    def _ensure_abi_comm(self, e):
-        # readiness belongs to the ENGINE INSTANCE: a model that re-creates its engine for a larger batch hands the
-        # communicator over (Engine.comm_adopt), so this collective bootstrap runs once per job, on every rank together
-        if e.comm_world > 0:
-            return
-        if self.loopback_world > 0:
-            e.comm_init_loopback(self.loopback_world)
-            return
-        rank = dist.get_rank(self.pg) if self.world > 1 else 0
-        uid = [e.comm_unique_id() if rank == 0 else None]
-        if self.world > 1:
-            dist.broadcast_object_list(uid, src=0, group=self.pg)
-        e.comm_init(rank, self.world, uid[0])
-
-    # -- backward with bucketed all-reduce overlapped on a side stream
+    # -- backward: the exchange schedule (dp.pick_transport says how a bucket travels)
     def backward(self, loss=None):
         e = self.module._engine
-        if self.abi_comm:
-            self._ensure_abi_comm(e)
-        # single-rank step: nothing touches the gradient array between this backward and AdamW - the engine MAY take the layers' share
-        # of the gradient norm from its weight-gradient launches (include/gget.h GGET_OPT_NORM_FROM_BACKWARD).  Opt-in
-        # (GGET_NORM_FROM_BACKWARD=1): measured in the step it saves its 31 us of norm pass and loses them again in AdamW, whose
-        # gradient reads the full pass had warmed the memory-side cache for (7.095 against 7.093 ms, profiles/r04_step_experiments.txt)
-        fold = self.world == 1 and not self.force_staged and bool(int(os.environ.get("GGET_NORM_FROM_BACKWARD", "0") or 0))
+        tx = pick_transport(self)
+        tx.ready(e)
+        fold = self.world == 1 and not self.force_staged and self._norm_from_backward
         if getattr(e, "_norm_fold", None) != fold:
             from . import _lib as L
             e.set_option(L.OPT_NORM_FROM_BACKWARD, int(fold))
@@ -336,63 +171,43 @@ class GgetEngine:
             return
         if self.sharded:
             self._ensure_shard(e)
-        if not self.overlap:
+        if not self.overlap:                # one exchange behind the monolithic backward
             e.backward()
-            if not self.exchange:
-                return
-            if self.sharded:
+            if self.exchange and self.sharded:
                 for b in range(len(e.buckets)):
-                    self._exchange_shard(e, b, None)
-                return
-            if self.abi_comm:
-                e.allreduce_grads_async(-1, self.fp32_reduce)
-            elif self.world > 1:
-                all_reduce_bucket(e.grad_bf16, (0, e.grad_bf16.numel()), self.pg, async_op=False, fp32_accumulate=self.fp32_reduce)
+                    tx.reduce_scatter(e, b)
+            elif self.exchange:
+                tx.all_reduce_all(e)
             return
-        if self._comm_stream is None:
-            self._comm_stream = torch.cuda.Stream(device=e.device)
-        main = torch.cuda.current_stream()
         L_ = e.spec.num_layers
+        # sharded: no coalescing, one reduce-scatter + tail all-reduce per bucket; replicated: one all-reduce per group of buckets
+        groups = None if self.sharded else self.exchange_groups(e)
 
-        groups = self.exchange_groups(e)
-
-        def reduce_bucket(b):
-            if self.sharded:             # (no coalescing: one reduce-scatter + tail all-reduce per bucket)
-                ev = torch.cuda.Event()
-                ev.record(main)
-                self._comm_stream.wait_event(ev)
-                with torch.cuda.stream(self._comm_stream):
-                    if self.exchange:
-                        self._exchange_shard(e, b, self._comm_stream)
-                    self._pending.append(None)
+        def exchange_bucket(b):
+            if groups is not None and b not in groups:   # a bucket inside a coalesced group: exchanged with the group's last bucket
                 return
-            if b not in groups:          # a bucket inside a coalesced group: exchanged with the group's last bucket
-                return
-            off, cnt = groups[b]
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self._comm_stream.wait_event(ev)
-            with torch.cuda.stream(self._comm_stream):
-                if not self.exchange:
-                    self._pending.append(None)
-                elif self.abi_comm:   # RCCL through the C ABI on the side stream (works at world 1 too: a one-rank communicator)
-                    e.allreduce_range_async(off, cnt, self.fp32_reduce, self._comm_stream)
-                    self._pending.append(None)
-                elif self.world > 1 or (self.force_staged and dist.is_available() and dist.is_initialized()):
-                    # (a ONE-rank process group with GGET_FORCE_STAGED=1 still issues the collectives: the real backend - RCCL - runs the
-                    #  whole exchange schedule on a one-GPU box, tests/test_gpu_dist.py::test_torch_rccl_one_rank_group_through_staged_backward)
-                    self._pending.append(all_reduce_bucket(e.grad_bf16, (off, cnt), self.pg, async_op=True,
-                                                           fp32_accumulate=self.fp32_reduce))
-                else:  # single-rank dry run of the staged path (tests): the exchange is the identity
-                    self._pending.append(None)
+            with torch.cuda.stream(self._comm_behind_main(e)):
+                work = None                 # (`exchange` off, a dry run or a stream-ordered collective: nothing for step() to wait on)
+                if self.exchange:
+                    work = tx.reduce_scatter(e, b) if groups is None else tx.all_reduce(e, *groups[b])
+                self._pending.append(work)
 
         e.backward_begin()
-        reduce_bucket(0)
+        exchange_bucket(0)
         for i in range(L_ - 1, -1, -1):
             e.backward_layer(i)
-            reduce_bucket(L_ - i)
+            exchange_bucket(L_ - i)
         e.backward_end()
-        reduce_bucket(L_ + 1)
+        exchange_bucket(L_ + 1)
+
+    def _comm_behind_main(self, e):
+        """The side stream, made to wait for everything the current stream holds so far."""
+        if self._comm_stream is None:
+            self._comm_stream = torch.cuda.Stream(device=e.device)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self._comm_stream.wait_event(ev)
+        return self._comm_stream
 
     # -- sharded optimizer step (ZeRO stage 2)
     def _ensure_shard(self, e):
@@ -400,49 +215,19 @@ class GgetEngine:
         if e.shard != (self.world, self.rank):
             e.shard_init(self.world, self.rank)
 
-    def _exchange_shard(self, e, b: int, stream):
-        """Reduce-scatter of bucket b's body + all-reduce of its tail, on the current stream (the side stream when overlapped)."""
-        if self.abi_comm:
-            e.reduce_scatter_grads_async(b, self.fp32_reduce, stream)
-        else:
-            reduce_scatter_bucket(e.grad_bf16, e.shard_buckets[b], self.rank, self.world, self.pg, self.fp32_reduce)
-
     def _sharded_update(self, e, lr, o, grad_scale):
         from . import _lib as L
+        tx = pick_transport(self)
         e.shard_sqnorm_partials()
-        if self.abi_comm:
-            e.shard_allgather_async(L.SHARD_SLOTS)      # (a no-op on the loopback, which summed every rank's chunks itself)
-        else:
-            self._gather_slots(e)
+        tx.all_gather(e, L.SHARD_SLOTS)
         gn = e.adamw_step_sharded(lr, o.betas[0], o.betas[1], o.eps, o.weight_decay, o.max_grad_norm, grad_scale)
         # the bf16 weights: every rank's updated slices gathered on the side stream behind AdamW; the next reader of the weights waits
-        if self._comm_stream is None:
-            self._comm_stream = torch.cuda.Stream(device=e.device)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self._comm_stream.wait_event(ev)
-        with torch.cuda.stream(self._comm_stream):
-            self._gather_arena(e, L.SHARD_PARAMS, self._comm_stream)
+        with torch.cuda.stream(self._comm_behind_main(e)):
+            tx.all_gather(e, L.SHARD_PARAMS)
             done = torch.cuda.Event()
             done.record(self._comm_stream)
         e._params_ready = done
         return gn
-
-    def _gather_slots(self, e):
-        slots = e.shard_slots
-        n = slots.numel() // self.world
-        dev = torch.device("cpu") if _host_staged(slots, self.pg) else slots.device
-        out = torch.empty(slots.numel(), dtype=slots.dtype, device=dev)
-        dist.all_gather_into_tensor(out, slots[self.rank * n: (self.rank + 1) * n].to(dev).clone(), group=self.pg)
-        slots.copy_(out)
-
-    def _gather_arena(self, e, what: int, stream):
-        if self.abi_comm:
-            e.shard_allgather_async(what, stream)
-            return
-        arena = {0: e.param_bf16, 1: e.master, 2: e.adam_m, 3: e.adam_v}[what]
-        for plan in reversed(e.shard_buckets):       # embeddings, layer 0, ..., heads: the order the forward reads them
-            all_gather_bucket(arena, plan, self.rank, self.world, self.pg)
 
     def consolidate(self):
         """Collective (every rank calls it): after sharded steps, all-gather the fp32 master weights and the Adam moments so that every
@@ -453,31 +238,14 @@ class GgetEngine:
             return
         e.await_params()
         from . import _lib as L
+        tx = pick_transport(self)
         for what in (L.SHARD_MASTER, L.SHARD_ADAM_M, L.SHARD_ADAM_V):
-            self._gather_arena(e, what, None)
+            tx.all_gather(e, what)
         e.shard_stale = False
 
     def exchange_groups(self, e) -> Dict[int, Any]:
-        """{last bucket of a group: (offset, count)} - what one collective covers.  Buckets are numbered in completion order and laid
-        out back to front in the flat array, so consecutive buckets are adjacent ranges; a group is closed when it reaches
-        GGET_DP_BUCKET_MB (or at the last bucket).  Non-adjacent neighbours (never the case for the engine's layout) close a group too."""
-        if self._groups is not None and self._groups[0] is e:
-            return self._groups[1]
-        groups, lo, hi = {}, None, None
-        thresh = self.bucket_mb * 2 ** 20 / 2        # elements (bf16)
-        nb = len(e.buckets)
-        for b, (off, cnt) in enumerate(e.buckets):
-            if lo is not None and (off + cnt == lo or off == hi):
-                lo, hi = min(lo, off), max(hi, off + cnt)
-            else:
-                if lo is not None:
-                    groups[b - 1] = (lo, hi - lo)
-                lo, hi = off, off + cnt
-            if hi - lo >= thresh or b == nb - 1:
-                groups[b] = (lo, hi - lo)
-                lo = hi = None
-        self._groups = (e, groups)
-        return groups
+        """{last bucket of a group: (offset, count)} - what one collective covers at this engine's `bucket_mb` (dp.exchange_groups)."""
+        return exchange_groups(e.buckets, self.bucket_mb)
 
     # -- the data-parallel launch menu, decided by measurement on the machine the job runs on
     def set_dp_menu(self, overlap: Optional[bool] = None, reserve_cus: Optional[int] = None):
@@ -496,7 +264,7 @@ class GgetEngine:
         (after `warm`), max over ranks, the decision broadcast from rank 0 so that every rank takes the same.  `step_fn()` runs one
         step (forward + backward + step) on this rank.  The probe steps are ordinary training steps (the replicas stay identical).
         Returns {"menus": [...], "chosen": {...}}; a single-rank engine returns without measuring."""
-        if self.world <= 1 or not (dist.is_available() and dist.is_initialized()):
+        if self.world <= 1 or not dist_ready():
             return {"menus": [], "chosen": {"overlap": self.overlap, "reserve_cus": self.reserved_cus}, "probed": False}
         if menus is None:
             menus = [dict(overlap=True, reserve_cus=0), dict(overlap=False, reserve_cus=0), dict(overlap=True, reserve_cus=32)]
@@ -525,9 +293,7 @@ class GgetEngine:
     def describe_dp(self) -> Dict[str, Any]:
         """What the data-parallel exchange of this engine looks like (bench.py prints it on N > 1 lines)."""
         e = self.module._engine
-        live = dist.is_available() and dist.is_initialized() and (self.world > 1 or self.force_staged)
-        backend = dist.get_backend(self.pg) if live else "none"
-        info = {"world": self.world, "backend": ("rccl-via-c-abi" if self.abi_comm else f"torch.distributed/{backend}"),
+        info = {"world": self.world, "backend": pick_transport(self).name,
                 "n_buckets": len(e.buckets) if e is not None else None, "overlap_with_backward": bool(self.overlap),
                 "reduce_dtype": "fp32" if self.fp32_reduce else "bf16",
                 "bucket_mb": [round(c * 2 / 2 ** 20, 1) for _, c in e.buckets] if e is not None else None,
@@ -866,7 +632,7 @@ def evaluate(model, loader, eval_name: str = "valid", do_eval: bool = True):
     `do_eval=False` returns (None, None)."""
     if not do_eval:
         return None, None
-    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    world = dist.get_world_size() if dist_ready() else 1
     rank = dist.get_rank() if world > 1 else 0
     model.eval()
     device = model.device
@@ -906,7 +672,7 @@ def _check_deferred_all_ranks(model):
         m.check_deferred()
     except (IndexError, ValueError) as ex:
         err = ex
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if dist_ready() and dist.get_world_size() > 1:
         dev = m.device if dist.get_backend() == "nccl" else torch.device("cpu")
         flag = torch.tensor([1 if err is not None else 0], device=dev, dtype=torch.int32)
         dist.all_reduce(flag, op=dist.ReduceOp.MAX)
@@ -915,20 +681,6 @@ def _check_deferred_all_ranks(model):
                                "count mismatch): see that rank's error")
     if err is not None:
         raise err
-
-
-def all_gather_varlen(q: torch.Tensor) -> torch.Tensor:
-    """reference misc_utils.all_gather (:472-504): concatenates per-rank tensors of different lengths along dim 0."""
-    ws = dist.get_world_size()
-    local = torch.tensor(q.shape[0], device=q.device)
-    sizes = [torch.zeros_like(local) for _ in range(ws)]
-    dist.all_gather(sizes, local)
-    mx = int(max(sizes).item())
-    if mx > q.shape[0]:
-        q = torch.cat([q, torch.zeros([mx - q.shape[0]] + list(q.shape[1:]), device=q.device, dtype=q.dtype)], dim=0)
-    out = [torch.zeros_like(q) for _ in range(ws)]
-    dist.all_gather(out, q)
-    return torch.cat([o[: int(n)] for o, n in zip(out, sizes)])
 
 
 @torch.no_grad()
@@ -962,7 +714,7 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
         raise ValueError(f"ft_evaluate: the {eval_name} loader yielded no batch")
     test_loss = test_loss / j
     input_dict = cls_metrics.to_dict()
-    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    world = dist.get_world_size() if dist_ready() else 1
     if world > 1:
         gdev = device if dist.get_backend() == "nccl" else torch.device("cpu")
         input_dict = {k: all_gather_varlen(v.to(gdev)).cpu() for k, v in input_dict.items()}
@@ -974,37 +726,6 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
     if res is None:
         res = cls_metrics.results_in_dict()
     return test_loss, cls_metrics, res, input_dict
-
-
-# ----------------------------------------------------------------------------- distributed env
-
-def dp_env_defaults() -> int:
-    """Environment a multi-process job wants BEFORE its process group / communicator exists: the collective library is held to as many
-    channels (= workgroups) as the GEMM launches leave CUs free - GGET_DP_RESERVE_CUS = R, OFF by default (0: tools/dp_standin.py measured that
-    16 free CUs do not protect the exact-fit launches and that 32 cost more than the collisions they prevent at the 8-GPU residency of the
-    collectives); an NCCL_MAX_NCHANNELS the user set wins.  Returns R (GgetEngine applies the GEMM side: the handle's data-parallel menu)."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    r = max(0, int(os.environ.get("GGET_DP_RESERVE_CUS", "0"))) if world > 1 else 0
-    if r:
-        os.environ.setdefault("NCCL_MAX_NCHANNELS", str(r))
-    return r
-
-def set_dist_env(backend: Optional[str] = None):
-    """reference misc_utils.set_dist_env (:507-539): env:// rendezvous, one process per GPU, barrier."""
-    dp_env_defaults()
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if torch.cuda.is_available():
-        torch.cuda.set_device(local)
-    if world > 1 and not dist.is_initialized():
-        backend = backend or ("nccl" if torch.cuda.is_available() else "gloo")
-        kw = {}
-        if backend == "nccl":
-            kw["device_id"] = torch.device("cuda", local)
-        dist.init_process_group(backend=backend, init_method="env://", **kw)
-        dist.barrier()
-    return rank, local, world
 
 
 # ----------------------------------------------------------------------------- pipeline

@@ -263,7 +263,7 @@ def test_exchange_groups_coalesce_buckets_in_completion_order():
     e = types.SimpleNamespace(buckets=list(zip(offs, sizes)))
     eng = tr.GgetEngine.__new__(tr.GgetEngine)
     for mb, want in ((0, 14), (40, 5), (60, 4), (10 ** 6, 1)):
-        eng.bucket_mb, eng._groups = mb, None
+        eng.bucket_mb = mb
         groups = eng.exchange_groups(e)
         assert len(groups) == want
         covered = sorted((off, off + cnt) for off, cnt in groups.values())
@@ -273,5 +273,5 @@ def test_exchange_groups_coalesce_buckets_in_completion_order():
             assert off == e.buckets[last][0] and (mb == 0 or cnt * 2 >= mb * 2 ** 20 or last == len(sizes) - 1)
     # neighbours that are NOT adjacent in memory are never merged
     e2 = types.SimpleNamespace(buckets=[(100, 10), (50, 10), (40, 10)])
-    eng.bucket_mb, eng._groups = 10 ** 6, None
+    eng.bucket_mb = 10 ** 6
     assert eng.exchange_groups(e2) == {0: (100, 10), 2: (40, 20)}

@@ -81,7 +81,6 @@ def run_schedule(menu, blocks, gbps, world=8, steps=12, warm=4):
     main = torch.cuda.current_stream()
 
     eng.bucket_mb = float(os.environ.get("DP_STANDIN_BUCKET_MB", "0"))      # (GGET_DP_BUCKET_MB: consecutive buckets in ONE collective)
-    eng._groups = None
     groups = eng.exchange_groups(e)
 
     def bucket(b):
