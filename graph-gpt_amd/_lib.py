@@ -46,6 +46,10 @@ SIGNATURES = {
     "gget_bucket_count": (i32, [vp]),
     "gget_bucket_range": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64)]),
     "gget_sync_params": (i32, [vp, vp]),
+    "gget_ema_attach": (i32, [vp, vp]),
+    "gget_set_ema_decay": (i32, [vp, f32]),
+    "gget_ema_update": (i32, [vp, f32, vp]),
+    "gget_ema_to_params": (i32, [vp, vp]),
     "gget_forward_pretrain": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "gget_forward_pretrain_packed": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "gget_forward_task": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
@@ -129,7 +133,7 @@ GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 OPT_NORM_FROM_BACKWARD = 1   # gget_set_option
 OPT_SKIP_NONFINITE_STEP = 2
 SHARD_CHUNK = 4096   # include/gget.h GGET_SHARD_CHUNK: the sharded norm's chunk grid and the granule of the body slices
-SHARD_PARAMS, SHARD_MASTER, SHARD_ADAM_M, SHARD_ADAM_V, SHARD_SLOTS = 0, 1, 2, 3, 4   # gget_shard_allgather_async arenas
+SHARD_PARAMS, SHARD_MASTER, SHARD_ADAM_M, SHARD_ADAM_V, SHARD_SLOTS, SHARD_EMA = 0, 1, 2, 3, 4, 5   # gget_shard_allgather_async arenas
 TOKENS_AUTO = -2   # gget_set_token_count: count the real tokens on the device (include/gget.h GGET_TOKENS_AUTO)
 EPI_NONE, EPI_RESIDUAL, EPI_ATOMIC_F32, EPI_SLAB_F32 = 0, 1, 2, 3
 

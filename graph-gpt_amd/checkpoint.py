@@ -25,6 +25,7 @@ import torch
 
 MODEL_NAME = "model.pt"          # reference misc_utils.py:25
 _CANDIDATES = (MODEL_NAME, "model.safetensors", "pytorch_model.bin")
+EMA_NAME, EMA_BEST_NAME = "model_ema.pt", "model_ema_best.pt"      # reference src/conf/stats_configs.py:95-98 (EMAConfig)
 
 
 def _scan_ckps(pretrain_cpt: str):
@@ -169,6 +170,19 @@ def load_from_ckp(pretrain_cpt: str, output_dir: str, model, config=None, skip_k
         ckp, _ = get_latest_ckp(pretrain_cpt)
         model = load_from_ckp_with_try(model, ckp, skip_keys, strict)
     return model
+
+
+def save_ema_state_dict(state: Dict[str, torch.Tensor], output_dir: str, best: bool = False) -> str:
+    """`EMAStats.save_ema_ckp` (reference stats_configs.py:138-146): the averaged weights as a plain state dict with the reference's keys
+    in <output_dir>/model_ema.pt, and in model_ema_best.pt as well when `best` - the file `read_state_dict(ckp, use_ema=True)` and the
+    reference's loader (loader_utils.py:181-189) look for next to the `epoch_<n>` directories."""
+    os.makedirs(output_dir, exist_ok=True)
+    sd = {k: v.detach().float().cpu().contiguous() for k, v in state.items()}
+    path = os.path.join(output_dir, EMA_NAME)
+    torch.save(sd, path)
+    if best:
+        torch.save(sd, os.path.join(output_dir, EMA_BEST_NAME))
+    return path
 
 
 def save_model(model, output_dir: str, ddp_prefix: bool = False):

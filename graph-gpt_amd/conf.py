@@ -172,7 +172,10 @@ def optim_from_training(train_cfg, use_deepspeed: bool, finetune: bool):
       reproduced on purpose: min_lr = lr).  `training.optimizer.min_lr` (0.1 * lr, pretrain_mode.py:108) is not read on this path.
     * DeepSpeed + a torch scheduler (fine-tuning, OneCycleLR): total_steps = total_num_steps, pct_start = warmup / total,
       min_lr = optimizer.min_lr (conf_utils.py:106-131).
-    * DDP (no DeepSpeed JSON): OneCycleLR over total_num_steps + 1 steps, min_lr = optimizer.min_lr (opt_utils.py:25-33)."""
+    * DDP (no DeepSpeed JSON): OneCycleLR over total_num_steps + 1 steps, min_lr = optimizer.min_lr (opt_utils.py:25-33).
+    * Weight EMA: `training.optimizer.use_ema` / `ema_decay` pass through on both branches.  Fine-tuning hands `ema_decay` to the
+      average (finetune_mode.py:256); pre-training calls `init_ema(model)` WITHOUT it (pretrain_mode.py:302), so a pre-training run with
+      `use_ema` averages with timm's default 0.9999 whatever `ema_decay` says - REPRODUCED here: a pre-train OptimConfig carries 0.9999."""
     from .training import OptimConfig
     oc, sc = _get(train_cfg, "optimizer"), _get(train_cfg, "schedule")
     total, warm = _get(sc, "total_num_steps"), _get(sc, "warmup_num_steps")
@@ -181,7 +184,9 @@ def optim_from_training(train_cfg, use_deepspeed: bool, finetune: bool):
                          "token budget (update_num_steps) or the epoch budget (update_ft_num_steps)")
     lr = float(_get(oc, "lr"))
     kw = dict(lr=lr, betas=tuple(_get(oc, "betas")), eps=float(_get(oc, "eps")), weight_decay=float(_get(oc, "weight_decay")),
-              max_grad_norm=float(_get(oc, "max_grad_norm")), warmup_num_steps=int(warm), total_num_steps=int(total))
+              max_grad_norm=float(_get(oc, "max_grad_norm")), warmup_num_steps=int(warm), total_num_steps=int(total),
+              use_ema=bool(_get(oc, "use_ema", False)),
+              ema_decay=float(_get(oc, "ema_decay", 0.9999)) if finetune else 0.9999)
     if use_deepspeed:
         # conf_utils.py:59-66: the DS engine gets `gradient_accumulation_steps` (its step() fires at the boundary only)
         kw["gradient_accumulation_steps"] = int(_get(oc, "gradient_accumulation_steps", 1) or 1)

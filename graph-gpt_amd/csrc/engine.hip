@@ -398,6 +398,8 @@ struct gget_engine {
   float* master;
   float* am;
   float* av;
+  float* ema = nullptr;           // weight-EMA arena (gget_ema_attach; fp32 [n_params], the offsets of the other arenas), or none
+  float ema_decay_next = -1.f;    // decay the NEXT gget_adamw_step[_sharded] applies (gget_set_ema_decay); < 0 = that step leaves the EMA alone
   bf16_t* G;
   unsigned char* W;
   const float* cos_tab;
@@ -788,6 +790,39 @@ extern "C" int gget_set_dropout(gget_handle_t h, float attention_p, float path_p
   h->path_drop_p = path_p;
   h->attn_drop_seed = seed;
   return 0;
+}
+
+extern "C" int gget_ema_attach(gget_handle_t h, float* ema_dev) {
+  GGET_REQUIRE(h != nullptr, "ema_attach: null handle");
+  h->ema = ema_dev;
+  h->ema_decay_next = -1.f;
+  if (ema_dev && h->plan.lm_pad_count)    // as gget_create: the pad rows read as zeros whatever the caller's arena held
+    GGET_HIP_CHECK(hipMemset(ema_dev + h->plan.lm_pad_off, 0, h->plan.lm_pad_count * 4));
+  return 0;
+}
+
+extern "C" int gget_set_ema_decay(gget_handle_t h, float decay) {
+  GGET_REQUIRE(h != nullptr, "set_ema_decay: null handle");
+  GGET_REQUIRE(decay <= 1.f, "set_ema_decay: decay %g > 1", (double)decay);     // (NaN fails the comparison too)
+  GGET_REQUIRE(decay < 0.f || h->ema, "set_ema_decay: no EMA arena (gget_ema_attach)");
+  h->ema_decay_next = decay < 0.f ? -1.f : decay;
+  return 0;
+}
+
+extern "C" int gget_ema_update(gget_handle_t h, float decay, void* stream) {
+  GGET_REQUIRE(h != nullptr, "ema_update: null handle");
+  GGET_REQUIRE(h->ema && h->master, "ema_update: no EMA arena (gget_ema_attach) or no fp32 master arena");
+  GGET_REQUIRE(decay >= 0.f && decay <= 1.f, "ema_update: decay %g outside [0, 1]", (double)decay);
+  if (h->shard_world > 0)     // this rank's share (body slices + every tail; all of them for the loopback), as the sharded AdamW step
+    return k_ema_lerp_items(h->master, h->ema, h->shard_items(), h->shard_nitems, decay, (hipStream_t)stream);
+  return k_ema_lerp(h->master, h->ema, h->plan.n_params, decay, (hipStream_t)stream);
+}
+
+extern "C" int gget_ema_to_params(gget_handle_t h, void* stream) {
+  GGET_REQUIRE(h != nullptr, "ema_to_params: null handle");
+  GGET_REQUIRE(h->ema, "ema_to_params: no EMA arena (gget_ema_attach)");
+  h->wo_packed = false;      // a parameter write, as gget_sync_params: the per-sample kernels must not keep evaluating the live weights' packed copies
+  return k_f32_to_bf16(h->ema, h->P, h->plan.n_params, (hipStream_t)stream);
 }
 
 extern "C" int gget_sync_params(gget_handle_t h, void* stream) {
@@ -2163,6 +2198,9 @@ extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float bet
   GGET_REQUIRE(h && h->master && h->am && h->av, "adamw needs master/m/v arenas");
   GGET_REQUIRE(step >= 1, "step is 1-based");
   hipStream_t st = (hipStream_t)stream;
+  const float ema_decay = h->ema_decay_next;      // (gget_set_ema_decay: consumed by this call)
+  h->ema_decay_next = -1.f;
+  float* ema = ema_decay >= 0.f ? h->ema : nullptr;
   h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies)
   float* sq = h->wsp<float>(h->ws.sqnorm);
   const bool need_norm = max_grad_norm > 0.f || gnorm_dev != nullptr || h->opt_skip_nonfinite;
@@ -2176,7 +2214,7 @@ extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float bet
     } else if (int e = k_grad_sqnorm(h->G, h->plan.n_params, sq, st)) return e;
   }
   return k_adamw(h->master, h->am, h->av, h->G, h->P, h->plan.n_params, lr, beta1, beta2, eps, weight_decay, step,
-                 max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite);
+                 max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay);
 }
 
 // ================================================================================================
@@ -2272,6 +2310,9 @@ extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, f
   GGET_REQUIRE(h->shard_world > 0, "adamw_step_sharded: call gget_shard_init first");
   GGET_REQUIRE(step >= 1, "step is 1-based");
   hipStream_t st = (hipStream_t)stream;
+  const float ema_decay = h->ema_decay_next;      // (gget_set_ema_decay: consumed by this call)
+  h->ema_decay_next = -1.f;
+  float* ema = ema_decay >= 0.f ? h->ema : nullptr;
   h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies from the gathered weights)
   float* sq = h->wsp<float>(h->ws.sqnorm);
   const bool need_norm = max_grad_norm > 0.f || gnorm_dev != nullptr || h->opt_skip_nonfinite;
@@ -2280,7 +2321,7 @@ extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, f
     if (int e = k_grad_sqnorm_slots(slots_dev, h->shard_slot_of(), h->shard_nglobal, sq, st)) return e;
   }
   return k_adamw_items(h->master, h->am, h->av, h->G, h->P, h->shard_items(), h->shard_nitems, lr, beta1, beta2, eps, weight_decay, step,
-                       max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite);
+                       max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay);
 }
 
 extern "C" int gget_head_counts(gget_handle_t h, int32_t counts[2], void* stream) {
@@ -2847,9 +2888,11 @@ extern "C" int gget_reduce_scatter_grads_async(gget_handle_t h, int bucket, int 
 extern "C" int gget_shard_allgather_async(gget_handle_t h, int what, float* slots_dev, void* stream) {
   GGET_REQUIRE(h && (h->comm || h->comm_loopback), "shard_allgather: call gget_comm_init first");
   GGET_REQUIRE(h->shard_world > 0, "shard_allgather: call gget_shard_init first");
-  GGET_REQUIRE(what >= GGET_SHARD_PARAMS && what <= GGET_SHARD_SLOTS, "shard_allgather: unknown arena %d", what);
+  GGET_REQUIRE(what >= GGET_SHARD_PARAMS && what <= GGET_SHARD_EMA, "shard_allgather: unknown arena %d", what);
   GGET_REQUIRE(what != GGET_SHARD_SLOTS || slots_dev, "shard_allgather: null slot vector");
-  GGET_REQUIRE(what == GGET_SHARD_PARAMS || what == GGET_SHARD_SLOTS || (h->master && h->am && h->av), "shard_allgather: no fp32 state");
+  GGET_REQUIRE(what != GGET_SHARD_EMA || h->ema, "shard_allgather: no EMA arena (gget_ema_attach)");
+  GGET_REQUIRE(what == GGET_SHARD_PARAMS || what == GGET_SHARD_SLOTS || what == GGET_SHARD_EMA || (h->master && h->am && h->av),
+               "shard_allgather: no fp32 state");
   if (h->comm_loopback) return 0;    // (the loopback handle updated and summed every rank's share itself)
   hipStream_t st = (hipStream_t)stream;
   ncclComm_t c = static_cast<ncclComm_t>(h->comm);
@@ -2867,7 +2910,7 @@ extern "C" int gget_shard_allgather_async(gget_handle_t h, int what, float* slot
     if (what == GGET_SHARD_PARAMS) {
       GGET_RCCL_CHECK(rccl()->AllGather(h->P + mine, h->P + b.off, b.slice, ncclBfloat16, c, st));
     } else {
-      float* x = what == GGET_SHARD_MASTER ? h->master : what == GGET_SHARD_ADAM_M ? h->am : h->av;
+      float* x = what == GGET_SHARD_MASTER ? h->master : what == GGET_SHARD_ADAM_M ? h->am : what == GGET_SHARD_ADAM_V ? h->av : h->ema;
       GGET_RCCL_CHECK(rccl()->AllGather(x + mine, x + b.off, b.slice, ncclFloat32, c, st));
     }
   }

@@ -122,12 +122,21 @@ int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchun
 constexpr int kAdamwItemElems = 2048;
 int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st);
 int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, float* ws, hipStream_t st);
+// ema != nullptr (both AdamW launches): the weight EMA fused into the update - ema' = w' + ema_decay * (ema - w') against the NEW weights,
+// or against the unchanged ones when the skip rule drops the step
 int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
                   float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
-                  float* gnorm_out, hipStream_t st, bool skip_nonfinite);
+                  float* gnorm_out, hipStream_t st, bool skip_nonfinite, float* ema = nullptr, float ema_decay = 0.f);
 int k_adamw(float* master, float* m, float* v, const void* grad, void* param, size_t n, float lr, float beta1, float beta2,
             float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm, float* gnorm_out,
-            hipStream_t st, bool skip_nonfinite = false);   // skip_nonfinite: leave everything untouched when the gradient norm is inf / NaN
+            hipStream_t st, bool skip_nonfinite = false,   // skip_nonfinite: leave everything untouched when the gradient norm is inf / NaN
+            float* ema = nullptr, float ema_decay = 0.f);
+// weight EMA, stand-alone (reference: timm ModelEmaV3.update through src/utils/patch_utils.py:10-39).  THE formula, here and fused into
+// AdamW (one device function, kernels.hip ema_lerp4):  ema' = w + d * (ema - w)  in fp32 - fmaf(d, ema - w, w), d the fp32 decay exactly as
+// it crossed the ABI.  d = 0 gives ema' == w bit for bit (the arena is seeded that way); no 1 - d is formed (float32(0.9999) is off by up
+// to 3e-8 = 3e-4 of 1 - d).  n a multiple of 4; the items variant runs over a shard plan's work items.
+int k_ema_lerp(const float* master, float* ema, size_t n, float d, hipStream_t st);
+int k_ema_lerp_items(const float* master, float* ema, const GgetSqChunk* items_dev, int nitems, float d, hipStream_t st);
 constexpr int kZeroRanges = 6;
 struct GgetZeroRanges {
   void* ptr[kZeroRanges];

@@ -1751,11 +1751,32 @@ __device__ __forceinline__ bool adamw_coef(float grad_scale, float max_norm, con
   return true;
 }
 
+// weight EMA (reference: timm ModelEmaV3.apply_update_ as patched by src/utils/patch_utils.py:10-39, ema.lerp_(model, 1 - decay)): the
+// lerp of four consecutive elements (vector index i) against the weights w, ONE definition for the fused and the stand-alone kernels.
+// The formula is fixed (kernels.h): ema' = w + d * (ema - w) in fp32, one fused multiply-add on the rounded difference, d as it crossed
+// the ABI - no 1 - d is formed, and d = 0 returns w.  The arena is streamed once per step: non-temporal 16-byte load and store.
+__device__ __forceinline__ void ema_lerp4(float* __restrict__ ema, size_t i, const float (&w)[4], float d) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v e = __builtin_nontemporal_load(reinterpret_cast<f4v*>(ema) + i);
+  const f4v o = {fmaf(d, e.x - w[0], w[0]), fmaf(d, e.y - w[1], w[1]), fmaf(d, e.z - w[2], w[2]), fmaf(d, e.w - w[3], w[3])};
+  __builtin_nontemporal_store(o, reinterpret_cast<f4v*>(ema) + i);
+}
+// ... against the master weights as they are in memory (no AdamW update in front: stand-alone launch, skipped step)
+__device__ __forceinline__ void ema_update4(const float* __restrict__ master, float* __restrict__ ema, size_t i, float d) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v w = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(master) + i);
+  const float wp[4] = {w.x, w.y, w.z, w.w};
+  ema_lerp4(ema, i, wp, d);
+}
+
 // the per-element AdamW update of four consecutive elements (vector index i): ONE definition for both kernels, so that a sharded update
-// is bit-identical to the replicated one given the same coefficient
+// is bit-identical to the replicated one given the same coefficient.  EMA: the lerp of the weight EMA against the NEW weights, taken
+// from the registers (the master arena is not read a second time); without it the function is what it was before the EMA existed.
+template <bool EMA>
 __device__ __forceinline__ void adamw_update4(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
                                               const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t i, float coef,
-                                              float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt) {
+                                              float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt,
+                                              float* __restrict__ ema, float ema_decay) {
   typedef float f4v __attribute__((ext_vector_type(4)));
   typedef unsigned u2v __attribute__((ext_vector_type(2)));
   const u2v gr = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(grad + i * 4));
@@ -1781,6 +1802,7 @@ __device__ __forceinline__ void adamw_update4(float* __restrict__ master, float*
   o.x = pack2bf(wp[0], wp[1]);
   o.y = pack2bf(wp[2], wp[3]);
   __builtin_nontemporal_store(u2v{o.x, o.y}, reinterpret_cast<u2v*>(param + i * 4));
+  if (EMA) ema_lerp4(ema, i, wp, ema_decay);
 }
 
 template <int UNR>
@@ -1798,7 +1820,30 @@ __global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ maste
   for (int u = 0; u < UNR; ++u) {
     const size_t i = i0 + u * stride;
     if (i >= nv) break;
-    adamw_update4(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
+    adamw_update4<false>(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, nullptr, 0.f);
+  }
+}
+// the same launch with the weight EMA fused in: one more fp32 arena read and written (28 -> 36 B per parameter).  A step the skip rule
+// drops still averages - against the unchanged master weights (the reference calls update_ema after every batch whether or not the
+// optimizer stepped, src/training/finetune_mode.py:405-413); the decision is uniform over the launch
+template <int UNR>
+__global__ void __launch_bounds__(kBlock) adamw_ema_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
+                                                           const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
+                                                           float lr, float beta1, float beta2, float eps, float wd, float bc1,
+                                                           float bc2_sqrt, float max_norm, float grad_scale,
+                                                           const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite,
+                                                           float* __restrict__ ema, float ema_decay) {
+  float coef;
+  const bool go = adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef);
+  const size_t nv = n >> 2;
+  const size_t stride = (size_t)gridDim.x * kBlock;
+  for (size_t i0 = (size_t)blockIdx.x * kBlock + threadIdx.x; i0 < nv; i0 += stride * UNR)
+#pragma unroll
+  for (int u = 0; u < UNR; ++u) {
+    const size_t i = i0 + u * stride;
+    if (i >= nv) break;
+    if (go) adamw_update4<true>(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, ema, ema_decay);
+    else ema_update4(master, ema, i, ema_decay);
   }
 }
 
@@ -1815,7 +1860,45 @@ __global__ void __launch_bounds__(kBlock) adamw_items_kernel(float* __restrict__
   const GgetSqChunk it = items[blockIdx.x];
   const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
   for (size_t i = threadIdx.x; i < nv; i += kBlock)
-    adamw_update4(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
+    adamw_update4<false>(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, nullptr, 0.f);
+}
+__global__ void __launch_bounds__(kBlock) adamw_items_ema_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
+                                                                 const bf16_t* __restrict__ grad, bf16_t* __restrict__ param,
+                                                                 const GgetSqChunk* __restrict__ items, float lr, float beta1, float beta2,
+                                                                 float eps, float wd, float bc1, float bc2_sqrt, float max_norm,
+                                                                 float grad_scale, const float* __restrict__ sqnorm,
+                                                                 float* __restrict__ gnorm_out, int skip_nonfinite, float* __restrict__ ema,
+                                                                 float ema_decay) {
+  float coef;
+  const bool go = adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef);
+  const GgetSqChunk it = items[blockIdx.x];
+  const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
+  for (size_t i = threadIdx.x; i < nv; i += kBlock) {
+    if (go) adamw_update4<true>(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, ema, ema_decay);
+    else ema_update4(master, ema, v0 + i, ema_decay);      // (a skipped step still averages: adamw_ema_kernel)
+  }
+}
+
+// the stand-alone EMA lerp (12 B per parameter: master and ema read, ema written), needed where the reference averages although no AdamW
+// launch runs - the non-boundary micro-steps of a gradient accumulation, seeding (d = 0: ema = master, bit for bit) - in the form of
+// adamw_kernel<2>, and over the work items of a shard plan
+template <int UNR>
+__global__ void __launch_bounds__(kBlock) ema_lerp_kernel(const float* __restrict__ master, float* __restrict__ ema, size_t n, float d) {
+  const size_t nv = n >> 2;
+  const size_t stride = (size_t)gridDim.x * kBlock;
+  for (size_t i0 = (size_t)blockIdx.x * kBlock + threadIdx.x; i0 < nv; i0 += stride * UNR)
+#pragma unroll
+  for (int u = 0; u < UNR; ++u) {
+    const size_t i = i0 + u * stride;
+    if (i >= nv) break;
+    ema_update4(master, ema, i, d);
+  }
+}
+__global__ void __launch_bounds__(kBlock) ema_lerp_items_kernel(const float* __restrict__ master, float* __restrict__ ema,
+                                                                const GgetSqChunk* __restrict__ items, float d) {
+  const GgetSqChunk it = items[blockIdx.x];
+  const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
+  for (size_t i = threadIdx.x; i < nv; i += kBlock) ema_update4(master, ema, v0 + i, d);
 }
 
 __global__ void __launch_bounds__(kBlock) f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, size_t n) {
@@ -2880,14 +2963,32 @@ int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchun
 
 int k_adamw(float* master, float* m, float* v, const void* grad, void* param, size_t n, float lr, float beta1, float beta2,
             float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm, float* gnorm_out,
-            hipStream_t st, bool skip_nonfinite) {
+            hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay) {
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
   // one pass, two float4 groups per thread (grid up to 65536 blocks): the grid-stride form with 4096 blocks ran at 5.1 TB/s of
   // state traffic, this one at 6.0 (profiles/r02_adamw_sweep.txt); loads and the fp32 state stores are non-temporal
-  hipLaunchKernelGGL(adamw_kernel<2>, dim3(grid_for((long)(n / 8), kBlock, 65536)), dim3(kBlock), 0, st, master, m, v,
-                     (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
-                     grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
+  const dim3 grid(grid_for((long)(n / 8), kBlock, 65536));
+  if (ema)
+    hipLaunchKernelGGL(adamw_ema_kernel<2>, grid, dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1,
+                       beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0, ema, ema_decay);
+  else
+    hipLaunchKernelGGL(adamw_kernel<2>, grid, dim3(kBlock), 0, st, master, m, v,
+                       (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
+                       grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_ema_lerp(const float* master, float* ema, size_t n, float d, hipStream_t st) {
+  hipLaunchKernelGGL(ema_lerp_kernel<2>, dim3(grid_for((long)(n / 8), kBlock, 65536)), dim3(kBlock), 0, st, master, ema, n, d);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_ema_lerp_items(const float* master, float* ema, const GgetSqChunk* items_dev, int nitems, float d, hipStream_t st) {
+  if (nitems <= 0) return 0;
+  hipLaunchKernelGGL(ema_lerp_items_kernel, dim3(nitems), dim3(kBlock), 0, st, master, ema, items_dev, d);
   GGET_LAUNCH_CHECK();
   return 0;
 }
@@ -2907,12 +3008,17 @@ int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, f
 
 int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
                   float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
-                  float* gnorm_out, hipStream_t st, bool skip_nonfinite) {
+                  float* gnorm_out, hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay) {
   if (nitems <= 0) return 0;
   const float bc1 = 1.0f - powf(beta1, (float)step);      // (the constants exactly as k_adamw derives them)
   const float bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_items_kernel, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, items_dev,
-                     lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
+  if (ema)
+    hipLaunchKernelGGL(adamw_items_ema_kernel, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param,
+                       items_dev, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out,
+                       skip_nonfinite ? 1 : 0, ema, ema_decay);
+  else
+    hipLaunchKernelGGL(adamw_items_kernel, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, items_dev,
+                       lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
   GGET_LAUNCH_CHECK();
   return 0;
 }

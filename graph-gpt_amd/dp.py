@@ -216,7 +216,7 @@ class TorchTransport(NoTransport):
 
     def all_gather(self, e, what: int):
         arena = {L.SHARD_PARAMS: e.param_bf16, L.SHARD_MASTER: e.master, L.SHARD_ADAM_M: e.adam_m, L.SHARD_ADAM_V: e.adam_v,
-                 L.SHARD_SLOTS: e.shard_slots}[what]
+                 L.SHARD_SLOTS: e.shard_slots, L.SHARD_EMA: e.ema}[what]
         # the norm partials: one "bucket" without a tail; an arena: embeddings, layer 0, ..., heads - the order the forward reads them
         plans = [(0, 0, arena.numel() // self.g.world, 0, 0)] if what == L.SHARD_SLOTS else reversed(e.shard_buckets)
         for plan in plans:

@@ -104,6 +104,12 @@ class Engine:
         self.shard_slots = None
         # True while master / m / v hold stale values outside this rank's share (after a sharded step, until a consolidation)
         self.shard_stale = False
+        # weight EMA (ema_attach): the sixth arena, allocated on demand; `ema_live` = it holds an average (seeded or loaded), `ema_stale` =
+        # partitioned by sharded steps like master / m / v; `_params_are_ema` = the bf16 copy currently holds the averaged weights
+        self.ema = None
+        self.ema_live = False
+        self.ema_stale = False
+        self._params_are_ema = False
         self._params_ready = None   # event behind the all-gather of the bf16 copy: the next reader of the weights waits for it
         self._keep = None  # keeps the last batch tensors alive until backward has consumed them
 
@@ -119,7 +125,9 @@ class Engine:
     def view(self, name: str, which: str = "master") -> torch.Tensor:
         p = self.params[name]
         arena = {"master": self.master, "bf16": self.param_bf16, "grad": self.grad_bf16, "m": self.adam_m,
-                 "v": self.adam_v}[which]
+                 "v": self.adam_v, "ema": self.ema}[which]
+        if arena is None:
+            raise L.GgetError(f"view({name!r}, {which!r}): this engine has no such arena")
         return arena[p["offset"]: p["offset"] + p["numel"]].view(p["shape"])
 
     def load_state_dict(self, state: Dict[str, "np.ndarray | torch.Tensor"], strict: bool = True):
@@ -145,6 +153,67 @@ class Engine:
             raise L.GgetError("sync_params: the fp32 master weights are partitioned after a sharded (ZeRO-2) step - outside this rank's "
                               "share they are stale; call GgetEngine.consolidate() on every rank first")
         L.check(self.lib.gget_sync_params(self.h, _stream()))
+        self._params_are_ema = False
+
+    # ------------------------------------------------------------------ weight EMA (optimizer.use_ema)
+    def ema_attach(self):
+        """Allocate the EMA arena (zero-filled fp32 [n_params]) and hand it to the handle (gget_ema_attach); a no-op when it exists.
+        The arena holds nothing yet: seed it (ema_update(0.0)) or load one (load_ema_state_dict)."""
+        if self.ema is None:
+            self.ema = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()    # (gget_ema_attach clears the pad rows on the NULL stream)
+            L.check(self.lib.gget_ema_attach(self.h, _ptr(self.ema)))
+        return self.ema
+
+    def ema_detach(self):
+        L.check(self.lib.gget_ema_attach(self.h, None))
+        self.ema, self.ema_live, self.ema_stale = None, False, False
+
+    def set_ema_decay(self, decay: float):
+        """The decay the NEXT adamw_step / adamw_step_sharded applies inside its launch (gget_set_ema_decay); negative = leave the EMA alone."""
+        L.check(self.lib.gget_set_ema_decay(self.h, float(decay)))
+
+    def ema_update(self, decay: float):
+        """The stand-alone lerp ema <- master + decay * (ema - master) (gget_ema_update); decay 0 copies the master weights bit for bit."""
+        L.check(self.lib.gget_ema_update(self.h, float(decay), _stream()))
+        self.ema_live = True
+        if self.shard is not None and self.shard[0] > 1 and not getattr(self, "_loopback", False):
+            self.ema_stale = True       # (a shard plan: only this rank's share was averaged)
+
+    def ema_to_params(self):
+        """bf16 compute copy <- EMA arena (gget_ema_to_params): forwards run on the averaged weights until sync_params()."""
+        if self.ema is None or not self.ema_live:
+            raise L.GgetError("ema_to_params: this engine holds no weight EMA")
+        if self.ema_stale:
+            raise L.GgetError("ema_to_params: the weight EMA is partitioned after a sharded (ZeRO-2) step - outside this rank's share it "
+                              "is stale; call GgetEngine.consolidate() on every rank first")
+        self.await_params()
+        L.check(self.lib.gget_ema_to_params(self.h, _stream()))
+        self._params_are_ema = True
+
+    def ema_state_dict(self, shapes=None) -> "OrderedDict[str, torch.Tensor]":
+        """The averaged weights by state-dict name (clones); `shapes` = {name: shape} overrides the engine's own shapes with the
+        module's reference shapes (emb_mask_token is [1,1,embed_dim] there, flat in the arena)."""
+        if self.ema is None or not self.ema_live:
+            raise L.GgetError("ema_state_dict: this engine holds no weight EMA")
+        if self.ema_stale:
+            raise L.GgetError("ema_state_dict: the weight EMA is partitioned after a sharded (ZeRO-2) step and stale outside this rank's "
+                              "share; call GgetEngine.consolidate() on every rank first")
+        shapes = shapes or {}
+        return OrderedDict((k, self.view(k, "ema").detach().clone().reshape(tuple(shapes.get(k, p["shape"])))) for k, p in self.params.items())
+
+    def load_ema_state_dict(self, state: Dict[str, "np.ndarray | torch.Tensor"], strict: bool = True):
+        missing = [k for k in self.params if k not in state]
+        unexpected = [k for k in state if k not in self.params]
+        if strict and (missing or unexpected):
+            raise KeyError(f"EMA state dict mismatch: missing {missing[:4]} unexpected {unexpected[:4]}")
+        self.ema_attach()
+        for k, p in self.params.items():
+            if k in state:
+                self.view(k, "ema").copy_(torch.as_tensor(state[k]).to(torch.float32).reshape(p["shape"]).to(self.device))
+        if not missing:
+            self.ema_live, self.ema_stale = True, False
+        return missing, unexpected
 
     def await_params(self):
         """Make the current stream wait for the all-gather of the bf16 weights a sharded step left in flight (no-op otherwise)."""
@@ -370,6 +439,7 @@ class Engine:
                                                  self.step_count, _ptr(self.shard_slots), _ptr(self._gnorm), _stream()))
         if self.shard[0] > 1 and not getattr(self, "_loopback", False):    # (the loopback handle updates every rank's share itself)
             self.shard_stale = True
+            self.ema_stale = self.ema is not None and self.ema_live
         return self._gnorm[0]
 
     # ------------------------------------------------------------------ data-parallel exchange through the C ABI (RCCL)

@@ -311,6 +311,9 @@ class _GgetModel(nn.Module):
             new.adam_m.copy_(e.adam_m)
             new.adam_v.copy_(e.adam_v)
             new.step_count = e.step_count
+            if e.ema is not None:       # the weight EMA moves with the optimizer state
+                new.ema_attach().copy_(e.ema)
+                new.ema_live, new.ema_stale = e.ema_live, e.ema_stale
             new.comm_adopt(e)       # an RCCL communicator bound through the C ABI moves to the new handle
         for name, p in self._flat.items():
             p.data = new.view(name, "master").view(p.shape)      # (emb_mask_token is [1,1,e] in the reference, flat in the engine)
@@ -320,6 +323,8 @@ class _GgetModel(nn.Module):
             new.shard_stale = True
         else:
             new.sync_params()
+        if e is not None and e._params_are_ema:     # (inside GgetEngine.ema_weights: the new handle keeps evaluating the averaged weights)
+            new.ema_to_params()
         new.set_stack_method(getattr(self.config, "stack_method", None) == "long")
         new.set_rope_range(float(getattr(self.config, "rope_range", 0) or 0))
         new.set_dp_menu(*self._dp_menu)

@@ -10,6 +10,7 @@ Data parallelism: GgetEngine.backward is the exchange schedule; the collectives,
 from __future__ import annotations
 
 import abc
+import contextlib
 import math
 import os
 import time
@@ -56,7 +57,12 @@ class OptimConfig:
 
     def __init__(self, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, min_lr=0.0,
                  warmup_num_steps=0, total_num_steps=0, schedule="constant", onecycle_extra_step=1, gradient_accumulation_steps=1,
-                 zero_stage=0):
+                 zero_stage=0, use_ema=False, ema_decay=0.9999):
+        # `training.optimizer.use_ema` / `ema_decay` (reference base_configs.py:75-87; the fine-tune launch scripts run use_ema=true with
+        # 0.9999): GgetEngine keeps an exponential moving average of the fp32 master weights (see GgetEngine.ema_decay_at / step)
+        self.use_ema, self.ema_decay = bool(use_ema), float(ema_decay)
+        if not 0.0 <= self.ema_decay <= 1.0:
+            raise ValueError(f"ema_decay {ema_decay} outside [0, 1]")
         # DeepSpeed's zero_optimization.stage (examples/ds_config2_pt.json:29-32): 1 and 2 select the sharded optimizer step of a
         # data-parallel run (see GgetEngine; this engine partitions the work, not the buffers, so the two stages are one path), 0 the
         # replicated step; the environment variable GGET_ZERO_STAGE overrides it
@@ -133,6 +139,8 @@ class GgetEngine:
         # skipped (weights and Adam state untouched, Adam's step count not advanced) while the LR schedule still advances
         self.skip_nonfinite = False
         self.skipped_steps = 0
+        # weight EMA (optim.use_ema): step() calls so far that averaged = the reference's `train_stats.j` at its update_ema call
+        self.ema_updates = 0
         if self.world > 1 and torch.cuda.is_available():     # (DpOptions.reserve_cus: a real multi-process job only, not a loopback world)
             if real_world > 1:
                 self.reserved_cus = o.reserve_cus
@@ -231,17 +239,22 @@ class GgetEngine:
 
     def consolidate(self):
         """Collective (every rank calls it): after sharded steps, all-gather the fp32 master weights and the Adam moments so that every
-        rank holds the whole optimizer state again (what DeepSpeed's zero_to_fp32 does offline).  Needed before module.state_dict(),
-        save_checkpoint and Engine.sync_params; a no-op when nothing is stale."""
+        rank holds the whole optimizer state again (what DeepSpeed's zero_to_fp32 does offline) - and the weight EMA, which every rank
+        averages over its share only.  Needed before module.state_dict(), save_checkpoint, Engine.sync_params, ema_weights and
+        save_ema_checkpoint; a no-op when nothing is stale."""
         e = self.module._engine
-        if e is None or not e.shard_stale:
+        if e is None or not (e.shard_stale or e.ema_stale):
             return
         e.await_params()
         from . import _lib as L
         tx = pick_transport(self)
-        for what in (L.SHARD_MASTER, L.SHARD_ADAM_M, L.SHARD_ADAM_V):
-            tx.all_gather(e, what)
-        e.shard_stale = False
+        if e.shard_stale:
+            for what in (L.SHARD_MASTER, L.SHARD_ADAM_M, L.SHARD_ADAM_V):
+                tx.all_gather(e, what)
+            e.shard_stale = False
+        if e.ema_stale:
+            tx.all_gather(e, L.SHARD_EMA)
+            e.ema_stale = False
 
     def exchange_groups(self, e) -> Dict[int, Any]:
         """{last bucket of a group: (offset, count)} - what one collective covers at this engine's `bucket_mb` (dp.exchange_groups)."""
@@ -327,12 +340,82 @@ class GgetEngine:
             e._skip_nonfinite = on
         self.skip_nonfinite = on
 
+    # -- weight EMA (reference: EMAStats + timm ModelEmaV3, src/conf/stats_configs.py:102-146, src/utils/patch_utils.py:5-42)
+    def ema_decay_at(self, step: int) -> float:
+        """The decay of the update made when `step` loop iterations were done before it (the reference passes `train_stats.j`,
+        finetune_mode.py:413 / pretrain_mode.py:460).  timm's `ModelEmaV3.get_decay` with the defaults the reference constructs it with
+        (`update_after_step = 0`, `use_warmup = False`): 0.0 while step - 1 <= 0, the configured decay afterwards - the first two updates
+        copy the weights, from the third on it averages.  timm is a third-party dependency that is not installed here: the rule is
+        RESTATED from its published source and UNPINNED (no run of timm itself was available to check it against), like DeepSpeed's
+        WarmupDecayLR."""
+        return 0.0 if int(step) - 1 <= 0 else float(self.optim.ema_decay)
+
+    def _ema_engine(self, what: str):
+        e = self.module._engine
+        if e is None or e.ema is None or not e.ema_live:
+            raise RuntimeError(f"{what}: this engine holds no weight EMA (OptimConfig(use_ema=True) and at least one step, or load_ema_checkpoint)")
+        if e.shard_stale or e.ema_stale:
+            raise RuntimeError(f"{what}: the optimizer state is partitioned after a sharded (ZeRO-2) step; call engine.consolidate() "
+                               "on every rank before saving")
+        return e
+
+    def _ema_next_decay(self, e) -> float:
+        """Attach + seed on first use (ModelEmaV3.__init__ deep-copies the model: the d = 0 update), then the decay of this update."""
+        if e.ema is None or not e.ema_live:
+            e.ema_attach()
+            e.ema_update(0.0)
+        d = self.ema_decay_at(self.ema_updates)
+        self.ema_updates += 1
+        return d
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block every forward of `engine.module` runs on the averaged weights (the bf16 compute copy is rewritten from the
+        EMA arena); on exit the live weights are back.  This is `ft_evaluate(ema_stats.model_ema, ...)` of the reference
+        (log_eval_dump_utils.py:720-793) without a second model.  `step()` inside the block raises: it would rewrite the bf16 copy
+        from the live weights and the rest of the block would silently evaluate those."""
+        e = self._ema_engine("ema_weights")
+        if self.module._dirty:          # (an external write of the master weights is still owed to the bf16 copy: it must not land inside the block)
+            e.sync_params()
+            self.module._dirty = False
+        e.ema_to_params()
+        try:
+            yield self.module
+        finally:
+            self.module._engine.sync_params()       # (the model may have re-created its engine for a larger batch inside the block)
+
+    def ema_state_dict(self):
+        """The averaged weights in the module's reference shapes (what `get_state_dict(model_ema, unwrap_model)` returns there)."""
+        e = self._ema_engine("ema_state_dict")
+        return e.ema_state_dict({k: tuple(p.shape) for k, p in self.module._flat.items()})
+
+    def save_ema_checkpoint(self, output_dir: str, best: bool = False):
+        """`EMAStats.save_ema_ckp` (stats_configs.py:138-146): model_ema.pt - and model_ema_best.pt when `best` - as a plain state dict."""
+        from . import checkpoint as CK
+        self._ema_engine("save_ema_checkpoint")
+        return CK.save_ema_state_dict(self.ema_state_dict(), output_dir, best=best)
+
+    def load_ema_checkpoint(self, output_dir: str):
+        """`EMAStats.load_ema_ckp` (stats_configs.py:125-129): <output_dir>/model_ema.pt into the EMA arena."""
+        from . import checkpoint as CK
+        e = self.module._engine
+        if e is None:
+            e = self.module._ensure_engine(1, 8)
+        path = os.path.join(output_dir, CK.EMA_NAME)
+        e.load_ema_state_dict(CK.read_state_dict(path))
+        return path
+
     def step(self):
         """One `engine.step()` of the reference's loop.  With `gradient_accumulation_steps = k > 1` (DeepSpeed branch) the call is made
         after every micro-batch like there, and like the DS engine only every k-th call updates the weights: the others add the
         micro-batch's (exchanged) gradient to an fp32 sum and return None; at the boundary the sum goes back into the gradient
-        array and AdamW runs with 1 / (world * k) - the mean over the k * world micro-batches - clip and LR schedule once per update."""
+        array and AdamW runs with 1 / (world * k) - the mean over the k * world micro-batches - clip and LR schedule once per update.
+        With `optim.use_ema` every call averages, as the reference calls `update_ema` after every batch: inside the AdamW launch at an
+        update (also when the skip rule drops it), by the stand-alone lerp on the other micro-steps."""
         e = self.module._engine
+        if e is not None and e._params_are_ema:
+            raise RuntimeError("step() inside ema_weights(): the bf16 weights are the averaged ones (the gradients were taken on them, and "
+                               "the update would put the live weights back for the rest of the block); leave the block before training")
         if self._pending:
             for w in self._pending:
                 if w is not None:
@@ -341,6 +424,11 @@ class GgetEngine:
             torch.cuda.current_stream().wait_stream(self._comm_stream)
         o = self.optim
         k = getattr(o, "gradient_accumulation_steps", 1)
+        ema_decay = None
+        if getattr(o, "use_ema", False):
+            if self.sharded:
+                self._ensure_shard(e)       # (the seed and the stand-alone lerp run over this rank's share)
+            ema_decay = self._ema_next_decay(e)
         if k > 1:
             g = e.grad_bf16
             if self._grad_acc is None or self._grad_acc.shape != g.shape:
@@ -349,12 +437,16 @@ class GgetEngine:
             self._grad_acc += g
             self.micro_steps += 1
             if self.micro_steps % k != 0:
+                if ema_decay is not None:
+                    e.ema_update(ema_decay)
                 return None
             g.copy_(self._grad_acc)
             self._grad_acc.zero_()
         lr = o.lr_at(self.global_steps)
         if self.skip_nonfinite and getattr(e, "_skip_nonfinite", None) is not True:
             self.set_skip_nonfinite(True)       # (the model re-created its engine: the option lives on the engine instance)
+        if ema_decay is not None:
+            e.set_ema_decay(ema_decay)
         if self.sharded:
             self._ensure_shard(e)
             gn = self._sharded_update(e, lr, o, 1.0 / (self.world * k))
@@ -370,7 +462,7 @@ class GgetEngine:
     # -- checkpoint = reference DDP layout (misc_utils.py:105-121): model.pt / optimizer.pt keyed by state-dict names
     def save_checkpoint(self, save_dir: str, tag: Optional[str] = None):
         e = self.module._engine
-        if e is not None and e.shard_stale:     # (no collective here: the pipeline saves on rank 0 only; it consolidates on every rank first)
+        if e is not None and (e.shard_stale or e.ema_stale):     # (no collective here: the pipeline saves on rank 0 only; it consolidates on every rank first)
             raise RuntimeError("save_checkpoint: the optimizer state is partitioned after a sharded (ZeRO-2) step; call engine.consolidate() "
                                "on every rank before saving")
         if e is not None:
@@ -380,7 +472,10 @@ class GgetEngine:
         # the MODULE's state dict: reference shapes (emb_mask_token is [1,1,embed_dim] there, flat in the engine arena)
         torch.save({k: v.detach().cpu().clone() for k, v in self.module.state_dict().items()}, os.path.join(d, "model.pt"))
         torch.save({"m": {k: e.view(k, "m").cpu() for k in e.params}, "v": {k: e.view(k, "v").cpu() for k in e.params},
-                    "step": e.step_count, "global_steps": self.global_steps}, os.path.join(d, "optimizer.pt"))
+                    "step": e.step_count, "global_steps": self.global_steps, "ema_updates": self.ema_updates},
+                   os.path.join(d, "optimizer.pt"))
+        if e.ema is not None and e.ema_live:        # the average travels with the checkpoint: a resumed run continues it (pipeline.py:202)
+            self.save_ema_checkpoint(d)
         self.module.config.save_pretrained(d)
 
     def load_checkpoint(self, load_dir: str, tag: Optional[str] = None):
@@ -397,7 +492,12 @@ class GgetEngine:
                 e.view(k, "v").copy_(st["v"][k].to(e.device))
             e.step_count = int(st["step"])
             self.global_steps = int(st["global_steps"])
+            self.ema_updates = int(st.get("ema_updates", 0))
             e.shard_stale = False       # (every arena was written in full)
+        from . import checkpoint as CK
+        # (a run that does not average leaves a model_ema.pt it finds alone: no arena, nothing carried into its next save)
+        if getattr(self.optim, "use_ema", False) and os.path.exists(os.path.join(d, CK.EMA_NAME)):
+            self.load_ema_checkpoint(d)
         return d, {}
 
 

@@ -312,6 +312,36 @@ int gget_adamw_step(gget_handle_t h, float lr, float beta1, float beta2, float e
                     float max_grad_norm, float grad_scale, int step, float* gnorm_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Weight EMA (`training.optimizer.use_ema` / `ema_decay`; the reference's fine-tune launch scripts switch it on, e.g.
+ * examples/graph_lvl/pcqm4m_v2_supervised.sh:65).  replaces: timm's ModelEmaV3 as the reference patches and drives it -
+ * src/utils/patch_utils.py:11-42 (apply_update_: every bf16 DeepSpeed weight cast to fp32, torch._foreach_lerp_ over the module's tensors)
+ * and src/conf/stats_configs.py:102-146 (EMAStats: init_ema deep-copies the module, update_ema after every batch, save / load of
+ * model_ema.pt).  Here the average is a SIXTH arena, fp32 [n_params] with the offsets of the other five, and lives inside the AdamW launch.
+ * THE formula, fused or stand-alone (one device function):  ema' = w + d * (ema - w)  in fp32, evaluated as fmaf(d, ema - w, w) with d the
+ * fp32 decay exactly as it crossed this ABI (timm's ema.lerp_(w, 1 - d) written without the 1 - d).  d = 0 gives ema' == w bit for bit -
+ * how the arena is seeded - and no 1 - d is formed.  w = the fp32 MASTER weights: the one deliberate difference to the reference's
+ * DeepSpeed branch, which averages the bf16 module weights cast to fp32 because it cannot reach the master copy (patch_utils.py:8; its DDP
+ * branch averages fp32 parameters as this does).  Gaps and lm_head pad rows stay zero (zero in, zero out).
+ * ------------------------------------------------------------------------------------------ */
+/* replaces: EMAStats.init_ema -> ModelEmaV3.__init__ (stats_configs.py:109-116; the deep copy itself is the d = 0 update below).  The
+ * arena: n_params floats, ZERO-FILLED by the caller like the others; NULL detaches.  Clears its lm_head pad rows like gget_create
+ * (synchronously) and forgets a pending decay. */
+int gget_ema_attach(gget_handle_t h, float* ema_dev);
+/* replaces: the `decay` ModelEmaV3.update hands to apply_update_ (timm ModelEmaV3.get_decay; patch_utils.py:11-42): the decay the NEXT
+ * gget_adamw_step / gget_adamw_step_sharded applies inside its launch, consumed by it - the lerp runs against the NEW weights, from the
+ * registers (28 -> 36 B per parameter), and a step that GGET_OPT_SKIP_NONFINITE_STEP drops still averages, against the unchanged weights,
+ * as the reference calls update_ema whether or not the optimizer stepped (src/training/finetune_mode.py:405-413).  A negative value (the
+ * state of a new handle) = that step leaves the EMA alone.  The per-step rule (which decay at which step) lives on the host. */
+int gget_set_ema_decay(gget_handle_t h, float decay);
+/* replaces: EMAStats.update_ema -> ModelEmaV3.update (stats_configs.py:131-136) where no AdamW launch runs: the stand-alone lerp over the
+ * whole arena, or over this rank's share (body slices + tails) when a shard plan is active.  decay in [0, 1]; 0 copies the master weights. */
+int gget_ema_update(gget_handle_t h, float decay, void* stream);
+/* replaces: evaluating `ema_stats.model_ema.module` instead of the model (src/utils/log_eval_dump_utils.py:720-793): the bf16 compute copy
+ * is rewritten from the EMA arena (gget_sync_params with another source; the fragment-major o-weight copies are dropped like there).
+ * gget_sync_params restores the live weights. */
+int gget_ema_to_params(gget_handle_t h, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sharded optimizer step (ZeRO stage 2).  replaces: DeepSpeed's `"zero_optimization": {"stage": 2}` of the reference's pre-training
  * (examples/ds_config2_pt.json:29-32, engine built at src/training/pretrain_mode.py:281-287): gradients are reduce-scattered, every rank
  * runs clip + AdamW over its 1/world of the fp32 state only, and the bf16 compute copy is all-gathered.  The fp32 arenas keep their full
@@ -333,6 +363,7 @@ int gget_adamw_step(gget_handle_t h, float lr, float beta1, float beta2, float e
 #define GGET_SHARD_ADAM_M 2
 #define GGET_SHARD_ADAM_V 3
 #define GGET_SHARD_SLOTS 4  /* the norm's partial vector (slots_dev) */
+#define GGET_SHARD_EMA 5    /* the weight-EMA arena (gget_ema_attach): every rank averages its share only */
 /* replaces: DeepSpeed stage-2 partitioning (deepspeed/runtime/zero/stage_1_and_2.py, driven by ds_config2_pt.json:29-32).  The plan of
  * one bucket for `world` ranks, from the configuration alone (no device): out = {offset, count, slice, tail_offset, tail_count}. */
 int gget_shard_plan(const gget_config_t* cfg, int world, int bucket, uint64_t out[5]);
