@@ -46,6 +46,10 @@ SIGNATURES = {
     "gget_bucket_count": (i32, [vp]),
     "gget_bucket_range": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64)]),
     "gget_sync_params": (i32, [vp, vp]),
+    "gget_grad_acc_attach": (i32, [vp, vp]),
+    "gget_grad_accumulate": (i32, [vp, vp]),
+    "gget_grad_acc_count": (i32, [vp, C.POINTER(i32)]),
+    "gget_grad_acc_set_count": (i32, [vp, i32]),
     "gget_ema_attach": (i32, [vp, vp]),
     "gget_set_ema_decay": (i32, [vp, f32]),
     "gget_ema_update": (i32, [vp, f32, vp]),

@@ -185,6 +185,43 @@ def save_ema_state_dict(state: Dict[str, torch.Tensor], output_dir: str, best: b
     return path
 
 
+def optimizer_state(m: Dict[str, torch.Tensor], v: Dict[str, torch.Tensor], step: int, global_steps: int, ema_updates: int = 0,
+                    micro_steps: int = 0, grad_acc: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, object]:
+    """The dictionary `GgetEngine.save_checkpoint` writes as optimizer.pt: Adam's moments by state-dict name, the step counts, and - for
+    gradient accumulation (`optimizer.gradient_accumulation_steps`, reference conf_utils.py:59-66: DeepSpeed keeps both inside its engine
+    checkpoint) - `micro_steps`, plus `grad_acc`, the partial fp32 gradient sum by state-dict name, ONLY when the checkpoint is taken
+    inside a window.  The other keys are those of earlier files."""
+    st: Dict[str, object] = {"m": m, "v": v, "step": int(step), "global_steps": int(global_steps), "ema_updates": int(ema_updates),
+                             "micro_steps": int(micro_steps)}
+    if grad_acc is not None:
+        st["grad_acc"] = {k: t.detach().float().cpu().contiguous() for k, t in grad_acc.items()}
+    return st
+
+
+def read_accumulation(st: Dict[str, object], k: int, names=None) -> Tuple[int, Optional[Dict[str, torch.Tensor]], int]:
+    """(micro_steps, partial sum or None, micro-steps of the open window) out of a loaded optimizer.pt for a run that accumulates over `k`
+    micro-batches.  A file written before the two keys existed carries no window: (0, None, 0), a run that starts its next window with
+    its next micro-batch, as such a file always loaded.  A partial sum whose window does not fit `k` (saved under another
+    gradient_accumulation_steps) or that misses a parameter of `names` is refused rather than continued wrongly."""
+    k = max(1, int(k))
+    acc = st.get("grad_acc")
+    if "micro_steps" not in st:
+        if acc is not None:
+            raise ValueError("optimizer.pt holds a partial gradient sum (grad_acc) but no micro_steps")
+        return 0, None, 0
+    micro = int(st["micro_steps"])
+    if acc is None:
+        return micro, None, 0
+    n = micro % k
+    if n == 0:
+        raise ValueError(f"optimizer.pt was saved inside an accumulation window ({micro} micro-steps) that gradient_accumulation_steps = {k} "
+                         "does not leave open: resume with the value the run was saved under")
+    missing = [x for x in (names or []) if x not in acc]
+    if missing:
+        raise KeyError(f"optimizer.pt: the partial gradient sum misses {missing[:4]}")
+    return micro, {x: t.float() for x, t in acc.items()}, n
+
+
 def save_model(model, output_dir: str, ddp_prefix: bool = False):
     """`model.pt` in the reference's DDP layout (misc_utils.py:105-121) + config.json; readable by the reference."""
     os.makedirs(output_dir, exist_ok=True)

@@ -401,6 +401,13 @@ struct gget_engine {
   float* ema = nullptr;           // weight-EMA arena (gget_ema_attach; fp32 [n_params], the offsets of the other arenas), or none
   float ema_decay_next = -1.f;    // decay the NEXT gget_adamw_step[_sharded] applies (gget_set_ema_decay); < 0 = that step leaves the EMA alone
   bf16_t* G;
+  // gradient accumulation (gget_grad_acc_attach): the fp32 sum of a window's micro-batch gradients, [n_params] with the offsets of the other
+  // arenas, or none; grad_acc_count = micro-steps summed so far in the open window (0 = closed: the next gget_grad_accumulate overwrites)
+  float* grad_acc = nullptr;
+  int grad_acc_count = 0;
+  // what the norm passes and AdamW read: the accumulator while a window is open, else the bf16 gradient array
+  bool grad_from_acc() const { return grad_acc != nullptr && grad_acc_count > 0; }
+  const void* grad_src() const { return grad_from_acc() ? (const void*)grad_acc : (const void*)G; }
   unsigned char* W;
   const float* cos_tab;
   const float* sin_tab;
@@ -798,6 +805,35 @@ extern "C" int gget_ema_attach(gget_handle_t h, float* ema_dev) {
   h->ema_decay_next = -1.f;
   if (ema_dev && h->plan.lm_pad_count)    // as gget_create: the pad rows read as zeros whatever the caller's arena held
     GGET_HIP_CHECK(hipMemset(ema_dev + h->plan.lm_pad_off, 0, h->plan.lm_pad_count * 4));
+  return 0;
+}
+
+extern "C" int gget_grad_acc_attach(gget_handle_t h, float* acc_dev) {
+  GGET_REQUIRE(h != nullptr, "grad_acc_attach: null handle");
+  h->grad_acc = acc_dev;
+  h->grad_acc_count = 0;      // (no window is open: the first gget_grad_accumulate overwrites whatever the arena holds)
+  return 0;
+}
+
+extern "C" int gget_grad_accumulate(gget_handle_t h, void* stream) {
+  GGET_REQUIRE(h != nullptr, "grad_accumulate: null handle");
+  GGET_REQUIRE(h->grad_acc, "grad_accumulate: no accumulator arena (gget_grad_acc_attach)");
+  if (int e = k_grad_accumulate(h->G, h->grad_acc, h->plan.n_params, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
+  ++h->grad_acc_count;
+  return 0;
+}
+
+extern "C" int gget_grad_acc_count(gget_handle_t h, int32_t* out) {
+  GGET_REQUIRE(h != nullptr && out != nullptr, "grad_acc_count: null argument");
+  *out = h->grad_acc_count;
+  return 0;
+}
+
+extern "C" int gget_grad_acc_set_count(gget_handle_t h, int32_t n) {
+  GGET_REQUIRE(h != nullptr, "grad_acc_set_count: null handle");
+  GGET_REQUIRE(n >= 0, "grad_acc_set_count: count %d < 0", (int)n);
+  GGET_REQUIRE(n == 0 || h->grad_acc, "grad_acc_set_count: no accumulator arena (gget_grad_acc_attach)");
+  h->grad_acc_count = n;
   return 0;
 }
 
@@ -2204,17 +2240,23 @@ extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float bet
   h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies)
   float* sq = h->wsp<float>(h->ws.sqnorm);
   const bool need_norm = max_grad_norm > 0.f || gnorm_dev != nullptr || h->opt_skip_nonfinite;
+  // an open accumulation window (gget_grad_accumulate): norm, clip, skip rule and update read the fp32 sum, and this call closes the window
+  // whether or not the skip rule drops the update (GradScaler drops the whole update, not one micro-batch of it)
+  const bool from_acc = h->grad_from_acc();
+  const void* grad = h->grad_src();
+  h->grad_acc_count = 0;
   if (need_norm) {
     // the shortcut holds only while the gradient array is exactly what the last backward wrote: the caller promised that
-    // (GGET_OPT_NORM_FROM_BACKWARD), grad_scale != 1 means an exchange happened anyway, and every layer must have left its partials
-    if (h->opt_norm_from_backward && grad_scale == 1.0f && h->sq_layers == h->cfg.num_layers && h->n_sq_chunks >= 0) {
+    // (GGET_OPT_NORM_FROM_BACKWARD), grad_scale != 1 means an exchange happened anyway, and every layer must have left its partials;
+    // the partials of the last backward say nothing about a sum of several (from_acc: the full pass over the accumulator)
+    if (h->opt_norm_from_backward && !from_acc && grad_scale == 1.0f && h->sq_layers == h->cfg.num_layers && h->n_sq_chunks >= 0) {
       if (int e = k_grad_sqnorm_chunks(h->G, h->wsp<GgetSqChunk>(h->ws.sq_chunks), h->n_sq_chunks, h->wsp<float>(h->ws.sq_tiles),
                                        h->cfg.num_layers * kSqTilesPerLayer, sq, st))
         return e;
-    } else if (int e = k_grad_sqnorm(h->G, h->plan.n_params, sq, st)) return e;
+    } else if (int e = k_grad_sqnorm(grad, h->plan.n_params, sq, st, from_acc)) return e;
   }
-  return k_adamw(h->master, h->am, h->av, h->G, h->P, h->plan.n_params, lr, beta1, beta2, eps, weight_decay, step,
-                 max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay);
+  return k_adamw(h->master, h->am, h->av, grad, h->P, h->plan.n_params, lr, beta1, beta2, eps, weight_decay, step,
+                 max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay, from_acc);
 }
 
 // ================================================================================================
@@ -2301,7 +2343,9 @@ extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* sl
 
 extern "C" int gget_shard_sqnorm_partials(gget_handle_t h, float* slots_dev, void* stream) {
   GGET_REQUIRE(h && h->shard_world > 0 && slots_dev, "shard_sqnorm_partials: call gget_shard_init first (and pass the slot vector)");
-  return k_grad_sqnorm_partials(h->G, h->shard_chunks(), h->shard_chunk_slot(), h->shard_nchunks, slots_dev, (hipStream_t)stream);
+  // (an open accumulation window: the chunks of the fp32 sum; the window stays open for gget_adamw_step_sharded, which closes it)
+  return k_grad_sqnorm_partials(h->grad_src(), h->shard_chunks(), h->shard_chunk_slot(), h->shard_nchunks, slots_dev, (hipStream_t)stream,
+                                h->grad_from_acc());
 }
 
 extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -2320,8 +2364,11 @@ extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, f
     GGET_REQUIRE(slots_dev, "adamw_step_sharded: the norm needs the gathered partial vector");
     if (int e = k_grad_sqnorm_slots(slots_dev, h->shard_slot_of(), h->shard_nglobal, sq, st)) return e;
   }
-  return k_adamw_items(h->master, h->am, h->av, h->G, h->P, h->shard_items(), h->shard_nitems, lr, beta1, beta2, eps, weight_decay, step,
-                       max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay);
+  const bool from_acc = h->grad_from_acc();       // (as gget_adamw_step: this rank's share of the fp32 sum, and the window closes)
+  const void* grad = h->grad_src();
+  h->grad_acc_count = 0;
+  return k_adamw_items(h->master, h->am, h->av, grad, h->P, h->shard_items(), h->shard_nitems, lr, beta1, beta2, eps, weight_decay, step,
+                       max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay, from_acc);
 }
 
 extern "C" int gget_head_counts(gget_handle_t h, int32_t counts[2], void* stream) {

@@ -1625,27 +1625,50 @@ __global__ void __launch_bounds__(kBlock) score_bwd_kernel(const float* __restri
 // differences between ranks and the replicas would drift apart; a last-block-done counter costs 1024 contended returning
 // atomics, ~35 us).  ws: [0] result, [16 .. 16 + blocks) partials.
 constexpr int kSqnormBlocks = 1024;
-__global__ void __launch_bounds__(kBlock) grad_sqnorm_kernel(const bf16_t* __restrict__ g, size_t n, float* __restrict__ ws) {
+// The gradient SOURCE of the norm passes and of AdamW: the bf16 gradient array, or the fp32 accumulator of a gradient-accumulation window
+// (grad_accumulate_kernel below).  Only these loads differ between the two instantiations of a kernel - read order, summation order, chunk
+// grid and the per-element device functions are the same text; the bf16 forms are what they were before the accumulator existed.
+// Grad8: eight consecutive elements (vector index i) in flight as 16-byte loads, unpacked to fp32 later.
+template <typename GT> struct Grad8;
+template <> struct Grad8<bf16_t> {
+  uint4 q;
+  __device__ __forceinline__ void load(const bf16_t* __restrict__ g, size_t i) { q = ldg16(g + i * 8); }
+  __device__ __forceinline__ void unpack(float (&v)[8]) const { unpack8(q, v); }
+};
+template <> struct Grad8<float> {
+  float4 a, b;
+  __device__ __forceinline__ void load(const float* __restrict__ g, size_t i) {
+    a = reinterpret_cast<const float4*>(g)[i * 2];
+    b = reinterpret_cast<const float4*>(g)[i * 2 + 1];
+  }
+  __device__ __forceinline__ void unpack(float (&v)[8]) const {
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+  }
+};
+template <typename GT>
+__global__ void __launch_bounds__(kBlock) grad_sqnorm_kernel(const GT* __restrict__ g, size_t n, float* __restrict__ ws) {
   __shared__ float part[kBlock / 64];
   float s = 0.f;
   const size_t nv = n >> 3;
   const size_t stride = (size_t)gridDim.x * kBlock;
   size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
   for (; i + 3 * stride < nv; i += 4 * stride) {   // four loads in flight per thread
-    uint4 q[4];
+    Grad8<GT> q[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) q[u] = ldg16(g + (i + u * stride) * 8);
+    for (int u = 0; u < 4; ++u) q[u].load(g, i + u * stride);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       float v[8];
-      unpack8(q[u], v);
+      q[u].unpack(v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) s += v[e] * v[e];
     }
   }
   for (; i < nv; i += stride) {
+    Grad8<GT> q;
+    q.load(g, i);
     float v[8];
-    unpack8(ldg16(g + i * 8), v);
+    q.unpack(v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += v[e] * v[e];
   }
@@ -1672,15 +1695,18 @@ __global__ void __launch_bounds__(kBlock) grad_sqnorm_final_kernel(float* __rest
 }
 
 // one block per chunk (see k_grad_sqnorm_chunks): out[slot ? slot[chunk] : chunk] = sum of squares of the chunk
-__global__ void __launch_bounds__(kBlock) grad_sqnorm_chunks_kernel(const bf16_t* __restrict__ g, const GgetSqChunk* __restrict__ chunks,
+template <typename GT>
+__global__ void __launch_bounds__(kBlock) grad_sqnorm_chunks_kernel(const GT* __restrict__ g, const GgetSqChunk* __restrict__ chunks,
                                                                     float* __restrict__ out, const int32_t* __restrict__ slot) {
   __shared__ float part[kBlock / 64];
   const GgetSqChunk c = chunks[blockIdx.x];
-  const bf16_t* p = g + c.off;
+  const GT* p = g + c.off;
   float s = 0.f;
   for (size_t i = threadIdx.x; i < (c.cnt >> 3); i += kBlock) {
+    Grad8<GT> q;
+    q.load(p, i);
     float v[8];
-    unpack8(ldg16(p + i * 8), v);
+    q.unpack(v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += v[e] * v[e];
   }
@@ -1772,16 +1798,27 @@ __device__ __forceinline__ void ema_update4(const float* __restrict__ master, fl
 // the per-element AdamW update of four consecutive elements (vector index i): ONE definition for both kernels, so that a sharded update
 // is bit-identical to the replicated one given the same coefficient.  EMA: the lerp of the weight EMA against the NEW weights, taken
 // from the registers (the master arena is not read a second time); without it the function is what it was before the EMA existed.
-template <bool EMA>
+// four consecutive gradient elements (vector index i) as fp32, non-temporal: 8 bytes of the bf16 array, or 16 of the fp32 accumulator
+__device__ __forceinline__ void load_grad4(const bf16_t* __restrict__ grad, size_t i, float (&g)[4]) {
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  const u2v gr = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(grad + i * 4));
+  g[0] = __uint_as_float(gr.x << 16), g[1] = __uint_as_float(gr.x & 0xffff0000u);
+  g[2] = __uint_as_float(gr.y << 16), g[3] = __uint_as_float(gr.y & 0xffff0000u);
+}
+__device__ __forceinline__ void load_grad4(const float* __restrict__ grad, size_t i, float (&g)[4]) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v gr = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(grad) + i);
+  g[0] = gr.x, g[1] = gr.y, g[2] = gr.z, g[3] = gr.w;
+}
+template <bool EMA, typename GT>
 __device__ __forceinline__ void adamw_update4(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                              const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t i, float coef,
+                                              const GT* __restrict__ grad, bf16_t* __restrict__ param, size_t i, float coef,
                                               float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt,
                                               float* __restrict__ ema, float ema_decay) {
   typedef float f4v __attribute__((ext_vector_type(4)));
   typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const u2v gr = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(grad + i * 4));
-  float g[4] = {__uint_as_float(gr.x << 16), __uint_as_float(gr.x & 0xffff0000u), __uint_as_float(gr.y << 16),
-                __uint_as_float(gr.y & 0xffff0000u)};
+  float g[4];
+  load_grad4(grad, i, g);
   f4v w = __builtin_nontemporal_load(reinterpret_cast<f4v*>(master) + i);
   f4v mm = __builtin_nontemporal_load(reinterpret_cast<f4v*>(m_) + i);
   f4v vv = __builtin_nontemporal_load(reinterpret_cast<f4v*>(v_) + i);
@@ -1805,9 +1842,9 @@ __device__ __forceinline__ void adamw_update4(float* __restrict__ master, float*
   if (EMA) ema_lerp4(ema, i, wp, ema_decay);
 }
 
-template <int UNR>
+template <int UNR, typename GT>
 __global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                       const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
+                                                       const GT* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
                                                        float lr, float beta1, float beta2, float eps, float wd, float bc1,
                                                        float bc2_sqrt, float max_norm, float grad_scale,
                                                        const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
@@ -1826,9 +1863,9 @@ __global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ maste
 // the same launch with the weight EMA fused in: one more fp32 arena read and written (28 -> 36 B per parameter).  A step the skip rule
 // drops still averages - against the unchanged master weights (the reference calls update_ema after every batch whether or not the
 // optimizer stepped, src/training/finetune_mode.py:405-413); the decision is uniform over the launch
-template <int UNR>
+template <int UNR, typename GT>
 __global__ void __launch_bounds__(kBlock) adamw_ema_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                           const bf16_t* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
+                                                           const GT* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
                                                            float lr, float beta1, float beta2, float eps, float wd, float bc1,
                                                            float bc2_sqrt, float max_norm, float grad_scale,
                                                            const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite,
@@ -1850,8 +1887,9 @@ __global__ void __launch_bounds__(kBlock) adamw_ema_kernel(float* __restrict__ m
 // sharded step (ZeRO-2): the same update over a list of work items (element ranges of <= kAdamwItemElems elements, offsets and counts multiples
 // of 4) that cut the rank's body slices and the replicated tails - one launch, one block per item, every thread two float4 groups
 static_assert(kAdamwItemElems == kBlock * 8, "an AdamW work item is two float4 groups per thread");
+template <typename GT>
 __global__ void __launch_bounds__(kBlock) adamw_items_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                             const bf16_t* __restrict__ grad, bf16_t* __restrict__ param,
+                                                             const GT* __restrict__ grad, bf16_t* __restrict__ param,
                                                              const GgetSqChunk* __restrict__ items, float lr, float beta1, float beta2,
                                                              float eps, float wd, float bc1, float bc2_sqrt, float max_norm, float grad_scale,
                                                              const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
@@ -1862,8 +1900,9 @@ __global__ void __launch_bounds__(kBlock) adamw_items_kernel(float* __restrict__
   for (size_t i = threadIdx.x; i < nv; i += kBlock)
     adamw_update4<false>(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, nullptr, 0.f);
 }
+template <typename GT>
 __global__ void __launch_bounds__(kBlock) adamw_items_ema_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                                 const bf16_t* __restrict__ grad, bf16_t* __restrict__ param,
+                                                                 const GT* __restrict__ grad, bf16_t* __restrict__ param,
                                                                  const GgetSqChunk* __restrict__ items, float lr, float beta1, float beta2,
                                                                  float eps, float wd, float bc1, float bc2_sqrt, float max_norm,
                                                                  float grad_scale, const float* __restrict__ sqnorm,
@@ -1899,6 +1938,30 @@ __global__ void __launch_bounds__(kBlock) ema_lerp_items_kernel(const float* __r
   const GgetSqChunk it = items[blockIdx.x];
   const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
   for (size_t i = threadIdx.x; i < nv; i += kBlock) ema_update4(master, ema, v0 + i, d);
+}
+
+// gradient accumulation (reference: the DeepSpeed engine's gradient_accumulation_steps, conf_utils.py:59-66 - its bf16 optimizer sums the
+// micro-batches' gradients in fp32): acc[i] = (FIRST ? 0 : acc[i]) + float(grad[i]) over the whole flat array, eight elements per thread -
+// one 16-byte bf16 load, two 16-byte fp32 loads (none on the first micro-step of a window, which overwrites: there is no zero-fill pass)
+// and two 16-byte stores; 6 or 10 B per parameter.  The accumulator is streamed once per micro-step and next read a whole forward +
+// backward later: non-temporal.  Grid-stride, every element has one owner, no atomics; gaps and pad rows are zero in, zero out.
+template <bool FIRST>
+__global__ void __launch_bounds__(kBlock) grad_accumulate_kernel(const bf16_t* __restrict__ grad, float* __restrict__ acc, size_t n) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const size_t nv = n >> 3;
+  const size_t stride = (size_t)gridDim.x * kBlock;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < nv; i += stride) {
+    float g[8];
+    unpack8(ldg16(grad + i * 8), g);
+    f4v* a = reinterpret_cast<f4v*>(acc) + i * 2;
+    f4v lo = {g[0], g[1], g[2], g[3]}, hi = {g[4], g[5], g[6], g[7]};
+    if (!FIRST) {
+      lo += __builtin_nontemporal_load(a);
+      hi += __builtin_nontemporal_load(a + 1);
+    }
+    __builtin_nontemporal_store(lo, a);
+    __builtin_nontemporal_store(hi, a + 1);
+  }
 }
 
 __global__ void __launch_bounds__(kBlock) f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, size_t n) {
@@ -2944,9 +3007,12 @@ int k_score_bwd(const float* dlogits, const void* hidden, const int32_t* pool_ro
   return 0;
 }
 
-int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st) {
+int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st, bool grad_f32) {
   const int blocks = grid_for((long)(n / 8), kBlock, kSqnormBlocks);   // (2048 .. 8192 blocks measured slower)
-  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(blocks), dim3(kBlock), 0, st, (const bf16_t*)g, n, ws);
+  if (grad_f32)
+    hipLaunchKernelGGL(grad_sqnorm_kernel<float>, dim3(blocks), dim3(kBlock), 0, st, (const float*)g, n, ws);
+  else
+    hipLaunchKernelGGL(grad_sqnorm_kernel<bf16_t>, dim3(blocks), dim3(kBlock), 0, st, (const bf16_t*)g, n, ws);
   hipLaunchKernelGGL(grad_sqnorm_final_kernel, dim3(1), dim3(kBlock), 0, st, ws, blocks);
   GGET_LAUNCH_CHECK();
   return 0;
@@ -2954,7 +3020,7 @@ int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st) {
 
 int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st) {
   if (nchunks > 0)
-    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, ws + 16,
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<bf16_t>, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, ws + 16,
                        (const int32_t*)nullptr);
   hipLaunchKernelGGL(grad_sqnorm_final2_kernel, dim3(1), dim3(kBlock), 0, st, ws, nchunks, extra, nextra);
   GGET_LAUNCH_CHECK();
@@ -2963,19 +3029,37 @@ int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchun
 
 int k_adamw(float* master, float* m, float* v, const void* grad, void* param, size_t n, float lr, float beta1, float beta2,
             float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm, float* gnorm_out,
-            hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay) {
+            hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay, bool grad_f32) {
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
   // one pass, two float4 groups per thread (grid up to 65536 blocks): the grid-stride form with 4096 blocks ran at 5.1 TB/s of
   // state traffic, this one at 6.0 (profiles/r02_adamw_sweep.txt); loads and the fp32 state stores are non-temporal
   const dim3 grid(grid_for((long)(n / 8), kBlock, 65536));
-  if (ema)
-    hipLaunchKernelGGL(adamw_ema_kernel<2>, grid, dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1,
+  // (grad_f32: the same launch reading the fp32 accumulator of a gradient-accumulation window - 4 gradient bytes instead of 2)
+  if (ema && grad_f32)
+    hipLaunchKernelGGL((adamw_ema_kernel<2, float>), grid, dim3(kBlock), 0, st, master, m, v, (const float*)grad, (bf16_t*)param, n, lr, beta1,
                        beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0, ema, ema_decay);
+  else if (ema)
+    hipLaunchKernelGGL((adamw_ema_kernel<2, bf16_t>), grid, dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1,
+                       beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0, ema, ema_decay);
+  else if (grad_f32)
+    hipLaunchKernelGGL((adamw_kernel<2, float>), grid, dim3(kBlock), 0, st, master, m, v,
+                       (const float*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
+                       grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
   else
-    hipLaunchKernelGGL(adamw_kernel<2>, grid, dim3(kBlock), 0, st, master, m, v,
+    hipLaunchKernelGGL((adamw_kernel<2, bf16_t>), grid, dim3(kBlock), 0, st, master, m, v,
                        (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
                        grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_grad_accumulate(const void* grad, float* acc, size_t n, bool first, hipStream_t st) {
+  const dim3 grid(grid_for((long)(n / 8), kBlock, 65536));     // (one 8-element group per thread up to 134 M parameters, as k_adamw)
+  if (first)
+    hipLaunchKernelGGL(grad_accumulate_kernel<true>, grid, dim3(kBlock), 0, st, (const bf16_t*)grad, acc, n);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<false>, grid, dim3(kBlock), 0, st, (const bf16_t*)grad, acc, n);
   GGET_LAUNCH_CHECK();
   return 0;
 }
@@ -2993,9 +3077,13 @@ int k_ema_lerp_items(const float* master, float* ema, const GgetSqChunk* items_d
   return 0;
 }
 
-int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st) {
+int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st,
+                           bool grad_f32) {
   if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(grad_sqnorm_chunks_kernel, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, out, slot_dev);
+  if (grad_f32)
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<float>, dim3(nchunks), dim3(kBlock), 0, st, (const float*)g, chunks_dev, out, slot_dev);
+  else
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<bf16_t>, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, out, slot_dev);
   GGET_LAUNCH_CHECK();
   return 0;
 }
@@ -3008,16 +3096,23 @@ int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, f
 
 int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
                   float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
-                  float* gnorm_out, hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay) {
+                  float* gnorm_out, hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay, bool grad_f32) {
   if (nitems <= 0) return 0;
   const float bc1 = 1.0f - powf(beta1, (float)step);      // (the constants exactly as k_adamw derives them)
   const float bc2 = 1.0f - powf(beta2, (float)step);
-  if (ema)
-    hipLaunchKernelGGL(adamw_items_ema_kernel, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param,
+  if (ema && grad_f32)
+    hipLaunchKernelGGL(adamw_items_ema_kernel<float>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const float*)grad, (bf16_t*)param,
                        items_dev, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out,
                        skip_nonfinite ? 1 : 0, ema, ema_decay);
+  else if (ema)
+    hipLaunchKernelGGL(adamw_items_ema_kernel<bf16_t>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param,
+                       items_dev, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out,
+                       skip_nonfinite ? 1 : 0, ema, ema_decay);
+  else if (grad_f32)
+    hipLaunchKernelGGL(adamw_items_kernel<float>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const float*)grad, (bf16_t*)param, items_dev,
+                       lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
   else
-    hipLaunchKernelGGL(adamw_items_kernel, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, items_dev,
+    hipLaunchKernelGGL(adamw_items_kernel<bf16_t>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, items_dev,
                        lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
   GGET_LAUNCH_CHECK();
   return 0;

@@ -110,6 +110,8 @@ class Engine:
         self.ema_live = False
         self.ema_stale = False
         self._params_are_ema = False
+        # gradient accumulation (grad_acc_attach): the seventh arena, allocated on demand - the fp32 sum of a window's micro-batch gradients
+        self.grad_acc = None
         self._params_ready = None   # event behind the all-gather of the bf16 copy: the next reader of the weights waits for it
         self._keep = None  # keeps the last batch tensors alive until backward has consumed them
 
@@ -125,7 +127,7 @@ class Engine:
     def view(self, name: str, which: str = "master") -> torch.Tensor:
         p = self.params[name]
         arena = {"master": self.master, "bf16": self.param_bf16, "grad": self.grad_bf16, "m": self.adam_m,
-                 "v": self.adam_v, "ema": self.ema}[which]
+                 "v": self.adam_v, "ema": self.ema, "grad_acc": self.grad_acc}[which]
         if arena is None:
             raise L.GgetError(f"view({name!r}, {which!r}): this engine has no such arena")
         return arena[p["offset"]: p["offset"] + p["numel"]].view(p["shape"])
@@ -154,6 +156,37 @@ class Engine:
                               "share they are stale; call GgetEngine.consolidate() on every rank first")
         L.check(self.lib.gget_sync_params(self.h, _stream()))
         self._params_are_ema = False
+
+    # ------------------------------------------------------------------ gradient accumulation (optimizer.gradient_accumulation_steps)
+    def grad_acc_attach(self):
+        """Allocate the accumulator arena (fp32 [n_params]) and hand it to the handle (gget_grad_acc_attach); a no-op when it exists.
+        No window is open: the first grad_accumulate() overwrites it."""
+        if self.grad_acc is None:
+            self.grad_acc = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+            L.check(self.lib.gget_grad_acc_attach(self.h, _ptr(self.grad_acc)))
+        return self.grad_acc
+
+    def grad_acc_detach(self):
+        L.check(self.lib.gget_grad_acc_attach(self.h, None))
+        self.grad_acc = None
+
+    def grad_accumulate(self):
+        """grad_acc (+)= grad_bf16 in fp32, one launch (gget_grad_accumulate); the first call of a window overwrites.  Until the next
+        adamw_step / adamw_step_sharded, which closes the window, norm, clip and update read the fp32 sum."""
+        self.grad_acc_attach()
+        L.check(self.lib.gget_grad_accumulate(self.h, _stream()))
+
+    def grad_acc_count(self) -> int:
+        """Micro-steps summed in the open window (gget_grad_acc_count); 0 = none open."""
+        n = C.c_int32(0)
+        L.check(self.lib.gget_grad_acc_count(self.h, C.byref(n)))
+        return int(n.value)
+
+    def grad_acc_set_count(self, n: int):
+        """Re-open a window at `n` micro-steps over what the arena holds (gget_grad_acc_set_count: the resume path); 0 closes it."""
+        if int(n) > 0:
+            self.grad_acc_attach()
+        L.check(self.lib.gget_grad_acc_set_count(self.h, int(n)))
 
     # ------------------------------------------------------------------ weight EMA (optimizer.use_ema)
     def ema_attach(self):

@@ -314,6 +314,9 @@ class _GgetModel(nn.Module):
             if e.ema is not None:       # the weight EMA moves with the optimizer state
                 new.ema_attach().copy_(e.ema)
                 new.ema_live, new.ema_stale = e.ema_live, e.ema_stale
+            if e.grad_acc is not None and e.grad_acc_count() > 0:       # an open accumulation window moves too: its partial sum and count
+                new.grad_acc_attach().copy_(e.grad_acc)
+                new.grad_acc_set_count(e.grad_acc_count())
             new.comm_adopt(e)       # an RCCL communicator bound through the C ABI moves to the new handle
         for name, p in self._flat.items():
             p.data = new.view(name, "master").view(p.shape)      # (emb_mask_token is [1,1,e] in the reference, flat in the engine)

@@ -132,7 +132,8 @@ class GgetEngine:
         self.exchange = True
         self.reserved_cus = 0
         # gradient accumulation (DeepSpeed branch, conf_utils.py:59-66 -> the DS engine steps at the boundary only): the micro-batches'
-        # gradients are summed in an fp32 copy of the flat gradient array; step() k - 1 times out of k only does that
+        # gradients are summed in the engine's fp32 accumulator arena (Engine.grad_accumulate, one HIP launch); step() k - 1 times out of
+        # k only does that.  micro_steps counts every such call; _grad_acc is the arena view (None before the first k > 1 step)
         self.micro_steps = 0
         self._grad_acc = None
         # GradScaler's rule of the reference's DDP branch (training_utils.py:46-86): an optimizer step whose gradient norm is inf / NaN is
@@ -408,8 +409,9 @@ class GgetEngine:
     def step(self):
         """One `engine.step()` of the reference's loop.  With `gradient_accumulation_steps = k > 1` (DeepSpeed branch) the call is made
         after every micro-batch like there, and like the DS engine only every k-th call updates the weights: the others add the
-        micro-batch's (exchanged) gradient to an fp32 sum and return None; at the boundary the sum goes back into the gradient
-        array and AdamW runs with 1 / (world * k) - the mean over the k * world micro-batches - clip and LR schedule once per update.
+        micro-batch's (exchanged) gradient to the engine's fp32 accumulator (one launch, the first of a window overwrites) and return
+        None; at the boundary the norm, the clip and AdamW read that fp32 sum - it is never rounded back to bf16 - with 1 / (world * k),
+        the mean over the k * world micro-batches; clip and LR schedule once per update, and the update closes the window.
         With `optim.use_ema` every call averages, as the reference calls `update_ema` after every batch: inside the AdamW launch at an
         update (also when the skip rule drops it), by the stand-alone lerp on the other micro-steps."""
         e = self.module._engine
@@ -430,18 +432,13 @@ class GgetEngine:
                 self._ensure_shard(e)       # (the seed and the stand-alone lerp run over this rank's share)
             ema_decay = self._ema_next_decay(e)
         if k > 1:
-            g = e.grad_bf16
-            if self._grad_acc is None or self._grad_acc.shape != g.shape:
-                self._grad_acc = torch.zeros(g.shape, dtype=torch.float32, device=g.device)
-                self.micro_steps = 0
-            self._grad_acc += g
+            e.grad_accumulate()         # (attaches the arena on first use; a re-created engine carries an open window over)
+            self._grad_acc = e.grad_acc
             self.micro_steps += 1
             if self.micro_steps % k != 0:
                 if ema_decay is not None:
                     e.ema_update(ema_decay)
                 return None
-            g.copy_(self._grad_acc)
-            self._grad_acc.zero_()
         lr = o.lr_at(self.global_steps)
         if self.skip_nonfinite and getattr(e, "_skip_nonfinite", None) is not True:
             self.set_skip_nonfinite(True)       # (the model re-created its engine: the option lives on the engine instance)
@@ -469,10 +466,14 @@ class GgetEngine:
             e.await_params()
         d = os.path.join(save_dir, tag) if tag else save_dir
         os.makedirs(d, exist_ok=True)
+        from . import checkpoint as CK
         # the MODULE's state dict: reference shapes (emb_mask_token is [1,1,embed_dim] there, flat in the engine arena)
         torch.save({k: v.detach().cpu().clone() for k, v in self.module.state_dict().items()}, os.path.join(d, "model.pt"))
-        torch.save({"m": {k: e.view(k, "m").cpu() for k in e.params}, "v": {k: e.view(k, "v").cpu() for k in e.params},
-                    "step": e.step_count, "global_steps": self.global_steps, "ema_updates": self.ema_updates},
+        # (a checkpoint inside an accumulation window carries the partial fp32 sum: checkpoint.optimizer_state)
+        window = e.grad_acc is not None and e.grad_acc_count() > 0
+        torch.save(CK.optimizer_state({k: e.view(k, "m").cpu() for k in e.params}, {k: e.view(k, "v").cpu() for k in e.params},
+                                      e.step_count, self.global_steps, self.ema_updates, self.micro_steps,
+                                      {k: e.view(k, "grad_acc").cpu() for k in e.params} if window else None),
                    os.path.join(d, "optimizer.pt"))
         if e.ema is not None and e.ema_live:        # the average travels with the checkpoint: a resumed run continues it (pipeline.py:202)
             self.save_ema_checkpoint(d)
@@ -483,6 +484,7 @@ class GgetEngine:
         e = self.module._engine
         if e is None:
             e = self.module._ensure_engine(1, 8)
+        from . import checkpoint as CK
         e.load_state_dict(torch.load(os.path.join(d, "model.pt"), map_location="cpu"))
         opt_path = os.path.join(d, "optimizer.pt")
         if os.path.exists(opt_path):
@@ -494,7 +496,14 @@ class GgetEngine:
             self.global_steps = int(st["global_steps"])
             self.ema_updates = int(st.get("ema_updates", 0))
             e.shard_stale = False       # (every arena was written in full)
-        from . import checkpoint as CK
+            # an open accumulation window continues where it was: the partial sum back into the arena, the count back into the engine
+            self.micro_steps, acc, n = CK.read_accumulation(st, getattr(self.optim, "gradient_accumulation_steps", 1), list(e.params))
+            if acc is not None:
+                e.grad_acc_attach().zero_()
+                for k in e.params:
+                    e.view(k, "grad_acc").copy_(acc[k].to(e.device))
+                self._grad_acc = e.grad_acc
+            e.grad_acc_set_count(n)
         # (a run that does not average leaves a model_ema.pt it finds alone: no arena, nothing carried into its next save)
         if getattr(self.optim, "use_ema", False) and os.path.exists(os.path.join(d, CK.EMA_NAME)):
             self.load_ema_checkpoint(d)

@@ -312,6 +312,32 @@ int gget_adamw_step(gget_handle_t h, float lr, float beta1, float beta2, float e
                     float max_grad_norm, float grad_scale, int step, float* gnorm_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradient accumulation (`training.optimizer.gradient_accumulation_steps = k`).  replaces: the fp32 accumulation of the DeepSpeed engine
+ * the reference hands k to (src/conf/conf_utils.py:59-66; its bf16 optimizer adds every micro-batch's gradient to an fp32 buffer and steps
+ * at the boundary only).  The sum is a SEVENTH, optional arena: fp32 [n_params] with the offsets of the other six.  While a window is open
+ * (count > 0) gget_adamw_step, gget_adamw_step_sharded, gget_shard_sqnorm_partials and the rules of GGET_OPT_NORM_FROM_BACKWARD (ignored:
+ * the last backward's partials say nothing about a sum) and GGET_OPT_SKIP_NONFINITE_STEP read the fp32 sum instead of the bf16 gradient
+ * array - the same kernels with an fp32 load, so the sum of k * world bf16 gradients is never rounded back to bf16 - and the two AdamW
+ * entries close the window (count = 0), also when the skip rule drops the update.  grad_scale = 1 / (k * world) turns the sum into the mean.
+ * A handle that never attaches an accumulator allocates nothing and launches nothing new.
+ * ------------------------------------------------------------------------------------------ */
+/* replaces: the allocation of DeepSpeed's fp32 gradient buffer at deepspeed.initialize (conf_utils.py:59-66 carries k into its config).
+ * The arena: n_params floats owned by the caller (its contents do not matter: the first micro-step of a window overwrites); NULL detaches.
+ * No window is open afterwards. */
+int gget_grad_acc_attach(gget_handle_t h, float* acc_dev);
+/* replaces: the per-micro-batch accumulation of the DeepSpeed engine's backward (conf_utils.py:59-66 -> gradient_accumulation_steps):
+ * acc[i] = (count == 0 ? 0 : acc[i]) + float(grad_bf16[i]) over the whole flat gradient array - gaps and lm_head pad rows included, zero
+ * in, zero out - in one launch of 16-byte loads and stores (6 B per parameter on the first micro-step, which overwrites instead of adding:
+ * there is no zero-fill pass; 10 B afterwards); count += 1.  Call it once the micro-batch's exchange has been waited for on `stream`. */
+int gget_grad_accumulate(gget_handle_t h, void* stream);
+/* replaces: DeepSpeed's micro_steps bookkeeping inside a window (engine.is_gradient_accumulation_boundary, driven by conf_utils.py:59-66):
+ * micro-steps summed so far in the open window; 0 = no window open (or no accumulator). */
+int gget_grad_acc_count(gget_handle_t h, int32_t* out);
+/* replaces: the restore of that bookkeeping when DeepSpeed loads a checkpoint taken inside a window (conf_utils.py:59-66's engine): the
+ * resume path - after the caller has written a saved partial sum into the arena, n > 0 re-opens the window at n micro-steps; 0 closes it. */
+int gget_grad_acc_set_count(gget_handle_t h, int32_t n);
+
+/* ------------------------------------------------------------------------------------------
  * Weight EMA (`training.optimizer.use_ema` / `ema_decay`; the reference's fine-tune launch scripts switch it on, e.g.
  * examples/graph_lvl/pcqm4m_v2_supervised.sh:65).  replaces: timm's ModelEmaV3 as the reference patches and drives it -
  * src/utils/patch_utils.py:11-42 (apply_update_: every bf16 DeepSpeed weight cast to fp32, torch._foreach_lerp_ over the module's tensors)
