@@ -131,6 +131,8 @@ SIGNATURES = {
     "gget_op_geglu_fwd": (i32, [vp, vp, i32, i32, vp]),
     "gget_op_geglu_bwd": (i32, [vp, vp, vp, i32, i32, vp]),
     "gget_op_ce_fwd_bwd": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, f32, i32, vp]),
+    "gget_op_rank_metrics_workspace": (C.c_size_t, [i32, i32]),
+    "gget_op_rank_metrics": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
 }
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2

@@ -824,6 +824,17 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
     test_loss = test_loss / j
     input_dict = cls_metrics.to_dict()
     world = dist.get_world_size() if dist_ready() else 1
+    if isinstance(cls_metrics, M.MultiLabelClassificationMetrics):
+        # rank metrics from the device-resident accumulations (the gathered tensors on the collective's device with several ranks): the HIP
+        # rank kernels for CUDA tensors; the ONE host transfer of the tensor dict comes after them
+        if world > 1:
+            gdev = device if dist.get_backend() == "nccl" else torch.device("cpu")
+            input_dict = {k: all_gather_varlen(v.to(gdev)) for k, v in input_dict.items()}
+        cls_metrics.compute(input_dict)
+        res = M.evaluate_ogb(dataset_name, input_dict)
+        if res is None:
+            res = cls_metrics.results_in_dict()
+        return test_loss, cls_metrics, res, {k: v.cpu() for k, v in input_dict.items()}
     if world > 1:
         gdev = device if dist.get_backend() == "nccl" else torch.device("cpu")
         input_dict = {k: all_gather_varlen(v.to(gdev)).cpu() for k, v in input_dict.items()}

@@ -642,6 +642,29 @@ int gget_op_ce_fwd_bwd(const void* logits, int ld, const int32_t* labels, const 
                        int n_rows_cap, int V, float* loss_sum, void* dlogits, float grad_scale_base, int mean_over_rows,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rank metrics of the multi-label evaluation pass (csrc/metrics.hip; the Python surface is graph-gpt_amd/metrics.py rank_metrics).
+ * replaces: MultiLabelClassificationMetrics.compute (src/utils/metrics_utils.py:112-114: torcheval BinaryAUROC over num_labels tasks),
+ * `_eval_rocauc` (src/utils/ogb_utils.py:13-29: scikit-learn roc_auc_score column by column on the host - ogbn-proteins :71-79, ogbg-molhiv
+ * :173-184) and OGB's `_eval_ap` for ogbg-molpcba (:187-195: average_precision_score column by column).
+ * scores f32 [n, C] (row stride ld_s elements), labels f32 [n, C] (row stride ld_y): 1 = positive, 0 = negative, NaN = unlabelled (the
+ * entry is skipped, whatever its score).  Per column c, over its labelled entries, with a_i / e_i = negatives scored below / equal to the
+ * positive i and g_i = positives scored >= it:
+ *   n_pos[c], n_neg[c]  i64   positives and negatives
+ *   auc2[c]             u64   sum_i (2 a_i + e_i):            ROC-AUC = auc2 / (2 n_pos n_neg), the Mann-Whitney statistic with mid-ranks
+ *   ap_sum[c]           f64   sum_i g_i / (g_i + n_neg - a_i): AP = ap_sum / n_pos, scikit-learn's average_precision_score with its tie rule
+ *   n_bad[c]            i32   labelled entries whose label is neither 0 nor 1 or whose score is not finite (left out of every count above;
+ *                             the caller decides - the Python surface raises, as scikit-learn does on such input)
+ * The counts are exact integers (compare-and-add, no sort); the fp64 sum runs over the positives in row order with a fixed tree: all five
+ * outputs are bit-identical from run to run and independent of the launch geometry.  -0.0 == 0.0.  A column with n_pos == 0 or
+ * n_neg == 0 gets auc2 = 0 and ap_sum = 0.  n == 0 or C == 0 is a valid call that launches nothing (the outputs are not written).
+ * workspace: device memory of at least the bytes the _workspace query returns for (n, C), 16-byte aligned, contents irrelevant; a smaller
+ * one is refused with an error before anything is launched.  Five launches on `stream`, no host sync.  C <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+size_t gget_op_rank_metrics_workspace(int n, int C);
+int gget_op_rank_metrics(const float* scores, int ld_s, const float* labels, int ld_y, int n, int C, int64_t* n_pos, int64_t* n_neg,
+                         uint64_t* auc2, double* ap_sum, int32_t* n_bad, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
