@@ -50,6 +50,8 @@ SIGNATURES = {
     "gget_grad_accumulate": (i32, [vp, vp]),
     "gget_grad_acc_count": (i32, [vp, C.POINTER(i32)]),
     "gget_grad_acc_set_count": (i32, [vp, i32]),
+    "gget_set_frozen": (i32, [vp, i32]),
+    "gget_trainable_ranges": (i32, [vp, vp, vp]),
     "gget_ema_attach": (i32, [vp, vp]),
     "gget_set_ema_decay": (i32, [vp, f32]),
     "gget_ema_update": (i32, [vp, f32, vp]),

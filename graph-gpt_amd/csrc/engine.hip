@@ -513,6 +513,30 @@ struct gget_engine {
   const GgetSqChunk* shard_chunks() const { return shard_items() + shard_nitems; }
   const int32_t* shard_chunk_slot() const { return reinterpret_cast<const int32_t*>(shard_chunks() + shard_nchunks); }
   const int32_t* shard_slot_of() const { return shard_chunk_slot() + shard_nchunks; }
+  // frozen prefix (gget_set_frozen; reference freeze_llama_layers): -1 = everything trains and nothing below is used.  >= 0: embed_tokens
+  // and the layers [0, frozen) are not trained - the trainable element ranges of the flat arenas (at most two), and one device allocation
+  // owned by the handle with the AdamW / EMA work items and the norm chunks that cut them (the item kernels of the sharded step)
+  int frozen = -1;
+  std::vector<std::pair<uint64_t, uint64_t>> train_ranges;   // [offset, count)
+  unsigned char* frozen_tab = nullptr;
+  int frozen_nitems = 0, frozen_nchunks = 0;
+  const GgetSqChunk* frozen_items() const { return reinterpret_cast<const GgetSqChunk*>(frozen_tab); }
+  const GgetSqChunk* frozen_chunks() const { return frozen_items() + frozen_nitems; }
+  // nothing trainable sits upstream of layer 0: the backward stops at the lowest trainable unit (else the full chain runs - the gate /
+  // raw-embedding gradients need the dgrad through the frozen layers)
+  bool truncated() const { return frozen >= 0 && !plan.has_gate && cfg.embed_dim == 0; }
+  int first_trainable_layer() const { return frozen < 0 ? 0 : std::min(frozen, cfg.num_layers); }
+  // [offset, count) of a bucket's trainable share: the bucket itself, nothing (count 0), or - the embedding bucket - its gate /
+  // raw-embedding parameters.  A bucket meets at most one of the ranges, in one piece.
+  std::pair<uint64_t, uint64_t> bucket_train_range(int bucket) const {
+    const uint64_t lo = bucket_range[bucket].first, hi = bucket_range[bucket].second;
+    if (frozen < 0) return {lo, hi - lo};
+    for (const auto& r : train_ranges) {
+      const uint64_t a = std::max(lo, r.first), b = std::min(hi, r.first + r.second);
+      if (a < b) return {a, b - a};
+    }
+    return {lo, 0};
+  }
   const int32_t* klo() const { return packed ? wsp<int32_t>(ws.key_lo) : nullptr; }
   const int32_t* khi() const { return packed ? wsp<int32_t>(ws.key_hi) : nullptr; }
 
@@ -654,6 +678,7 @@ extern "C" int gget_comm_destroy(gget_handle_t h);
 extern "C" int gget_destroy(gget_handle_t h) {
   if (h) gget_comm_destroy(h);
   if (h && h->shard_tab) (void)hipFree(h->shard_tab);
+  if (h && h->frozen_tab) (void)hipFree(h->frozen_tab);
   if (h && h->host_word) (void)hipHostFree(h->host_word);
   if (h && h->count_event) (void)hipEventDestroy(h->count_event);
   delete h;
@@ -818,7 +843,10 @@ extern "C" int gget_grad_acc_attach(gget_handle_t h, float* acc_dev) {
 extern "C" int gget_grad_accumulate(gget_handle_t h, void* stream) {
   GGET_REQUIRE(h != nullptr, "grad_accumulate: null handle");
   GGET_REQUIRE(h->grad_acc, "grad_accumulate: no accumulator arena (gget_grad_acc_attach)");
-  if (int e = k_grad_accumulate(h->G, h->grad_acc, h->plan.n_params, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
+  if (h->frozen >= 0) {      // the trainable ranges only: the frozen share of the accumulator is never written and never read
+    for (const auto& r : h->train_ranges)
+      if (int e = k_grad_accumulate(h->G + r.first, h->grad_acc + r.first, r.second, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
+  } else if (int e = k_grad_accumulate(h->G, h->grad_acc, h->plan.n_params, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
   ++h->grad_acc_count;
   return 0;
 }
@@ -837,6 +865,70 @@ extern "C" int gget_grad_acc_set_count(gget_handle_t h, int32_t n) {
   return 0;
 }
 
+extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* slots_per_rank);
+// the trainable element ranges for `frozen_layers` = k >= 0 with the parameter order of make_plan: [end of embed_tokens, start of layer 0)
+// (gate / raw-embedding parameters; usually empty) and [start of layer min(k, L), n_params); empty ranges are dropped
+static std::vector<std::pair<uint64_t, uint64_t>> frozen_train_ranges(const gget_config_t& c, const Plan& pl, int k) {
+  const int L = c.num_layers;
+  const uint64_t emb_end = pl.emb + align_up((uint64_t)c.vocab_size * c.hidden_size, 128);
+  const uint64_t layer0 = L > 0 ? pl.layers[0].ln1 : pl.normf;
+  const uint64_t from = k < L ? pl.layers[k].ln1 : pl.normf;
+  std::vector<std::pair<uint64_t, uint64_t>> r;
+  if (layer0 > emb_end) r.push_back({emb_end, layer0 - emb_end});
+  if (pl.n_params > from) r.push_back({from, pl.n_params - from});
+  return r;
+}
+
+extern "C" int gget_set_frozen(gget_handle_t h, int frozen_layers) {
+  GGET_REQUIRE(h != nullptr, "set_frozen: null handle");
+  GGET_REQUIRE(frozen_layers >= -1, "set_frozen: %d frozen layers (-1 = none, k >= 0 = embed_tokens and the first k layers)", frozen_layers);
+  GGET_REQUIRE(h->grad_acc_count == 0, "set_frozen: a gradient-accumulation window is open (%d micro-steps summed); step first", h->grad_acc_count);
+  if (h->frozen_tab) GGET_HIP_CHECK(hipFree(h->frozen_tab));
+  h->frozen_tab = nullptr;
+  h->frozen_nitems = h->frozen_nchunks = 0;
+  h->train_ranges.clear();
+  h->frozen = frozen_layers;
+  if (frozen_layers >= 0) {
+    h->train_ranges = frozen_train_ranges(h->cfg, h->plan, std::min(frozen_layers, h->cfg.num_layers));
+    uint64_t total = 0;
+    for (const auto& r : h->train_ranges) total += r.second;
+    // AdamW / EMA work items as the sharded step cuts them, and at most 1024 norm chunks (one block and one partial sum each)
+    const uint64_t chunk = std::max<uint64_t>(32768, align_up((total + 999) / 1000, 128));
+    std::vector<GgetSqChunk> items, chunks;
+    for (const auto& r : h->train_ranges) {
+      for (uint64_t o = 0; o < r.second; o += kAdamwItemElems) items.push_back(GgetSqChunk{r.first + o, std::min<uint64_t>(kAdamwItemElems, r.second - o)});
+      for (uint64_t o = 0; o < r.second; o += chunk) chunks.push_back(GgetSqChunk{r.first + o, std::min(chunk, r.second - o)});
+    }
+    GGET_REQUIRE(chunks.size() <= 1024, "set_frozen: %d norm chunks", (int)chunks.size());
+    if (!items.empty()) {
+      GGET_HIP_CHECK(hipMalloc(&h->frozen_tab, (items.size() + chunks.size()) * sizeof(GgetSqChunk)));
+      h->frozen_nitems = (int)items.size();
+      h->frozen_nchunks = (int)chunks.size();
+      GGET_HIP_CHECK(hipMemcpy((void*)h->frozen_items(), items.data(), items.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
+      GGET_HIP_CHECK(hipMemcpy((void*)h->frozen_chunks(), chunks.data(), chunks.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
+    }
+  }
+  // a shard plan cuts the trainable share of every bucket: built again for the new ranges
+  if (h->shard_world > 0) return gget_shard_init(h, h->shard_world, h->shard_rank, nullptr);
+  return 0;
+}
+
+extern "C" int gget_trainable_ranges(gget_handle_t h, uint64_t out[4], int32_t* n_out) {
+  GGET_REQUIRE(h != nullptr && out != nullptr && n_out != nullptr, "trainable_ranges: null argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (h->frozen < 0) {
+    out[1] = h->plan.n_params;
+    *n_out = 1;
+    return 0;
+  }
+  *n_out = (int32_t)h->train_ranges.size();
+  for (size_t i = 0; i < h->train_ranges.size(); ++i) {
+    out[2 * i] = h->train_ranges[i].first;
+    out[2 * i + 1] = h->train_ranges[i].second;
+  }
+  return 0;
+}
+
 extern "C" int gget_set_ema_decay(gget_handle_t h, float decay) {
   GGET_REQUIRE(h != nullptr, "set_ema_decay: null handle");
   GGET_REQUIRE(decay <= 1.f, "set_ema_decay: decay %g > 1", (double)decay);     // (NaN fails the comparison too)
@@ -849,8 +941,21 @@ extern "C" int gget_ema_update(gget_handle_t h, float decay, void* stream) {
   GGET_REQUIRE(h != nullptr, "ema_update: null handle");
   GGET_REQUIRE(h->ema && h->master, "ema_update: no EMA arena (gget_ema_attach) or no fp32 master arena");
   GGET_REQUIRE(decay >= 0.f && decay <= 1.f, "ema_update: decay %g outside [0, 1]", (double)decay);
+  // frozen weights are constant: lerp(ema, w) == w there once the arena was seeded, so the average skips them - bit-identical to timm's lerp
+  // over every entry.  decay == 0 IS the seed (ema = master): it also copies the frozen ranges (the complement of the trainable ones)
+  if (h->frozen >= 0 && decay == 0.f) {
+    uint64_t at = 0;
+    for (size_t i = 0; i <= h->train_ranges.size(); ++i) {
+      const uint64_t end = i < h->train_ranges.size() ? h->train_ranges[i].first : h->plan.n_params;
+      if (end > at)
+        if (int e = k_ema_lerp(h->master + at, h->ema + at, end - at, 0.f, (hipStream_t)stream)) return e;
+      if (i < h->train_ranges.size()) at = h->train_ranges[i].first + h->train_ranges[i].second;
+    }
+  }
   if (h->shard_world > 0)     // this rank's share (body slices + every tail; all of them for the loopback), as the sharded AdamW step
     return k_ema_lerp_items(h->master, h->ema, h->shard_items(), h->shard_nitems, decay, (hipStream_t)stream);
+  if (h->frozen >= 0)
+    return k_ema_lerp_items(h->master, h->ema, h->frozen_items(), h->frozen_nitems, decay, (hipStream_t)stream);
   return k_ema_lerp(h->master, h->ema, h->plan.n_params, decay, (hipStream_t)stream);
 }
 
@@ -1790,6 +1895,7 @@ namespace {
 
 int convert_bucket(gget_engine* h, int bucket, hipStream_t st) {
   if (h->defer_convert) return 0;   // monolithic backward: one conversion launch over all buckets at the end
+  if (h->truncated() && h->bucket_train_range(bucket).second == 0) return 0;
   const auto& bs = h->bucket_segs[bucket];
   return k_convert_segments(h->wsp<float>(h->ws.scratch32), h->G,
                             reinterpret_cast<const GgetSegment*>(h->W + h->ws.segs) + bs.first, bs.second, st);
@@ -1896,8 +2002,14 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
   if (int e = gemm_nn(dqkv, h->P + lo.wqkv, dxn, T, d, 3 * d, 3 * d, d, d, nullptr, st)) return e;
   // (fused with the LayerScale backward of the layer below, this RMSNorm backward writes w.dscaled - which this layer's down_proj weight
   //  gradient still reads - so it runs behind the weight gradients then)
-  const bool fuse_next = fuse_ls && i > 0;
-  if (!fuse_next)
+  // the lowest trainable layer above a frozen prefix (gget_set_frozen) with nothing trainable upstream: input_layernorm still owes its
+  // weight gradient, the input gradient has no reader - the weight-gradient-only kernel, and never the form fused with the LayerScale
+  // backward of the layer below (that layer needs nothing)
+  const bool boundary = h->truncated() && i == h->frozen;
+  const bool fuse_next = fuse_ls && i > 0 && !boundary;
+  if (boundary) {
+    if (int e = k_rmsnorm_dw(dxn, x_in, h->wsp<float>(lw.rstd1), s32 + lo.ln1_32, T, d, st, kAccumCopies, align_up((uint64_t)d, 128))) return e;
+  } else if (!fuse_next)
     if (int e = k_rmsnorm_bwd(dxn, x_in, h->P + lo.ln1, h->wsp<float>(lw.rstd1), dx_mid, dx_in, s32 + lo.ln1_32, T, d, st, kAccumCopies, align_up((uint64_t)d, 128)))
       return e;
   // weight gradients of the layer (dW = dY^T X, K = T).  All four dY / X pairs are still alive here.
@@ -2034,7 +2146,8 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
   }
   // ... and the bf16 count matrix of the embedding gradient (embed_bwd at the end of the backward: its own fill launch before)
   h->emb_cnt_cleared = false;
-  if (h->ws.emb_cnt && embed_dense_path(h->T, d, c.vocab_size, h->plan.has_gate, h->embed_drop()) && zr.n < kZeroRanges) {
+  if (h->ws.emb_cnt && embed_dense_path(h->T, d, c.vocab_size, h->plan.has_gate, h->embed_drop()) && zr.n < kZeroRanges &&
+      !h->truncated()) {     // (no embedding backward above a frozen embed_tokens)
     zr.add(h->wsp<unsigned char>(h->ws.emb_cnt), (size_t)h->T * align_up((uint64_t)c.vocab_size, 64) * 2);
     h->emb_cnt_cleared = true;
   }
@@ -2125,6 +2238,14 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
   bf16_t* dx = h->wsp<bf16_t>(w.dxa);
   h->ls2_done = false;
   T = h->T;   // from here on: rows of the token-major buffers
+  if (h->truncated() && h->frozen >= c.num_layers) {
+    // every layer is frozen: the final norm is the lowest trainable unit - its weight gradient only, and the chain ends here
+    if (int e = k_rmsnorm_dw(dhid, h->wsp<bf16_t>(w.xres[c.num_layers]), h->wsp<float>(w.rstd_f), s32 + h->plan.normf32, T, d, st,
+                             kAccumCopies, align_up((uint64_t)d, 128)))
+      return e;
+    h->dx_cur = nullptr;
+    return convert_bucket(h, 0, st);
+  }
   if (h->plan.has_res && ls_norm_fused()) {     // ... fused with the LayerScale backward of the last layer (layer_backward)
     const int li = c.num_layers - 1;
     const LayerOff& lp = h->plan.layers[li];
@@ -2142,8 +2263,9 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
 }
 
 extern "C" int gget_backward_layer(gget_handle_t h, int layer, void* stream) {
-  GGET_REQUIRE(h && h->fwd_valid && h->dx_cur, "backward_layer before backward_begin");
+  GGET_REQUIRE(h && h->fwd_valid && (h->dx_cur || h->truncated()), "backward_layer before backward_begin");
   GGET_REQUIRE(layer >= 0 && layer < h->cfg.num_layers, "layer %d out of range", layer);
+  if (h->truncated() && layer < h->frozen) return 0;   // below the boundary nothing is trainable: no launch (the schedule keeps its shape)
   CallScope scope(h);
   return layer_backward(h, layer, (hipStream_t)stream);
 }
@@ -2178,7 +2300,12 @@ int embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* g
 }
 
 extern "C" int gget_backward_end(gget_handle_t h, void* stream) {
-  GGET_REQUIRE(h && h->fwd_valid && h->dx_cur, "backward_end before backward_begin");
+  GGET_REQUIRE(h && h->fwd_valid && (h->dx_cur || h->truncated()), "backward_end before backward_begin");
+  if (h->truncated()) {     // embed_tokens is frozen and nothing else is upstream: no embedding backward
+    h->emb_cnt_cleared = false;
+    h->dx_cur = nullptr;
+    return 0;
+  }
   CallScope scope(h);
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
@@ -2225,6 +2352,10 @@ extern "C" int gget_backward(gget_handle_t h, float loss_scale, void* stream) {
   if (rc) return rc;
   int nseg = 0;
   for (const auto& bs : h->bucket_segs) nseg += bs.second;
+  if (h->truncated()) {    // the trainable buckets only: heads, then layers L-1 .. frozen - a prefix of the segment table (completion order)
+    nseg = 0;
+    for (int b = 0; b <= h->cfg.num_layers - h->first_trainable_layer(); ++b) nseg += h->bucket_segs[b].second;
+  }
   return k_convert_segments(h->wsp<float>(h->ws.scratch32), h->G, reinterpret_cast<const GgetSegment*>(h->W + h->ws.segs), nseg,
                             (hipStream_t)stream);
 }
@@ -2245,6 +2376,14 @@ extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float bet
   const bool from_acc = h->grad_from_acc();
   const void* grad = h->grad_src();
   h->grad_acc_count = 0;
+  if (h->frozen >= 0) {
+    // frozen prefix: norm, clip, update and EMA over the trainable ranges only, through the chunk / item kernels of the sharded step
+    // (one update function: the same bits per element).  GGET_OPT_NORM_FROM_BACKWARD falls back to this plain pass.
+    if (need_norm)
+      if (int e = k_grad_sqnorm_chunks(grad, h->frozen_chunks(), h->frozen_nchunks, nullptr, 0, sq, st, from_acc)) return e;
+    return k_adamw_items(h->master, h->am, h->av, grad, h->P, h->frozen_items(), h->frozen_nitems, lr, beta1, beta2, eps, weight_decay, step,
+                         max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay, from_acc);
+  }
   if (need_norm) {
     // the shortcut holds only while the gradient array is exactly what the last backward wrote: the caller promised that
     // (GGET_OPT_NORM_FROM_BACKWARD), grad_scale != 1 means an exchange happened anyway, and every layer must have left its partials;
@@ -2291,7 +2430,11 @@ extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* sl
   const bool all_ranks = h->comm_loopback;
   const uint64_t C = GGET_SHARD_CHUNK;
   std::vector<ShardBucket> plan;
-  for (const auto& r : h->bucket_range) plan.push_back(shard_bucket(r.first, r.second - r.first, world));
+  // (a frozen prefix, gget_set_frozen: a bucket's sharded range is its trainable share; an empty one - count 0 - is skipped everywhere)
+  for (int b = 0; b < (int)h->bucket_range.size(); ++b) {
+    const auto r = h->bucket_train_range(b);
+    plan.push_back(shard_bucket(r.first, r.second, world));
+  }
   // the norm's chunk grid: off_b + j C inside every bucket (independent of world: slices are multiples of C); owner = the rank of the body
   // slice, rank 0 for the tail
   std::vector<GgetSqChunk> grid;
@@ -2897,6 +3040,7 @@ extern "C" int gget_reduce_scatter_grads_async(gget_handle_t h, int bucket, int 
   GGET_REQUIRE(h->shard_world > 0, "reduce_scatter_grads: call gget_shard_init first");
   GGET_REQUIRE(bucket >= 0 && bucket < (int)h->shard_plan.size(), "reduce_scatter_grads: bucket %d out of range", bucket);
   const ShardBucket& b = h->shard_plan[bucket];
+  if (b.cnt == 0) return 0;     // (a frozen bucket, gget_set_frozen: nothing to exchange)
   // the loopback stands for world ranks with this rank's gradients and does the work of all of them: body and tail are world x
   if (h->comm_loopback) return gget_allreduce_range_async(h, b.off, b.cnt, 0, side_stream);
   hipStream_t st = (hipStream_t)side_stream;
@@ -2967,6 +3111,15 @@ extern "C" int gget_shard_allgather_async(gget_handle_t h, int what, float* slot
 extern "C" int gget_allreduce_grads_async(gget_handle_t h, int bucket, int fp32_accumulate, void* side_stream) {
   GGET_REQUIRE(h && (h->comm || h->comm_loopback), "allreduce_grads: call gget_comm_init first");
   GGET_REQUIRE(bucket >= -1 && bucket < (int)h->bucket_range.size(), "allreduce_grads: bucket %d out of range", bucket);
+  if (h->frozen >= 0) {     // the trainable share only: of the bucket, or (-1) every trainable range
+    if (bucket >= 0) {
+      const auto r = h->bucket_train_range(bucket);
+      return gget_allreduce_range_async(h, r.first, r.second, fp32_accumulate, side_stream);
+    }
+    for (const auto& r : h->train_ranges)
+      if (int e = gget_allreduce_range_async(h, r.first, r.second, fp32_accumulate, side_stream)) return e;
+    return 0;
+  }
   const uint64_t lo = bucket < 0 ? 0 : h->bucket_range[bucket].first;
   const uint64_t hi = bucket < 0 ? h->plan.n_params : h->bucket_range[bucket].second;
   return gget_allreduce_range_async(h, lo, hi - lo, fp32_accumulate, side_stream);

@@ -49,6 +49,10 @@ int k_det_scratch(size_t floats, float** out);
 int k_ordered_colsum(float* part, int nblk, int d, float* dst, hipStream_t st);
 int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
                   float* dw_accum, int T, int d, hipStream_t st, int copies = 1, uint64_t copy_stride = 0);
+// the weight gradient of k_rmsnorm_bwd alone (dw += sum_r dy * x * rstd; no residual gradient read, no dx written): the boundary of a
+// frozen prefix (gget_set_frozen).  Same accumulate-copies layout, same reproducible mode (menu().deterministic).
+int k_rmsnorm_dw(const void* dy, const void* x, const float* rstd, float* dw_accum, int T, int d, hipStream_t st, int copies = 1,
+                 uint64_t copy_stride = 0);
 int k_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H,
            int inverse, hipStream_t st);
 int k_rope_table(float* cos_tab, float* sin_tab, int max_pos, float theta, hipStream_t st);
@@ -118,7 +122,8 @@ inline size_t k_grad_sqnorm_ws_bytes() { return (16 + 1024) * sizeof(float); }
 // the same over a list of chunks of the gradient array (offset / count pairs, counts multiples of 8, at most 1024 chunks) plus `nextra`
 // ready-made partial sums (the weight-gradient kernels' per-tile sums): ws[0] = sum of both, fixed order
 struct GgetSqChunk { uint64_t off; uint64_t cnt; };
-int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st);
+int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st,
+                         bool grad_f32 = false);
 // sharded step (ZeRO-2, engine.hip gget_shard_*): per-chunk sums into out[slot[c]]; the one-block sum of the gathered partials in global chunk
 // order (ws[0]); AdamW over work items of <= kAdamwItemElems elements (offsets / counts multiples of 4, one block each)
 constexpr int kAdamwItemElems = 2048;

@@ -520,6 +520,77 @@ __global__ void __launch_bounds__(kBlock) rmsnorm_bwd_kernel(const bf16_t* __res
   }
 }
 
+// weight gradient ONLY: dw[c] += sum_r dy[r,c] * (x[r,c] * rstd[r]) - the RMSNorm backward of the lowest trainable unit above a frozen
+// prefix (gget_set_frozen; reference freeze_llama_layers, src/utils/modules_utils.py:45-54): nothing below it is trained, so the input
+// gradient has no reader.  Two HBM streams in (dy, x), no residual gradient read, no dx store, the norm weight itself not needed: 4 B per
+// element instead of 6 - 8.  Lane mapping, row dealing (wave w of block b: rows 4 b + w, + 4 gridDim, ...), one-row-ahead loads and the
+// block reduction through the two LDS planes are rmsnorm_bwd_kernel's: in reproducible mode (dw_part) the per-block partials, and with
+// them the sum, are the bits that kernel leaves.  Without dx, w and the residual the d <= 1024 form keeps 76 registers and no scratch
+// (the compiler's resource report): six waves per SIMD, a row in flight each.
+template <int NCH>
+__global__ void __launch_bounds__(kBlock) rmsnorm_dw_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                            const float* __restrict__ rstd_in, float* __restrict__ dw_accum, int T, int d,
+                                                            int copies, uint64_t copy_stride, float* __restrict__ dw_part) {
+  extern __shared__ float dw_lds[];  // [4][d]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nchunk = d >> 3;
+  float dwp[NCH][8];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dwp[i][e] = 0.f;
+  const int stride = gridDim.x * (kBlock / 64);
+  int row = blockIdx.x * (kBlock / 64) + wave;
+  uint4 xr[NCH], dr[NCH];
+  float rstd = 0.f;
+  auto fetch = [&](int r) {
+    rstd = rstd_in[r];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        xr[i] = ldg16(x + (size_t)r * d + c * 8);
+        dr[i] = ldg16(dy + (size_t)r * d + c * 8);
+      }
+    }
+  };
+  if (row < T) fetch(row);
+  for (; row < T; row += stride) {
+    const float rs = rstd;
+    float xv[NCH][8], dv[NCH][8];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      unpack8(xr[i], xv[i]);
+      unpack8(dr[i], dv[i]);
+    }
+    if (row + stride < T) fetch(row + stride);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dwp[i][e] += dv[i][e] * (xv[i][e] * rs);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {   // (plane layout of the partials: see rmsnorm_bwd_kernel)
+      *reinterpret_cast<float4*>(dw_lds + wave * d + c * 4) = make_float4(dwp[i][0], dwp[i][1], dwp[i][2], dwp[i][3]);
+      *reinterpret_cast<float4*>(dw_lds + wave * d + (d >> 1) + c * 4) = make_float4(dwp[i][4], dwp[i][5], dwp[i][6], dwp[i][7]);
+    }
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < d; t += kBlock) {
+    const int hd = d >> 1, pl = t >= hd ? 1 : 0, ix = t - pl * hd;
+    const int j = (ix >> 2) * 8 + pl * 4 + (ix & 3);
+    const float s = dw_lds[t] + dw_lds[d + t] + dw_lds[2 * d + t] + dw_lds[3 * d + t];
+    if (dw_part) dw_part[(size_t)blockIdx.x * d + j] = s;     // reproducible mode: summed in block order by ordered_colsum_kernel
+    else unsafeAtomicAdd(dw_accum + (size_t)(blockIdx.x % copies) * copy_stride + j, s);
+  }
+}
+
 // SHORT launches (round 5).  The step's shapes are short - T = 5 696 rows at the headline, 22 rows per CU: with 4-wave blocks of 4 rows per
 // wave only ~6 waves per CU had loads in flight (25 KB per CU where HBM latency x bandwidth wants ~47 KB: 3.2 TB/s), and fewer rows per wave
 // multiplied the per-block atomics of the weight gradient.  Here: ONE block of NW = 16 waves per CU, the rows cut into contiguous ranges
@@ -2491,6 +2562,28 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
   return 0;
 }
 
+int k_rmsnorm_dw(const void* dy, const void* x, const float* rstd, float* dw_accum, int T, int d, hipStream_t st, int copies,
+                 uint64_t copy_stride) {
+  GGET_REQUIRE(d % 8 == 0 && d <= 64 * 8 * kMaxChunksPerLane, "rmsnorm: d=%d unsupported", d);
+  if (T == 0) return 0;
+  if (copies < 1) copies = 1;
+  const LaunchMenu& m = menu();
+  const int grid = grid_for(T, 4 * m.rms_rows, 4096);     // (k_rmsnorm_bwd's grid of 4-wave blocks: <= 4096, the rows of the scratch below)
+  float* part = nullptr;
+  if (m.deterministic) {     // per-block partials [4096][d] + segment sums [64][d], as k_rmsnorm_bwd
+    if (int e = k_det_scratch((size_t)(4096 + 64) * d, &part)) return e;
+  }
+  if (d <= 1024)
+    hipLaunchKernelGGL(rmsnorm_dw_kernel<2>, dim3(grid), dim3(kBlock), 4 * d * sizeof(float), st, (const bf16_t*)dy, (const bf16_t*)x, rstd,
+                       dw_accum, T, d, copies, copy_stride, part);
+  else
+    hipLaunchKernelGGL(rmsnorm_dw_kernel<4>, dim3(grid), dim3(kBlock), 4 * d * sizeof(float), st, (const bf16_t*)dy, (const bf16_t*)x, rstd,
+                       dw_accum, T, d, copies, copy_stride, part);
+  GGET_LAUNCH_CHECK();
+  if (part) return k_ordered_colsum(part, grid, d, dw_accum, st);
+  return 0;
+}
+
 int k_det_scratch(size_t floats, float** out) {
   if (g_det_bytes < floats * sizeof(float)) {
     if (g_det_scratch) GGET_HIP_CHECK(hipFree(g_det_scratch));
@@ -3018,8 +3111,12 @@ int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st, bool grad_
   return 0;
 }
 
-int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st) {
-  if (nchunks > 0)
+int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st,
+                         bool grad_f32) {
+  if (nchunks > 0 && grad_f32)
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<float>, dim3(nchunks), dim3(kBlock), 0, st, (const float*)g, chunks_dev, ws + 16,
+                       (const int32_t*)nullptr);
+  else if (nchunks > 0)
     hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<bf16_t>, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, ws + 16,
                        (const int32_t*)nullptr);
   hipLaunchKernelGGL(grad_sqnorm_final2_kernel, dim3(1), dim3(kBlock), 0, st, ws, nchunks, extra, nextra);

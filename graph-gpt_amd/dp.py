@@ -98,6 +98,11 @@ def exchange_groups(buckets, bucket_mb: float) -> Dict[int, Any]:
     thresh = bucket_mb * 2 ** 20 / 2        # elements (bf16)
     nb = len(buckets)
     for b, (off, cnt) in enumerate(buckets):
+        if cnt == 0:        # a frozen bucket (Engine.trainable_buckets): nothing to exchange; what is open goes with the bucket before it
+            if lo is not None:
+                groups[b - 1] = (lo, hi - lo)
+                lo = hi = None
+            continue
         if lo is not None and (off + cnt == lo or off == hi):
             lo, hi = min(lo, off), max(hi, off + cnt)
         else:
@@ -209,7 +214,8 @@ class TorchTransport(NoTransport):
 
     def all_reduce_all(self, e):
         if self.g.world > 1:
-            all_reduce_bucket(e.grad_bf16, (0, e.grad_bf16.numel()), self.g.pg, async_op=False, fp32_accumulate=self.g.fp32_reduce)
+            for rng in e.train_ranges:      # (the whole array unless a prefix is frozen: Engine.set_frozen)
+                all_reduce_bucket(e.grad_bf16, rng, self.g.pg, async_op=False, fp32_accumulate=self.g.fp32_reduce)
 
     def reduce_scatter(self, e, b: int):
         reduce_scatter_bucket(e.grad_bf16, e.shard_buckets[b], self.g.rank, self.g.world, self.g.pg, self.g.fp32_reduce)

@@ -112,6 +112,9 @@ class Engine:
         self._params_are_ema = False
         # gradient accumulation (grad_acc_attach): the seventh arena, allocated on demand - the fp32 sum of a window's micro-batch gradients
         self.grad_acc = None
+        # frozen prefix (set_frozen): -1 = everything trains; `train_ranges` = [(offset, count)] of the trainable elements of the flat arenas
+        self.frozen = -1
+        self.train_ranges = [(0, self.n_params)]
         self._params_ready = None   # event behind the all-gather of the bf16 copy: the next reader of the weights waits for it
         self._keep = None  # keeps the last batch tensors alive until backward has consumed them
 
@@ -156,6 +159,36 @@ class Engine:
                               "share they are stale; call GgetEngine.consolidate() on every rank first")
         L.check(self.lib.gget_sync_params(self.h, _stream()))
         self._params_are_ema = False
+
+    # ------------------------------------------------------------------ frozen prefix (finetune.freeze)
+    def set_frozen(self, k: int):
+        """Freeze embed_tokens and the first k layers (gget_set_frozen; -1 = nothing, the reference's freeze_llama_layers pattern): norm,
+        clip, AdamW, EMA, accumulation and the exchange then touch `train_ranges` only, and the backward stops at the lowest trainable unit
+        when nothing trainable sits upstream of layer 0.  An active shard plan is rebuilt for the new ranges."""
+        L.check(self.lib.gget_set_frozen(self.h, int(k)))
+        self.frozen = int(k)
+        out, n = (C.c_uint64 * 4)(), C.c_int32(0)
+        L.check(self.lib.gget_trainable_ranges(self.h, out, C.byref(n)))
+        self.train_ranges = [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n.value)]
+        if self.shard is not None:
+            self.shard_init(*self.shard)
+
+    def bucket_train_range(self, b: int):
+        """(offset, count) of bucket b's trainable share: the bucket, nothing (count 0), or the embedding bucket's gate / raw-embedding part."""
+        lo, cnt = self.buckets[b]
+        for off, n in self.train_ranges:
+            a, z = max(lo, off), min(lo + cnt, off + n)
+            if a < z:
+                return a, z - a
+        return lo, 0
+
+    def trainable_buckets(self):
+        """The exchange's view of `buckets`: every bucket cut to its trainable share (count 0 = nothing to exchange)."""
+        return [self.bucket_train_range(b) for b in range(len(self.buckets))]
+
+    def is_frozen(self, name: str) -> bool:
+        p = self.params[name]
+        return not any(off <= p["offset"] < off + n for off, n in self.train_ranges)
 
     # ------------------------------------------------------------------ gradient accumulation (optimizer.gradient_accumulation_steps)
     def grad_acc_attach(self):
@@ -450,6 +483,14 @@ class Engine:
             return
         self.shard = (int(world), int(rank))
         self.shard_buckets = self.shard_plan_of(self.cfg, world, len(self.buckets))
+        if self.frozen >= 0:    # the plan of a bucket's trainable share (gget_shard_init cuts the same ranges by the same rule)
+            chunk = L.SHARD_CHUNK
+            plans = []
+            for b in range(len(self.buckets)):
+                off, cnt = self.bucket_train_range(b)
+                sl = cnt // (int(world) * chunk) * chunk
+                plans.append((off, cnt, sl, off + int(world) * sl, cnt - int(world) * sl))
+            self.shard_buckets = plans
         self.shard_slots = torch.zeros(int(world) * n.value, dtype=torch.float32, device=self.device)
 
     def reduce_scatter_grads_async(self, bucket: int, fp32_accumulate: bool = False, stream: Optional[torch.cuda.Stream] = None):

@@ -201,6 +201,7 @@ class _GgetModel(nn.Module):
         self._token_layout = "auto"
         self._dp_menu = (0, False)      # (reserve_cus, lds_headroom) of every handle this model creates: set_dp_menu
         self._dirty = False             # master weights changed behind the engine's back (external optimizer)
+        self._frozen_layers = -1        # freeze_layers(k): embed_tokens + the first k layers are not trained; -1 = nothing frozen
         state = make_state_dict(self.spec, seed=seed, std=config.initializer_range)
         # module tree with the reference's attribute paths: model.embed_tokens / model.layers[i].* / model.norm ...
         self._flat: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -256,6 +257,35 @@ class _GgetModel(nn.Module):
         self._dp_menu = (max(0, int(reserve_cus)), bool(lds_headroom))
         if self._engine is not None:
             self._engine.set_dp_menu(*self._dp_menu)
+
+    def frozen_names(self, k: Optional[int] = None):
+        """State-dict names `freeze_llama_layers(model, k)` of the reference leaves with requires_grad = False
+        (src/utils/modules_utils.py:45-54): model.embed_tokens.weight and every parameter of model.layers[:k] (a slice: k >= L = all)."""
+        k = self._frozen_layers if k is None else int(k)
+        if k < 0:
+            return []
+        out = []
+        for name in self._flat:
+            parts = name.split(".")
+            if name == "model.embed_tokens.weight" or (parts[:2] == ["model", "layers"] and int(parts[2]) < k):
+                out.append(name)
+        return out
+
+    def freeze_layers(self, k: int):
+        """`training.finetune.freeze = k` (reference freeze_llama_layers): requires_grad = False on exactly the reference's names, the
+        engine told (Engine.set_frozen) now and whenever it is re-created.  k = -1 changes nothing; a frozen parameter is never thawed
+        (the reference has no such call either)."""
+        k = int(k)
+        if k < 0:
+            return self
+        self._frozen_layers = max(k, self._frozen_layers)
+        for name in self.frozen_names():
+            p = self._flat[name]
+            p.requires_grad = False
+            p.grad = None
+        if self._engine is not None:
+            self._engine.set_frozen(self._frozen_layers)
+        return self
 
     def gradient_checkpointing_enable(self, *a, **k):
         return None  # activations for 288 GB HBM are kept; recompute is never needed on this path
@@ -331,6 +361,13 @@ class _GgetModel(nn.Module):
         new.set_stack_method(getattr(self.config, "stack_method", None) == "long")
         new.set_rope_range(float(getattr(self.config, "rope_range", 0) or 0))
         new.set_dp_menu(*self._dp_menu)
+        if self._frozen_layers >= 0:        # (after the accumulation window moved: the new handle's window count is set, the call below
+            n_open = new.grad_acc_count()   #  is refused inside one - close it around the call)
+            if n_open:
+                new.grad_acc_set_count(0)
+            new.set_frozen(self._frozen_layers)
+            if n_open:
+                new.grad_acc_set_count(n_open)
         new.varlen_mode = self._LAYOUTS[self._token_layout]
         self._engine = new
         self._anchor = torch.zeros(1, device=new.device, requires_grad=True)
@@ -378,6 +415,9 @@ class _GgetModel(nn.Module):
         if self.materialize_grads:
             scale = g.to(torch.float32) / world
             for name, p in self._flat.items():
+                if not p.requires_grad:     # (freeze_layers: a frozen parameter has no gradient)
+                    p.grad = None
+                    continue
                 p.grad = (e.view(name, "grad").to(torch.float32) * scale).view(p.shape)
         self._dirty = True  # an external optimizer will now touch the master weights
 
@@ -561,6 +601,23 @@ class GraphGPTTaskModel(_GgetModel):
         return DoubleHeadsModelOutput(pretrain_loss=None, task_loss=self._wrap_loss(loss), pretrain_logits=None,
                                       task_logits=logits, task_hidden_states=hid,
                                       hidden_states=self._collect_hidden_states(B, S) if want_hs else None)   # modeling_finetune.py:323
+
+
+def freeze_llama_layers(model, freeze_layer_count: int = 0):
+    """reference src/utils/modules_utils.py:45-54: freeze model.embed_tokens and model.layers[:freeze_layer_count].  The reference flips
+    requires_grad and lets autograd / the optimizer's parameter filter do the rest; here the model also tells its engine
+    (_GgetModel.freeze_layers), which stops the backward at the lowest trainable unit and steps over the trainable ranges only."""
+    model.freeze_layers(int(freeze_layer_count))
+    for name in model.frozen_names():
+        print(f"Freeze param:: {name}")
+
+
+def print_trainable_parameters(model) -> int:
+    """reference src/utils/inspection_utils.py:13-32 (copied there from peft): the trainable parameter count, printed and returned."""
+    trainable = sum(p.numel() for _, p in model.named_parameters() if p.requires_grad)
+    total = sum(p.numel() for _, p in model.named_parameters())
+    print(f"trainable params: {trainable} || all params: {total} || trainable%: {100 * trainable / total}")
+    return trainable
 
 
 def check_batch(input_ids, attention_mask, labels, vocab_size: int):

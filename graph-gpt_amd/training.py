@@ -259,7 +259,7 @@ class GgetEngine:
 
     def exchange_groups(self, e) -> Dict[int, Any]:
         """{last bucket of a group: (offset, count)} - what one collective covers at this engine's `bucket_mb` (dp.exchange_groups)."""
-        return exchange_groups(e.buckets, self.bucket_mb)
+        return exchange_groups(e.trainable_buckets() if getattr(e, "frozen", -1) >= 0 else e.buckets, self.bucket_mb)
 
     # -- the data-parallel launch menu, decided by measurement on the machine the job runs on
     def set_dp_menu(self, overlap: Optional[bool] = None, reserve_cus: Optional[int] = None):
@@ -1010,6 +1010,20 @@ class FinetuneMode(TrainingMode):
         CF._set(CF._get(mc, "pt_head"), "next_n_token", 1)
         pipeline.model_cfg = mc
         pipeline.config = convert_to_legacy_config(mc)
+
+    def post_model_setup(self, pipeline):
+        """reference finetune_mode.py:204-212: `finetune.freeze > -1` freezes embed_tokens and the first `freeze` layers
+        (modules_utils.freeze_llama_layers), then config.num_params = the trainable count print_trainable_parameters reports."""
+        from .modeling import freeze_llama_layers, print_trainable_parameters
+        freeze = -1
+        if pipeline.reference_cfg:
+            from . import conf as CF
+            ft = CF._get(pipeline.train_cfg, "finetune", None)
+            freeze = int(CF._get(ft, "freeze", -1)) if ft is not None else -1
+        if freeze > -1:
+            freeze_llama_layers(pipeline.model, freeze)
+        pipeline.model.config.num_params = print_trainable_parameters(pipeline.model)
+        return False
 
     def setup_optimizer(self, pipeline):
         if pipeline.reference_cfg:

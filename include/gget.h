@@ -338,6 +338,32 @@ int gget_grad_acc_count(gget_handle_t h, int32_t* out);
 int gget_grad_acc_set_count(gget_handle_t h, int32_t n);
 
 /* ------------------------------------------------------------------------------------------
+ * Frozen prefix (`training.finetune.freeze = k`, configs/training/base.yaml:65 "-1->no, 0->embedding").  replaces:
+ * modules_utils.freeze_llama_layers (src/utils/modules_utils.py:45-54) as FinetuneMode.post_model_setup calls it
+ * (src/training/finetune_mode.py:204-212) plus what torch does with requires_grad = False: no gradient, no share of the clip's norm, no
+ * optimizer update.  Only this prefix pattern exists; there is no per-parameter mask.
+ * ------------------------------------------------------------------------------------------ */
+/* replaces: freeze_llama_layers(model, k) (modules_utils.py:45-54).  frozen_layers = -1: nothing is frozen (the state of a new handle; every
+ * launch is then what it was without this entry).  k >= 0: model.embed_tokens.weight and every parameter of layers [0, min(k, L)) are
+ * frozen (a Python slice: k >= L freezes all layers); gate / raw-embedding parameters, lambda_1 / lambda_2 of the layers >= k, model.norm
+ * and the heads stay trainable.  From the next call on, norm, clip, AdamW, the EMA lerp (fused and gget_ema_update with decay > 0; decay
+ * = 0, the seed, still copies every weight), gget_grad_accumulate, the shard plan (a bucket's sharded range = its trainable share, count 0
+ * = skipped everywhere; an active plan is rebuilt, its slots_per_rank may shrink: gget_shard_init reports it) and gget_allreduce_grads_async touch
+ * the trainable ranges only: master, m, v, the bf16 copy and the EMA of the frozen ranges are never written.  If nothing trainable sits
+ * upstream of layer 0 (no gated aggregation, embed_dim = 0) the backward is truncated: gget_backward_layer(i < k) and gget_backward_end
+ * return 0 without a launch, the frozen gradient ranges are not written, and the lowest trainable unit - layer k's input_layernorm, or
+ * model.norm for k >= L - runs a weight-gradient-only RMSNorm backward.  Otherwise the full chain runs (the upstream gradients need the
+ * dgrad through the frozen layers) and frozen gradients are written but never read.  Callable between steps; refused while a
+ * gradient-accumulation window is open.  Synchronous (uploads the work-item tables of the ranges). */
+int gget_set_frozen(gget_handle_t h, int frozen_layers);
+/* replaces: the `p.requires_grad` filter the reference's optimizers and clip_grad_norm_ apply to model.parameters() (modules_utils.py:45-54
+ * sets the flags; src/utils/training_utils.py:68-80 consumes them): the trainable element ranges of the flat arenas, out = {offset0, count0,
+ * offset1, count1}, *n_out = how many are valid (1 = everything, [0, n_params), when nothing is frozen; else at most two:
+ * [end of embed_tokens, start of layer 0) - empty and dropped without gate / raw-embedding parameters - and [start of layer min(k, L),
+ * n_params)).  The host builds its exchange groups from them. */
+int gget_trainable_ranges(gget_handle_t h, uint64_t out[4], int32_t* n_out);
+
+/* ------------------------------------------------------------------------------------------
  * Weight EMA (`training.optimizer.use_ema` / `ema_decay`; the reference's fine-tune launch scripts switch it on, e.g.
  * examples/graph_lvl/pcqm4m_v2_supervised.sh:65).  replaces: timm's ModelEmaV3 as the reference patches and drives it -
  * src/utils/patch_utils.py:11-42 (apply_update_: every bf16 DeepSpeed weight cast to fp32, torch._foreach_lerp_ over the module's tensors)

@@ -1049,6 +1049,33 @@ def pipeline_config_fixture():
     print("pipeline_config.json written:", {k: sorted(v)[:4] for k, v in out.items()})
 
 
+def freeze_names_fixture():
+    """`training.finetune.freeze` (configs/training/base.yaml:65): what modules_utils.freeze_llama_layers (:45-54) leaves with
+    requires_grad = False on the reference's GraphGPTTaskModel and the count inspection_utils.print_trainable_parameters (:13-32) then
+    reports, for L = 3 (an interior boundary, k = L and k > L), with and without gated aggregation and LayerScale.  Names and numbers only."""
+    import json
+    PT, FT, Cfg = import_reference()
+    from src.utils import modules_utils, inspection_utils
+    cases = []
+    for gated in (False, True):
+        for ls in (0.0, 1.0):
+            spec = spec_mod.ModelSpec(kind=spec_mod.KIND_TASK, vocab_size=300, hidden_size=128, intermediate_size=512, num_layers=3, num_heads=2,
+                                      stacked_feat=4, next_n_token=1, gated_agg=gated, num_labels=2, layer_scale_init=ls)
+            for k in (-1, 0, 1, 2, 3, 5):
+                model = FT(ref_config(Cfg, spec, num_labels=2))
+                if k > -1:
+                    modules_utils.freeze_llama_layers(model, k)
+                frozen = sorted(n for n, p in model.named_parameters() if not p.requires_grad)
+                cases.append({"gated": gated, "layer_scale": ls, "freeze": k, "frozen": frozen,
+                              "trainable": int(inspection_utils.print_trainable_parameters(model)),
+                              "total": int(sum(p.numel() for p in model.parameters()))})
+    meta = {"vocab_size": 300, "hidden_size": 128, "intermediate_size": 512, "num_layers": 3, "num_heads": 2, "stacked_feat": 4, "num_labels": 2}
+    with open(os.path.join(ROOT, "tests", "golden", "freeze_names.json"), "w") as fh:
+        json.dump({"model": meta, "cases": cases}, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(f"freeze_names written: {len(cases)} cases")
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -1090,6 +1117,8 @@ def main():
         config_convert_fixture()
     if not only or "pipeline_config" in only:
         pipeline_config_fixture()
+    if not only or "freeze_names" in only:
+        freeze_names_fixture()
 
 
 if __name__ == "__main__":
