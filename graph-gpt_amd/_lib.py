@@ -52,6 +52,7 @@ SIGNATURES = {
     "gget_grad_acc_set_count": (i32, [vp, i32]),
     "gget_set_frozen": (i32, [vp, i32]),
     "gget_trainable_ranges": (i32, [vp, vp, vp]),
+    "gget_bucket_train_range": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64)]),
     "gget_ema_attach": (i32, [vp, vp]),
     "gget_set_ema_decay": (i32, [vp, f32]),
     "gget_ema_update": (i32, [vp, f32, vp]),
@@ -73,6 +74,7 @@ SIGNATURES = {
     "gget_comm_init_loopback": (i32, [vp, i32]),
     "gget_shard_plan": (i32, [C.POINTER(GgetConfig), i32, i32, C.POINTER(u64)]),
     "gget_shard_init": (i32, [vp, i32, i32, C.POINTER(i32)]),
+    "gget_shard_bucket": (i32, [vp, i32, C.POINTER(u64)]),
     "gget_reduce_scatter_grads_async": (i32, [vp, i32, i32, vp]),
     "gget_shard_sqnorm_partials": (i32, [vp, vp, vp]),
     "gget_shard_allgather_async": (i32, [vp, i32, vp, vp]),

@@ -390,6 +390,55 @@ static ShardBucket shard_bucket(uint64_t off, uint64_t cnt, int world) {
   return ShardBucket{off, cnt, slice, off + (uint64_t)world * slice, cnt - (uint64_t)world * slice};
 }
 
+// [offset, count) ranges cut into the work items of the item kernels (k_adamw_items, k_ema_lerp_items: one block per item)
+static std::vector<GgetSqChunk> cut_items(const std::vector<std::pair<uint64_t, uint64_t>>& ranges) {
+  std::vector<GgetSqChunk> items;
+  for (const auto& r : ranges)
+    for (uint64_t o = 0; o < r.second; o += kAdamwItemElems) items.push_back(GgetSqChunk{r.first + o, std::min<uint64_t>(kAdamwItemElems, r.second - o)});
+  return items;
+}
+
+// The work list of an optimizer step that does not run over the whole arena (a frozen prefix, a rank's shard), one device allocation: the
+// AdamW / EMA work items, the chunks the norm sums and - the sharded form - the slot of each of those chunks in the gathered partial vector
+// (chunk_slot) and of every chunk of the global grid (slot_of)
+struct OptWork {
+  unsigned char* tab = nullptr;
+  const GgetSqChunk* items = nullptr;
+  const GgetSqChunk* chunks = nullptr;
+  const int32_t* chunk_slot = nullptr;
+  const int32_t* slot_of = nullptr;
+  int nitems = 0, nchunks = 0, nglobal = 0;
+  int reset() {
+    unsigned char* t = tab;
+    *this = OptWork();
+    if (t) GGET_HIP_CHECK(hipFree(t));
+    return 0;
+  }
+  int upload(const std::vector<GgetSqChunk>& it, const std::vector<GgetSqChunk>& ch, const std::vector<int32_t>& ch_slot = {},
+             const std::vector<int32_t>& global_slot = {}) {
+    if (int e = reset()) return e;
+    const size_t b_it = it.size() * sizeof(GgetSqChunk), b_ch = ch.size() * sizeof(GgetSqChunk);
+    const size_t b_cs = ch_slot.size() * sizeof(int32_t), b_gs = global_slot.size() * sizeof(int32_t);
+    if (b_it + b_ch + b_cs + b_gs == 0) return 0;
+    GGET_HIP_CHECK(hipMalloc(&tab, b_it + b_ch + b_cs + b_gs));
+    items = reinterpret_cast<const GgetSqChunk*>(tab);
+    chunks = items + it.size();
+    chunk_slot = reinterpret_cast<const int32_t*>(chunks + ch.size());
+    slot_of = chunk_slot + ch_slot.size();
+    auto put = [](const void* dst, const void* src, size_t bytes) {
+      return bytes ? hipMemcpy(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    };
+    GGET_HIP_CHECK(put(items, it.data(), b_it));
+    GGET_HIP_CHECK(put(chunks, ch.data(), b_ch));
+    GGET_HIP_CHECK(put(chunk_slot, ch_slot.data(), b_cs));
+    GGET_HIP_CHECK(put(slot_of, global_slot.data(), b_gs));
+    nitems = (int)it.size();
+    nchunks = (int)ch.size();
+    nglobal = (int)global_slot.size();
+    return 0;
+  }
+};
+
 struct gget_engine {
   gget_config_t cfg;
   Plan plan;
@@ -427,6 +476,7 @@ struct gget_engine {
   // their weight-gradient launches left behind (sq_layers = layers of the last backward that did), the rest from a chunked pass
   bool opt_norm_from_backward = false;
   bool opt_skip_nonfinite = false;     // GGET_OPT_SKIP_NONFINITE_STEP: gget_adamw_step leaves the parameters alone when the gradient norm is inf / NaN
+  bool step_needs_norm(float max_grad_norm, const float* gnorm_dev) const { return max_grad_norm > 0.f || gnorm_dev != nullptr || opt_skip_nonfinite; }
   int sq_layers = 0;
   int n_sq_chunks = 0;
   bool emb_cnt_cleared = false;   // this backward's first launch cleared the embedding gradient's count matrix (gget_backward_begin)
@@ -502,26 +552,19 @@ struct gget_engine {
   bool dp_lds_headroom = false;
   float* comm_f32 = nullptr;
   uint64_t comm_f32_elems = 0;
-  // sharded optimizer step (ZeRO stage 2, gget_shard_init): the plan per bucket, and one device allocation owned by the handle with the
-  // AdamW work items of this rank's share, the norm chunks it sums (+ their slots in the gathered partial vector) and the chunk -> slot map
+  // sharded optimizer step (ZeRO stage 2, gget_shard_init): the plan per bucket and the work list of this rank's share
   int shard_world = 0, shard_rank = 0;   // shard_world 0 = off (the replicated step)
   int shard_slots = 0;                   // partial-vector slots per rank
-  int shard_nitems = 0, shard_nchunks = 0, shard_nglobal = 0;
   std::vector<ShardBucket> shard_plan;
-  unsigned char* shard_tab = nullptr;
-  const GgetSqChunk* shard_items() const { return reinterpret_cast<const GgetSqChunk*>(shard_tab); }
-  const GgetSqChunk* shard_chunks() const { return shard_items() + shard_nitems; }
-  const int32_t* shard_chunk_slot() const { return reinterpret_cast<const int32_t*>(shard_chunks() + shard_nchunks); }
-  const int32_t* shard_slot_of() const { return shard_chunk_slot() + shard_nchunks; }
+  OptWork shard_work;
   // frozen prefix (gget_set_frozen; reference freeze_llama_layers): -1 = everything trains and nothing below is used.  >= 0: embed_tokens
-  // and the layers [0, frozen) are not trained - the trainable element ranges of the flat arenas (at most two), and one device allocation
-  // owned by the handle with the AdamW / EMA work items and the norm chunks that cut them (the item kernels of the sharded step)
+  // and the layers [0, frozen) are not trained - the trainable element ranges of the flat arenas (at most two) and their work list
   int frozen = -1;
   std::vector<std::pair<uint64_t, uint64_t>> train_ranges;   // [offset, count)
-  unsigned char* frozen_tab = nullptr;
-  int frozen_nitems = 0, frozen_nchunks = 0;
-  const GgetSqChunk* frozen_items() const { return reinterpret_cast<const GgetSqChunk*>(frozen_tab); }
-  const GgetSqChunk* frozen_chunks() const { return frozen_items() + frozen_nitems; }
+  OptWork frozen_work;
+  // what a step, or an EMA lerp, runs over: the shard's work list (`sharded`: a plan is active and the caller runs its form), else the
+  // trainable ranges', else none - the whole arena
+  const OptWork* opt_work(bool sharded) const { return sharded ? &shard_work : frozen >= 0 ? &frozen_work : nullptr; }
   // nothing trainable sits upstream of layer 0: the backward stops at the lowest trainable unit (else the full chain runs - the gate /
   // raw-embedding gradients need the dgrad through the frozen layers)
   bool truncated() const { return frozen >= 0 && !plan.has_gate && cfg.embed_dim == 0; }
@@ -677,8 +720,8 @@ extern "C" int gget_create(const gget_config_t* cfg, const gget_buffers_t* bufs,
 extern "C" int gget_comm_destroy(gget_handle_t h);
 extern "C" int gget_destroy(gget_handle_t h) {
   if (h) gget_comm_destroy(h);
-  if (h && h->shard_tab) (void)hipFree(h->shard_tab);
-  if (h && h->frozen_tab) (void)hipFree(h->frozen_tab);
+  if (h) (void)h->shard_work.reset();
+  if (h) (void)h->frozen_work.reset();
   if (h && h->host_word) (void)hipHostFree(h->host_word);
   if (h && h->count_event) (void)hipEventDestroy(h->count_event);
   delete h;
@@ -822,148 +865,6 @@ extern "C" int gget_set_dropout(gget_handle_t h, float attention_p, float path_p
   h->path_drop_p = path_p;
   h->attn_drop_seed = seed;
   return 0;
-}
-
-extern "C" int gget_ema_attach(gget_handle_t h, float* ema_dev) {
-  GGET_REQUIRE(h != nullptr, "ema_attach: null handle");
-  h->ema = ema_dev;
-  h->ema_decay_next = -1.f;
-  if (ema_dev && h->plan.lm_pad_count)    // as gget_create: the pad rows read as zeros whatever the caller's arena held
-    GGET_HIP_CHECK(hipMemset(ema_dev + h->plan.lm_pad_off, 0, h->plan.lm_pad_count * 4));
-  return 0;
-}
-
-extern "C" int gget_grad_acc_attach(gget_handle_t h, float* acc_dev) {
-  GGET_REQUIRE(h != nullptr, "grad_acc_attach: null handle");
-  h->grad_acc = acc_dev;
-  h->grad_acc_count = 0;      // (no window is open: the first gget_grad_accumulate overwrites whatever the arena holds)
-  return 0;
-}
-
-extern "C" int gget_grad_accumulate(gget_handle_t h, void* stream) {
-  GGET_REQUIRE(h != nullptr, "grad_accumulate: null handle");
-  GGET_REQUIRE(h->grad_acc, "grad_accumulate: no accumulator arena (gget_grad_acc_attach)");
-  if (h->frozen >= 0) {      // the trainable ranges only: the frozen share of the accumulator is never written and never read
-    for (const auto& r : h->train_ranges)
-      if (int e = k_grad_accumulate(h->G + r.first, h->grad_acc + r.first, r.second, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
-  } else if (int e = k_grad_accumulate(h->G, h->grad_acc, h->plan.n_params, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
-  ++h->grad_acc_count;
-  return 0;
-}
-
-extern "C" int gget_grad_acc_count(gget_handle_t h, int32_t* out) {
-  GGET_REQUIRE(h != nullptr && out != nullptr, "grad_acc_count: null argument");
-  *out = h->grad_acc_count;
-  return 0;
-}
-
-extern "C" int gget_grad_acc_set_count(gget_handle_t h, int32_t n) {
-  GGET_REQUIRE(h != nullptr, "grad_acc_set_count: null handle");
-  GGET_REQUIRE(n >= 0, "grad_acc_set_count: count %d < 0", (int)n);
-  GGET_REQUIRE(n == 0 || h->grad_acc, "grad_acc_set_count: no accumulator arena (gget_grad_acc_attach)");
-  h->grad_acc_count = n;
-  return 0;
-}
-
-extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* slots_per_rank);
-// the trainable element ranges for `frozen_layers` = k >= 0 with the parameter order of make_plan: [end of embed_tokens, start of layer 0)
-// (gate / raw-embedding parameters; usually empty) and [start of layer min(k, L), n_params); empty ranges are dropped
-static std::vector<std::pair<uint64_t, uint64_t>> frozen_train_ranges(const gget_config_t& c, const Plan& pl, int k) {
-  const int L = c.num_layers;
-  const uint64_t emb_end = pl.emb + align_up((uint64_t)c.vocab_size * c.hidden_size, 128);
-  const uint64_t layer0 = L > 0 ? pl.layers[0].ln1 : pl.normf;
-  const uint64_t from = k < L ? pl.layers[k].ln1 : pl.normf;
-  std::vector<std::pair<uint64_t, uint64_t>> r;
-  if (layer0 > emb_end) r.push_back({emb_end, layer0 - emb_end});
-  if (pl.n_params > from) r.push_back({from, pl.n_params - from});
-  return r;
-}
-
-extern "C" int gget_set_frozen(gget_handle_t h, int frozen_layers) {
-  GGET_REQUIRE(h != nullptr, "set_frozen: null handle");
-  GGET_REQUIRE(frozen_layers >= -1, "set_frozen: %d frozen layers (-1 = none, k >= 0 = embed_tokens and the first k layers)", frozen_layers);
-  GGET_REQUIRE(h->grad_acc_count == 0, "set_frozen: a gradient-accumulation window is open (%d micro-steps summed); step first", h->grad_acc_count);
-  if (h->frozen_tab) GGET_HIP_CHECK(hipFree(h->frozen_tab));
-  h->frozen_tab = nullptr;
-  h->frozen_nitems = h->frozen_nchunks = 0;
-  h->train_ranges.clear();
-  h->frozen = frozen_layers;
-  if (frozen_layers >= 0) {
-    h->train_ranges = frozen_train_ranges(h->cfg, h->plan, std::min(frozen_layers, h->cfg.num_layers));
-    uint64_t total = 0;
-    for (const auto& r : h->train_ranges) total += r.second;
-    // AdamW / EMA work items as the sharded step cuts them, and at most 1024 norm chunks (one block and one partial sum each)
-    const uint64_t chunk = std::max<uint64_t>(32768, align_up((total + 999) / 1000, 128));
-    std::vector<GgetSqChunk> items, chunks;
-    for (const auto& r : h->train_ranges) {
-      for (uint64_t o = 0; o < r.second; o += kAdamwItemElems) items.push_back(GgetSqChunk{r.first + o, std::min<uint64_t>(kAdamwItemElems, r.second - o)});
-      for (uint64_t o = 0; o < r.second; o += chunk) chunks.push_back(GgetSqChunk{r.first + o, std::min(chunk, r.second - o)});
-    }
-    GGET_REQUIRE(chunks.size() <= 1024, "set_frozen: %d norm chunks", (int)chunks.size());
-    if (!items.empty()) {
-      GGET_HIP_CHECK(hipMalloc(&h->frozen_tab, (items.size() + chunks.size()) * sizeof(GgetSqChunk)));
-      h->frozen_nitems = (int)items.size();
-      h->frozen_nchunks = (int)chunks.size();
-      GGET_HIP_CHECK(hipMemcpy((void*)h->frozen_items(), items.data(), items.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
-      GGET_HIP_CHECK(hipMemcpy((void*)h->frozen_chunks(), chunks.data(), chunks.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
-    }
-  }
-  // a shard plan cuts the trainable share of every bucket: built again for the new ranges
-  if (h->shard_world > 0) return gget_shard_init(h, h->shard_world, h->shard_rank, nullptr);
-  return 0;
-}
-
-extern "C" int gget_trainable_ranges(gget_handle_t h, uint64_t out[4], int32_t* n_out) {
-  GGET_REQUIRE(h != nullptr && out != nullptr && n_out != nullptr, "trainable_ranges: null argument");
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (h->frozen < 0) {
-    out[1] = h->plan.n_params;
-    *n_out = 1;
-    return 0;
-  }
-  *n_out = (int32_t)h->train_ranges.size();
-  for (size_t i = 0; i < h->train_ranges.size(); ++i) {
-    out[2 * i] = h->train_ranges[i].first;
-    out[2 * i + 1] = h->train_ranges[i].second;
-  }
-  return 0;
-}
-
-extern "C" int gget_set_ema_decay(gget_handle_t h, float decay) {
-  GGET_REQUIRE(h != nullptr, "set_ema_decay: null handle");
-  GGET_REQUIRE(decay <= 1.f, "set_ema_decay: decay %g > 1", (double)decay);     // (NaN fails the comparison too)
-  GGET_REQUIRE(decay < 0.f || h->ema, "set_ema_decay: no EMA arena (gget_ema_attach)");
-  h->ema_decay_next = decay < 0.f ? -1.f : decay;
-  return 0;
-}
-
-extern "C" int gget_ema_update(gget_handle_t h, float decay, void* stream) {
-  GGET_REQUIRE(h != nullptr, "ema_update: null handle");
-  GGET_REQUIRE(h->ema && h->master, "ema_update: no EMA arena (gget_ema_attach) or no fp32 master arena");
-  GGET_REQUIRE(decay >= 0.f && decay <= 1.f, "ema_update: decay %g outside [0, 1]", (double)decay);
-  // frozen weights are constant: lerp(ema, w) == w there once the arena was seeded, so the average skips them - bit-identical to timm's lerp
-  // over every entry.  decay == 0 IS the seed (ema = master): it also copies the frozen ranges (the complement of the trainable ones)
-  if (h->frozen >= 0 && decay == 0.f) {
-    uint64_t at = 0;
-    for (size_t i = 0; i <= h->train_ranges.size(); ++i) {
-      const uint64_t end = i < h->train_ranges.size() ? h->train_ranges[i].first : h->plan.n_params;
-      if (end > at)
-        if (int e = k_ema_lerp(h->master + at, h->ema + at, end - at, 0.f, (hipStream_t)stream)) return e;
-      if (i < h->train_ranges.size()) at = h->train_ranges[i].first + h->train_ranges[i].second;
-    }
-  }
-  if (h->shard_world > 0)     // this rank's share (body slices + every tail; all of them for the loopback), as the sharded AdamW step
-    return k_ema_lerp_items(h->master, h->ema, h->shard_items(), h->shard_nitems, decay, (hipStream_t)stream);
-  if (h->frozen >= 0)
-    return k_ema_lerp_items(h->master, h->ema, h->frozen_items(), h->frozen_nitems, decay, (hipStream_t)stream);
-  return k_ema_lerp(h->master, h->ema, h->plan.n_params, decay, (hipStream_t)stream);
-}
-
-extern "C" int gget_ema_to_params(gget_handle_t h, void* stream) {
-  GGET_REQUIRE(h != nullptr, "ema_to_params: null handle");
-  GGET_REQUIRE(h->ema, "ema_to_params: no EMA arena (gget_ema_attach)");
-  h->wo_packed = false;      // a parameter write, as gget_sync_params: the per-sample kernels must not keep evaluating the live weights' packed copies
-  return k_f32_to_bf16(h->ema, h->P, h->plan.n_params, (hipStream_t)stream);
 }
 
 extern "C" int gget_sync_params(gget_handle_t h, void* stream) {
@@ -2360,59 +2261,202 @@ extern "C" int gget_backward(gget_handle_t h, float loss_scale, void* stream) {
                             (hipStream_t)stream);
 }
 
+// ================================================================================================
+// optimizer: arenas, gradient accumulation, frozen prefix, weight EMA, the step, the sharded step (ZeRO stage 2; reference: DeepSpeed
+// zero_optimization.stage 2, examples/ds_config2_pt.json:29-32, engine built at src/training/pretrain_mode.py:281-287)
+// ================================================================================================
+extern "C" int gget_ema_attach(gget_handle_t h, float* ema_dev) {
+  GGET_REQUIRE(h != nullptr, "ema_attach: null handle");
+  h->ema = ema_dev;
+  h->ema_decay_next = -1.f;
+  if (ema_dev && h->plan.lm_pad_count)    // as gget_create: the pad rows read as zeros whatever the caller's arena held
+    GGET_HIP_CHECK(hipMemset(ema_dev + h->plan.lm_pad_off, 0, h->plan.lm_pad_count * 4));
+  return 0;
+}
+
+extern "C" int gget_grad_acc_attach(gget_handle_t h, float* acc_dev) {
+  GGET_REQUIRE(h != nullptr, "grad_acc_attach: null handle");
+  h->grad_acc = acc_dev;
+  h->grad_acc_count = 0;      // (no window is open: the first gget_grad_accumulate overwrites whatever the arena holds)
+  return 0;
+}
+
+extern "C" int gget_grad_accumulate(gget_handle_t h, void* stream) {
+  GGET_REQUIRE(h != nullptr, "grad_accumulate: null handle");
+  GGET_REQUIRE(h->grad_acc, "grad_accumulate: no accumulator arena (gget_grad_acc_attach)");
+  if (h->frozen >= 0) {      // the trainable ranges only (every rank's: the exchange follows): the frozen share is never written and never read
+    for (const auto& r : h->train_ranges)
+      if (int e = k_grad_accumulate(h->G + r.first, h->grad_acc + r.first, r.second, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
+  } else if (int e = k_grad_accumulate(h->G, h->grad_acc, h->plan.n_params, h->grad_acc_count == 0, (hipStream_t)stream)) return e;
+  ++h->grad_acc_count;
+  return 0;
+}
+
+extern "C" int gget_grad_acc_count(gget_handle_t h, int32_t* out) {
+  GGET_REQUIRE(h != nullptr && out != nullptr, "grad_acc_count: null argument");
+  *out = h->grad_acc_count;
+  return 0;
+}
+
+extern "C" int gget_grad_acc_set_count(gget_handle_t h, int32_t n) {
+  GGET_REQUIRE(h != nullptr, "grad_acc_set_count: null handle");
+  GGET_REQUIRE(n >= 0, "grad_acc_set_count: count %d < 0", (int)n);
+  GGET_REQUIRE(n == 0 || h->grad_acc, "grad_acc_set_count: no accumulator arena (gget_grad_acc_attach)");
+  h->grad_acc_count = n;
+  return 0;
+}
+
+// the trainable element ranges for `frozen_layers` = k >= 0 with the parameter order of make_plan: [end of embed_tokens, start of layer 0)
+// (gate / raw-embedding parameters; usually empty) and [start of layer min(k, L), n_params); empty ranges are dropped
+static std::vector<std::pair<uint64_t, uint64_t>> frozen_train_ranges(const gget_config_t& c, const Plan& pl, int k) {
+  const int L = c.num_layers;
+  const uint64_t emb_end = pl.emb + align_up((uint64_t)c.vocab_size * c.hidden_size, 128);
+  const uint64_t layer0 = L > 0 ? pl.layers[0].ln1 : pl.normf;
+  const uint64_t from = k < L ? pl.layers[k].ln1 : pl.normf;
+  std::vector<std::pair<uint64_t, uint64_t>> r;
+  if (layer0 > emb_end) r.push_back({emb_end, layer0 - emb_end});
+  if (pl.n_params > from) r.push_back({from, pl.n_params - from});
+  return r;
+}
+
+extern "C" int gget_set_frozen(gget_handle_t h, int frozen_layers) {
+  GGET_REQUIRE(h != nullptr, "set_frozen: null handle");
+  GGET_REQUIRE(frozen_layers >= -1, "set_frozen: %d frozen layers (-1 = none, k >= 0 = embed_tokens and the first k layers)", frozen_layers);
+  GGET_REQUIRE(h->grad_acc_count == 0, "set_frozen: a gradient-accumulation window is open (%d micro-steps summed); step first", h->grad_acc_count);
+  if (int e = h->frozen_work.reset()) return e;
+  h->train_ranges.clear();
+  h->frozen = frozen_layers;
+  if (frozen_layers >= 0) {
+    h->train_ranges = frozen_train_ranges(h->cfg, h->plan, std::min(frozen_layers, h->cfg.num_layers));
+    uint64_t total = 0;
+    for (const auto& r : h->train_ranges) total += r.second;
+    // at most 1024 norm chunks (one block and one partial sum each)
+    const uint64_t chunk = std::max<uint64_t>(32768, align_up((total + 999) / 1000, 128));
+    std::vector<GgetSqChunk> chunks;
+    for (const auto& r : h->train_ranges)
+      for (uint64_t o = 0; o < r.second; o += chunk) chunks.push_back(GgetSqChunk{r.first + o, std::min(chunk, r.second - o)});
+    GGET_REQUIRE(chunks.size() <= 1024, "set_frozen: %d norm chunks", (int)chunks.size());
+    if (int e = h->frozen_work.upload(cut_items(h->train_ranges), chunks)) return e;
+  }
+  // a shard plan cuts the trainable share of every bucket: built again for the new ranges
+  if (h->shard_world > 0) return gget_shard_init(h, h->shard_world, h->shard_rank, nullptr);
+  return 0;
+}
+
+extern "C" int gget_trainable_ranges(gget_handle_t h, uint64_t out[4], int32_t* n_out) {
+  GGET_REQUIRE(h != nullptr && out != nullptr && n_out != nullptr, "trainable_ranges: null argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (h->frozen < 0) {
+    out[1] = h->plan.n_params;
+    *n_out = 1;
+    return 0;
+  }
+  *n_out = (int32_t)h->train_ranges.size();
+  for (size_t i = 0; i < h->train_ranges.size(); ++i) {
+    out[2 * i] = h->train_ranges[i].first;
+    out[2 * i + 1] = h->train_ranges[i].second;
+  }
+  return 0;
+}
+
+extern "C" int gget_bucket_train_range(gget_handle_t h, int bucket, uint64_t* offset, uint64_t* count) {
+  GGET_REQUIRE(h != nullptr && offset != nullptr && count != nullptr, "bucket_train_range: null argument");
+  GGET_REQUIRE(bucket >= 0 && bucket < (int)h->bucket_range.size(), "bucket_train_range: bucket %d out of range", bucket);
+  const auto r = h->bucket_train_range(bucket);
+  *offset = r.first;
+  *count = r.second;
+  return 0;
+}
+
+extern "C" int gget_set_ema_decay(gget_handle_t h, float decay) {
+  GGET_REQUIRE(h != nullptr, "set_ema_decay: null handle");
+  GGET_REQUIRE(decay <= 1.f, "set_ema_decay: decay %g > 1", (double)decay);     // (NaN fails the comparison too)
+  GGET_REQUIRE(decay < 0.f || h->ema, "set_ema_decay: no EMA arena (gget_ema_attach)");
+  h->ema_decay_next = decay < 0.f ? -1.f : decay;
+  return 0;
+}
+
+extern "C" int gget_ema_update(gget_handle_t h, float decay, void* stream) {
+  GGET_REQUIRE(h != nullptr, "ema_update: null handle");
+  GGET_REQUIRE(h->ema && h->master, "ema_update: no EMA arena (gget_ema_attach) or no fp32 master arena");
+  GGET_REQUIRE(decay >= 0.f && decay <= 1.f, "ema_update: decay %g outside [0, 1]", (double)decay);
+  // frozen weights are constant: lerp(ema, w) == w there once the arena was seeded, so the average skips them - bit-identical to timm's lerp
+  // over every entry.  decay == 0 IS the seed (ema = master): it also copies the frozen ranges (the complement of the trainable ones)
+  if (h->frozen >= 0 && decay == 0.f) {
+    uint64_t at = 0;
+    for (size_t i = 0; i <= h->train_ranges.size(); ++i) {
+      const uint64_t end = i < h->train_ranges.size() ? h->train_ranges[i].first : h->plan.n_params;
+      if (end > at)
+        if (int e = k_ema_lerp(h->master + at, h->ema + at, end - at, 0.f, (hipStream_t)stream)) return e;
+      if (i < h->train_ranges.size()) at = h->train_ranges[i].first + h->train_ranges[i].second;
+    }
+  }
+  // a shard plan: this rank's share (body slices + every tail; all of them for the loopback), as the sharded AdamW step
+  if (const OptWork* w = h->opt_work(h->shard_world > 0)) return k_ema_lerp_items(h->master, h->ema, w->items, w->nitems, decay, (hipStream_t)stream);
+  return k_ema_lerp(h->master, h->ema, h->plan.n_params, decay, (hipStream_t)stream);
+}
+
+extern "C" int gget_ema_to_params(gget_handle_t h, void* stream) {
+  GGET_REQUIRE(h != nullptr, "ema_to_params: null handle");
+  GGET_REQUIRE(h->ema, "ema_to_params: no EMA arena (gget_ema_attach)");
+  h->wo_packed = false;      // a parameter write, as gget_sync_params: the per-sample kernels must not keep evaluating the live weights' packed copies
+  return k_f32_to_bf16(h->ema, h->P, h->plan.n_params, (hipStream_t)stream);
+}
+
+// norm + clip + AdamW (+ EMA) of one step, the body of both entry points.  sharded: over the plan's work list, the norm from the gathered
+// partial vector slots_dev; else over the trainable ranges of a frozen model, or the whole arena
+static int optimizer_step(gget_engine* h, bool sharded, float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
+                          float grad_scale, int step, const float* slots_dev, float* gnorm_dev, hipStream_t st) {
+  GgetAdamwArgs a{};
+  a.master = h->master, a.m = h->am, a.v = h->av, a.param = h->P;
+  a.lr = lr, a.beta1 = beta1, a.beta2 = beta2, a.eps = eps, a.wd = weight_decay, a.step = step;
+  a.max_norm = max_grad_norm, a.grad_scale = grad_scale, a.gnorm_out = gnorm_dev, a.skip_nonfinite = h->opt_skip_nonfinite;
+  a.ema_decay = h->ema_decay_next;      // (gget_set_ema_decay: consumed by this call)
+  h->ema_decay_next = -1.f;
+  a.ema = a.ema_decay >= 0.f ? h->ema : nullptr;
+  h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies - the sharded step's from the gathered weights)
+  float* sq = h->wsp<float>(h->ws.sqnorm);
+  const bool need_norm = h->step_needs_norm(max_grad_norm, gnorm_dev);
+  a.sqnorm = need_norm ? sq : nullptr;
+  // an open accumulation window (gget_grad_accumulate): norm, clip, skip rule and update read the fp32 sum, and this call closes the window
+  // whether or not the skip rule drops the update (GradScaler drops the whole update, not one micro-batch of it)
+  a.grad_f32 = h->grad_from_acc();
+  a.grad = h->grad_src();
+  h->grad_acc_count = 0;
+  const OptWork* w = h->opt_work(sharded);
+  if (need_norm) {
+    if (sharded) {
+      if (int e = k_grad_sqnorm_slots(slots_dev, w->slot_of, w->nglobal, sq, st)) return e;
+    } else if (w) {
+      // frozen prefix: a plain chunk pass over the trainable ranges (GGET_OPT_NORM_FROM_BACKWARD falls back to it)
+      if (int e = k_grad_sqnorm_chunks(a.grad, w->chunks, w->nchunks, nullptr, 0, sq, st, a.grad_f32)) return e;
+    } else if (h->opt_norm_from_backward && !a.grad_f32 && grad_scale == 1.0f && h->sq_layers == h->cfg.num_layers && h->n_sq_chunks >= 0) {
+      // the shortcut holds only while the gradient array is exactly what the last backward wrote: the caller promised that
+      // (GGET_OPT_NORM_FROM_BACKWARD), grad_scale != 1 means an exchange happened anyway, and every layer must have left its partials;
+      // the partials of the last backward say nothing about a sum of several (grad_f32: the full pass over the accumulator)
+      if (int e = k_grad_sqnorm_chunks(h->G, h->wsp<GgetSqChunk>(h->ws.sq_chunks), h->n_sq_chunks, h->wsp<float>(h->ws.sq_tiles),
+                                       h->cfg.num_layers * kSqTilesPerLayer, sq, st))
+        return e;
+    } else if (int e = k_grad_sqnorm(a.grad, h->plan.n_params, sq, st, a.grad_f32)) return e;
+  }
+  // the item kernels share the per-element update with the grid-stride one: the same bits per element, given the same coefficient
+  return w ? k_adamw_items(a, w->items, w->nitems, st) : k_adamw(a, h->plan.n_params, st);
+}
+
 extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay,
                                float max_grad_norm, float grad_scale, int step, float* gnorm_dev, void* stream) {
   GGET_REQUIRE(h && h->master && h->am && h->av, "adamw needs master/m/v arenas");
   GGET_REQUIRE(step >= 1, "step is 1-based");
-  hipStream_t st = (hipStream_t)stream;
-  const float ema_decay = h->ema_decay_next;      // (gget_set_ema_decay: consumed by this call)
-  h->ema_decay_next = -1.f;
-  float* ema = ema_decay >= 0.f ? h->ema : nullptr;
-  h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies)
-  float* sq = h->wsp<float>(h->ws.sqnorm);
-  const bool need_norm = max_grad_norm > 0.f || gnorm_dev != nullptr || h->opt_skip_nonfinite;
-  // an open accumulation window (gget_grad_accumulate): norm, clip, skip rule and update read the fp32 sum, and this call closes the window
-  // whether or not the skip rule drops the update (GradScaler drops the whole update, not one micro-batch of it)
-  const bool from_acc = h->grad_from_acc();
-  const void* grad = h->grad_src();
-  h->grad_acc_count = 0;
-  if (h->frozen >= 0) {
-    // frozen prefix: norm, clip, update and EMA over the trainable ranges only, through the chunk / item kernels of the sharded step
-    // (one update function: the same bits per element).  GGET_OPT_NORM_FROM_BACKWARD falls back to this plain pass.
-    if (need_norm)
-      if (int e = k_grad_sqnorm_chunks(grad, h->frozen_chunks(), h->frozen_nchunks, nullptr, 0, sq, st, from_acc)) return e;
-    return k_adamw_items(h->master, h->am, h->av, grad, h->P, h->frozen_items(), h->frozen_nitems, lr, beta1, beta2, eps, weight_decay, step,
-                         max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay, from_acc);
-  }
-  if (need_norm) {
-    // the shortcut holds only while the gradient array is exactly what the last backward wrote: the caller promised that
-    // (GGET_OPT_NORM_FROM_BACKWARD), grad_scale != 1 means an exchange happened anyway, and every layer must have left its partials;
-    // the partials of the last backward say nothing about a sum of several (from_acc: the full pass over the accumulator)
-    if (h->opt_norm_from_backward && !from_acc && grad_scale == 1.0f && h->sq_layers == h->cfg.num_layers && h->n_sq_chunks >= 0) {
-      if (int e = k_grad_sqnorm_chunks(h->G, h->wsp<GgetSqChunk>(h->ws.sq_chunks), h->n_sq_chunks, h->wsp<float>(h->ws.sq_tiles),
-                                       h->cfg.num_layers * kSqTilesPerLayer, sq, st))
-        return e;
-    } else if (int e = k_grad_sqnorm(grad, h->plan.n_params, sq, st, from_acc)) return e;
-  }
-  return k_adamw(h->master, h->am, h->av, grad, h->P, h->plan.n_params, lr, beta1, beta2, eps, weight_decay, step,
-                 max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay, from_acc);
+  return optimizer_step(h, false, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale, step, nullptr, gnorm_dev, (hipStream_t)stream);
 }
 
-// ================================================================================================
-// sharded optimizer step (ZeRO stage 2; reference: DeepSpeed zero_optimization.stage 2, examples/ds_config2_pt.json:29-32, engine built at
-// src/training/pretrain_mode.py:281-287)
-// ================================================================================================
 extern "C" int gget_shard_plan(const gget_config_t* cfg, int world, int bucket, uint64_t out[5]) {
   if (int e = check_cfg(cfg)) return e;
   GGET_REQUIRE(out && world >= 1, "shard_plan: bad arguments (world %d)", world);
   GGET_REQUIRE(bucket >= 0 && bucket < cfg->num_layers + 2, "shard_plan: bucket %d out of range", bucket);
   const auto r = bucket_ranges(*cfg, make_plan(*cfg))[bucket];
   const ShardBucket sb = shard_bucket(r.first, r.second - r.first, world);
-  out[0] = sb.off;
-  out[1] = sb.cnt;
-  out[2] = sb.slice;
-  out[3] = sb.tail_off;
-  out[4] = sb.tail_cnt;
+  out[0] = sb.off, out[1] = sb.cnt, out[2] = sb.slice, out[3] = sb.tail_off, out[4] = sb.tail_cnt;
   return 0;
 }
 
@@ -2420,9 +2464,8 @@ extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* sl
   GGET_REQUIRE(h && world >= 0 && (world == 0 || (rank >= 0 && rank < world)), "shard_init: bad arguments (rank %d world %d)", rank, world);
   GGET_REQUIRE(world == 0 || !(h->comm || h->comm_loopback) || (world == h->comm_world && rank == h->comm_rank),
                "shard_init: rank %d of %d does not match the communicator (rank %d of %d)", rank, world, h->comm_rank, h->comm_world);
-  if (h->shard_tab) GGET_HIP_CHECK(hipFree(h->shard_tab));
-  h->shard_tab = nullptr;
-  h->shard_world = h->shard_rank = h->shard_slots = h->shard_nitems = h->shard_nchunks = h->shard_nglobal = 0;
+  if (int e = h->shard_work.reset()) return e;
+  h->shard_world = h->shard_rank = h->shard_slots = 0;
   h->shard_plan.clear();
   if (slots_per_rank) *slots_per_rank = 0;
   if (world == 0) return 0;
@@ -2458,24 +2501,13 @@ extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* sl
     }
   }
   // AdamW work items: this rank's body slice of every bucket (all of them for the loopback) and every tail
-  std::vector<GgetSqChunk> items;
-  auto cut = [&](uint64_t off, uint64_t cnt) {
-    for (uint64_t o = 0; o < cnt; o += kAdamwItemElems) items.push_back(GgetSqChunk{off + o, std::min<uint64_t>(kAdamwItemElems, cnt - o)});
-  };
+  std::vector<std::pair<uint64_t, uint64_t>> share;
   for (const ShardBucket& b : plan) {
     for (int r = 0; r < world; ++r)
-      if (all_ranks || r == rank) cut(b.off + (uint64_t)r * b.slice, b.slice);
-    cut(b.tail_off, b.tail_cnt);
+      if (all_ranks || r == rank) share.push_back({b.off + (uint64_t)r * b.slice, b.slice});
+    share.push_back({b.tail_off, b.tail_cnt});
   }
-  const size_t bytes = (items.size() + chunks.size()) * sizeof(GgetSqChunk) + (chunks.size() + slot_of.size()) * sizeof(int32_t);
-  GGET_HIP_CHECK(hipMalloc(&h->shard_tab, bytes));
-  h->shard_nitems = (int)items.size();
-  h->shard_nchunks = (int)chunks.size();
-  h->shard_nglobal = (int)slot_of.size();
-  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_items(), items.data(), items.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
-  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_chunks(), chunks.data(), chunks.size() * sizeof(GgetSqChunk), hipMemcpyHostToDevice));
-  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_chunk_slot(), chunk_slot.data(), chunk_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  GGET_HIP_CHECK(hipMemcpy((void*)h->shard_slot_of(), slot_of.data(), slot_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (int e = h->shard_work.upload(cut_items(share), chunks, chunk_slot, slot_of)) return e;
   h->shard_world = world;
   h->shard_rank = rank;
   h->shard_slots = S;
@@ -2484,11 +2516,20 @@ extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* sl
   return 0;
 }
 
+extern "C" int gget_shard_bucket(gget_handle_t h, int bucket, uint64_t out[5]) {
+  GGET_REQUIRE(h != nullptr && out != nullptr, "shard_bucket: null argument");
+  GGET_REQUIRE(h->shard_world > 0, "shard_bucket: no plan is active (gget_shard_init)");
+  GGET_REQUIRE(bucket >= 0 && bucket < (int)h->shard_plan.size(), "shard_bucket: bucket %d out of range", bucket);
+  const ShardBucket& sb = h->shard_plan[bucket];
+  out[0] = sb.off, out[1] = sb.cnt, out[2] = sb.slice, out[3] = sb.tail_off, out[4] = sb.tail_cnt;
+  return 0;
+}
+
 extern "C" int gget_shard_sqnorm_partials(gget_handle_t h, float* slots_dev, void* stream) {
   GGET_REQUIRE(h && h->shard_world > 0 && slots_dev, "shard_sqnorm_partials: call gget_shard_init first (and pass the slot vector)");
   // (an open accumulation window: the chunks of the fp32 sum; the window stays open for gget_adamw_step_sharded, which closes it)
-  return k_grad_sqnorm_partials(h->grad_src(), h->shard_chunks(), h->shard_chunk_slot(), h->shard_nchunks, slots_dev, (hipStream_t)stream,
-                                h->grad_from_acc());
+  const OptWork& w = h->shard_work;
+  return k_grad_sqnorm_partials(h->grad_src(), w.chunks, w.chunk_slot, w.nchunks, slots_dev, (hipStream_t)stream, h->grad_from_acc());
 }
 
 extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -2496,22 +2537,8 @@ extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, f
   GGET_REQUIRE(h && h->master && h->am && h->av, "adamw needs master/m/v arenas");
   GGET_REQUIRE(h->shard_world > 0, "adamw_step_sharded: call gget_shard_init first");
   GGET_REQUIRE(step >= 1, "step is 1-based");
-  hipStream_t st = (hipStream_t)stream;
-  const float ema_decay = h->ema_decay_next;      // (gget_set_ema_decay: consumed by this call)
-  h->ema_decay_next = -1.f;
-  float* ema = ema_decay >= 0.f ? h->ema : nullptr;
-  h->wo_packed = false;      // (see gget_sync_params; the next forward rebuilds the copies from the gathered weights)
-  float* sq = h->wsp<float>(h->ws.sqnorm);
-  const bool need_norm = max_grad_norm > 0.f || gnorm_dev != nullptr || h->opt_skip_nonfinite;
-  if (need_norm) {
-    GGET_REQUIRE(slots_dev, "adamw_step_sharded: the norm needs the gathered partial vector");
-    if (int e = k_grad_sqnorm_slots(slots_dev, h->shard_slot_of(), h->shard_nglobal, sq, st)) return e;
-  }
-  const bool from_acc = h->grad_from_acc();       // (as gget_adamw_step: this rank's share of the fp32 sum, and the window closes)
-  const void* grad = h->grad_src();
-  h->grad_acc_count = 0;
-  return k_adamw_items(h->master, h->am, h->av, grad, h->P, h->shard_items(), h->shard_nitems, lr, beta1, beta2, eps, weight_decay, step,
-                       max_grad_norm, grad_scale, need_norm ? sq : nullptr, gnorm_dev, st, h->opt_skip_nonfinite, ema, ema_decay, from_acc);
+  GGET_REQUIRE(slots_dev || !h->step_needs_norm(max_grad_norm, gnorm_dev), "adamw_step_sharded: the norm needs the gathered partial vector");
+  return optimizer_step(h, true, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale, step, slots_dev, gnorm_dev, (hipStream_t)stream);
 }
 
 extern "C" int gget_head_counts(gget_handle_t h, int32_t counts[2], void* stream) {

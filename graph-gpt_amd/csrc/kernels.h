@@ -115,7 +115,7 @@ int k_task_loss(const float* logits, const void* labels, const float* sample_wgt
 int k_score_bwd(const float* dlogits, const void* hidden, const int32_t* pool_row, const void* w, float* dw, float* dbias,
                 void* dhidden, int B, int C, int d, hipStream_t st);
 // ws: k_grad_sqnorm_ws_bytes() of scratch; ws[0] receives sum(g^2) (deterministic reduction order, two launches)
-// grad_f32 (here, k_grad_sqnorm_partials and both AdamW launches): g is the fp32 accumulator of a gradient-accumulation window
+// grad_f32 (here, the chunk passes and both AdamW launches): g is the fp32 accumulator of a gradient-accumulation window
 // (k_grad_accumulate) instead of the bf16 gradient array - the same kernels instantiated on the other element type, only the load differs
 int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st, bool grad_f32 = false);
 inline size_t k_grad_sqnorm_ws_bytes() { return (16 + 1024) * sizeof(float); }
@@ -124,28 +124,40 @@ inline size_t k_grad_sqnorm_ws_bytes() { return (16 + 1024) * sizeof(float); }
 struct GgetSqChunk { uint64_t off; uint64_t cnt; };
 int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st,
                          bool grad_f32 = false);
-// sharded step (ZeRO-2, engine.hip gget_shard_*): per-chunk sums into out[slot[c]]; the one-block sum of the gathered partials in global chunk
-// order (ws[0]); AdamW over work items of <= kAdamwItemElems elements (offsets / counts multiples of 4, one block each)
-constexpr int kAdamwItemElems = 2048;
+// its chunk pass alone, the sharded step's (ZeRO-2, engine.hip gget_shard_*): per-chunk sums into out[slot[c]] (slot == nullptr: out[c]),
+// any number of chunks, no finishing pass - that is the one-block sum of the gathered partials in global chunk order (ws[0])
 int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st,
                            bool grad_f32 = false);
 int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, float* ws, hipStream_t st);
-// ema != nullptr (both AdamW launches): the weight EMA fused into the update - ema' = w' + ema_decay * (ema - w') against the NEW weights,
-// or against the unchanged ones when the skip rule drops the step
-int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
-                  float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
-                  float* gnorm_out, hipStream_t st, bool skip_nonfinite, float* ema = nullptr, float ema_decay = 0.f, bool grad_f32 = false);
-int k_adamw(float* master, float* m, float* v, const void* grad, void* param, size_t n, float lr, float beta1, float beta2,
-            float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm, float* gnorm_out,
-            hipStream_t st, bool skip_nonfinite = false,   // skip_nonfinite: leave everything untouched when the gradient norm is inf / NaN
-            float* ema = nullptr, float ema_decay = 0.f, bool grad_f32 = false);
+// One clip + AdamW launch.  sqnorm: the norm pass's ws (nullptr = no norm: no clip, no skip rule, gnorm_out untouched); skip_nonfinite:
+// leave everything untouched when the gradient norm is inf / NaN.  ema != nullptr: the weight EMA fused into the update -
+// ema' = w' + ema_decay * (ema - w') against the NEW weights, or against the unchanged ones when the skip rule drops the step.
+struct GgetAdamwArgs {
+  float *master, *m, *v;
+  const void* grad;          // bf16, or fp32 when grad_f32
+  bool grad_f32;
+  void* param;               // the bf16 compute copy
+  float lr, beta1, beta2, eps, wd;
+  int step;                  // 1-based
+  float max_norm, grad_scale;
+  const float* sqnorm;
+  float* gnorm_out;
+  bool skip_nonfinite;
+  float* ema;
+  float ema_decay;
+};
+// grid-stride over the first n elements of the arenas (n a multiple of 4) ...
+int k_adamw(const GgetAdamwArgs& a, size_t n, hipStream_t st);
+// ... or over work items of <= kAdamwItemElems elements (offsets / counts multiples of 4, one block each)
+constexpr int kAdamwItemElems = 2048;
+int k_adamw_items(const GgetAdamwArgs& a, const GgetSqChunk* items_dev, int nitems, hipStream_t st);
 // gradient accumulation (reference: DeepSpeed's fp32 accumulation behind gradient_accumulation_steps, conf_utils.py:59-66):
 // acc[i] = (first ? 0 : acc[i]) + float(grad_bf16[i]) over the whole flat array (n a multiple of 8); 6 B per parameter when `first`, else 10
 int k_grad_accumulate(const void* grad, float* acc, size_t n, bool first, hipStream_t st);
 // weight EMA, stand-alone (reference: timm ModelEmaV3.update through src/utils/patch_utils.py:10-39).  THE formula, here and fused into
 // AdamW (one device function, kernels.hip ema_lerp4):  ema' = w + d * (ema - w)  in fp32 - fmaf(d, ema - w, w), d the fp32 decay exactly as
 // it crossed the ABI.  d = 0 gives ema' == w bit for bit (the arena is seeded that way); no 1 - d is formed (float32(0.9999) is off by up
-// to 3e-8 = 3e-4 of 1 - d).  n a multiple of 4; the items variant runs over a shard plan's work items.
+// to 3e-8 = 3e-4 of 1 - d).  n a multiple of 4; the items variant runs over the same work items as k_adamw_items.
 int k_ema_lerp(const float* master, float* ema, size_t n, float d, hipStream_t st);
 int k_ema_lerp_items(const float* master, float* ema, const GgetSqChunk* items_dev, int nitems, float d, hipStream_t st);
 constexpr int kZeroRanges = 6;

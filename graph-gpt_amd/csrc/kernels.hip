@@ -1752,18 +1752,6 @@ __global__ void __launch_bounds__(kBlock) grad_sqnorm_kernel(const GT* __restric
     ws[16 + blockIdx.x] = t;
   }
 }
-__global__ void __launch_bounds__(kBlock) grad_sqnorm_final_kernel(float* __restrict__ ws, int nblocks) {
-  __shared__ float part[kBlock];
-  float t = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += kBlock) t += ws[16 + i];
-  part[threadIdx.x] = t;
-  __syncthreads();
-  for (int o = kBlock / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) ws[0] = part[0];
-}
 
 // one block per chunk (see k_grad_sqnorm_chunks): out[slot ? slot[chunk] : chunk] = sum of squares of the chunk
 template <typename GT>
@@ -1913,36 +1901,20 @@ __device__ __forceinline__ void adamw_update4(float* __restrict__ master, float*
   if (EMA) ema_lerp4(ema, i, wp, ema_decay);
 }
 
-template <int UNR, typename GT>
+// EMA: the same launch with the weight EMA fused in - one more fp32 arena read and written (28 -> 36 B per parameter).  A step the skip
+// rule drops still averages - against the unchanged master weights (the reference calls update_ema after every batch whether or not the
+// optimizer stepped, src/training/finetune_mode.py:405-413); the decision is uniform over the launch.  Without EMA a dropped step returns
+// at once and `ema` / `ema_decay` are never read: the instantiation is the kernel as it was before the EMA existed.
+template <int UNR, typename GT, bool EMA>
 __global__ void __launch_bounds__(kBlock) adamw_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
                                                        const GT* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
                                                        float lr, float beta1, float beta2, float eps, float wd, float bc1,
                                                        float bc2_sqrt, float max_norm, float grad_scale,
-                                                       const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
-  float coef;
-  if (!adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef)) return;
-  const size_t nv = n >> 2;
-  const size_t stride = (size_t)gridDim.x * kBlock;
-  for (size_t i0 = (size_t)blockIdx.x * kBlock + threadIdx.x; i0 < nv; i0 += stride * UNR)
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) {
-    const size_t i = i0 + u * stride;
-    if (i >= nv) break;
-    adamw_update4<false>(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, nullptr, 0.f);
-  }
-}
-// the same launch with the weight EMA fused in: one more fp32 arena read and written (28 -> 36 B per parameter).  A step the skip rule
-// drops still averages - against the unchanged master weights (the reference calls update_ema after every batch whether or not the
-// optimizer stepped, src/training/finetune_mode.py:405-413); the decision is uniform over the launch
-template <int UNR, typename GT>
-__global__ void __launch_bounds__(kBlock) adamw_ema_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                           const GT* __restrict__ grad, bf16_t* __restrict__ param, size_t n,
-                                                           float lr, float beta1, float beta2, float eps, float wd, float bc1,
-                                                           float bc2_sqrt, float max_norm, float grad_scale,
-                                                           const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite,
-                                                           float* __restrict__ ema, float ema_decay) {
+                                                       const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite,
+                                                       float* __restrict__ ema, float ema_decay) {
   float coef;
   const bool go = adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef);
+  if (!EMA && !go) return;
   const size_t nv = n >> 2;
   const size_t stride = (size_t)gridDim.x * kBlock;
   for (size_t i0 = (size_t)blockIdx.x * kBlock + threadIdx.x; i0 < nv; i0 += stride * UNR)
@@ -1950,48 +1922,36 @@ __global__ void __launch_bounds__(kBlock) adamw_ema_kernel(float* __restrict__ m
   for (int u = 0; u < UNR; ++u) {
     const size_t i = i0 + u * stride;
     if (i >= nv) break;
-    if (go) adamw_update4<true>(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, ema, ema_decay);
+    if (!EMA || go) adamw_update4<EMA>(master, m_, v_, grad, param, i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, ema, ema_decay);
     else ema_update4(master, ema, i, ema_decay);
   }
 }
 
-// sharded step (ZeRO-2): the same update over a list of work items (element ranges of <= kAdamwItemElems elements, offsets and counts multiples
-// of 4) that cut the rank's body slices and the replicated tails - one launch, one block per item, every thread two float4 groups
+// The same update over a list of work items (element ranges of <= kAdamwItemElems elements, offsets and counts multiples of 4): the
+// trainable ranges of a frozen model, or a rank's body slices and the replicated tails of the sharded step (ZeRO-2) - one launch, one block
+// per item, every thread two float4 groups
 static_assert(kAdamwItemElems == kBlock * 8, "an AdamW work item is two float4 groups per thread");
-template <typename GT>
+template <typename GT, bool EMA>
 __global__ void __launch_bounds__(kBlock) adamw_items_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
                                                              const GT* __restrict__ grad, bf16_t* __restrict__ param,
                                                              const GgetSqChunk* __restrict__ items, float lr, float beta1, float beta2,
                                                              float eps, float wd, float bc1, float bc2_sqrt, float max_norm, float grad_scale,
-                                                             const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite) {
-  float coef;
-  if (!adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef)) return;
-  const GgetSqChunk it = items[blockIdx.x];
-  const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
-  for (size_t i = threadIdx.x; i < nv; i += kBlock)
-    adamw_update4<false>(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, nullptr, 0.f);
-}
-template <typename GT>
-__global__ void __launch_bounds__(kBlock) adamw_items_ema_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
-                                                                 const GT* __restrict__ grad, bf16_t* __restrict__ param,
-                                                                 const GgetSqChunk* __restrict__ items, float lr, float beta1, float beta2,
-                                                                 float eps, float wd, float bc1, float bc2_sqrt, float max_norm,
-                                                                 float grad_scale, const float* __restrict__ sqnorm,
-                                                                 float* __restrict__ gnorm_out, int skip_nonfinite, float* __restrict__ ema,
-                                                                 float ema_decay) {
+                                                             const float* __restrict__ sqnorm, float* __restrict__ gnorm_out, int skip_nonfinite,
+                                                             float* __restrict__ ema, float ema_decay) {
   float coef;
   const bool go = adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef);
+  if (!EMA && !go) return;
   const GgetSqChunk it = items[blockIdx.x];
   const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
   for (size_t i = threadIdx.x; i < nv; i += kBlock) {
-    if (go) adamw_update4<true>(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, ema, ema_decay);
-    else ema_update4(master, ema, v0 + i, ema_decay);      // (a skipped step still averages: adamw_ema_kernel)
+    if (!EMA || go) adamw_update4<EMA>(master, m_, v_, grad, param, v0 + i, coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, ema, ema_decay);
+    else ema_update4(master, ema, v0 + i, ema_decay);
   }
 }
 
 // the stand-alone EMA lerp (12 B per parameter: master and ema read, ema written), needed where the reference averages although no AdamW
 // launch runs - the non-boundary micro-steps of a gradient accumulation, seeding (d = 0: ema = master, bit for bit) - in the form of
-// adamw_kernel<2>, and over the work items of a shard plan
+// adamw_kernel<2>, and over the work items of a frozen model or a shard plan
 template <int UNR>
 __global__ void __launch_bounds__(kBlock) ema_lerp_kernel(const float* __restrict__ master, float* __restrict__ ema, size_t n, float d) {
   const size_t nv = n >> 2;
@@ -3106,49 +3066,72 @@ int k_grad_sqnorm(const void* g, size_t n, float* ws, hipStream_t st, bool grad_
     hipLaunchKernelGGL(grad_sqnorm_kernel<float>, dim3(blocks), dim3(kBlock), 0, st, (const float*)g, n, ws);
   else
     hipLaunchKernelGGL(grad_sqnorm_kernel<bf16_t>, dim3(blocks), dim3(kBlock), 0, st, (const bf16_t*)g, n, ws);
-  hipLaunchKernelGGL(grad_sqnorm_final_kernel, dim3(1), dim3(kBlock), 0, st, ws, blocks);
+  hipLaunchKernelGGL(grad_sqnorm_final2_kernel, dim3(1), dim3(kBlock), 0, st, ws, blocks, (const float*)nullptr, 0);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st,
+                           bool grad_f32) {
+  if (nchunks <= 0) return 0;
+  if (grad_f32)
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<float>, dim3(nchunks), dim3(kBlock), 0, st, (const float*)g, chunks_dev, out, slot_dev);
+  else
+    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<bf16_t>, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, out, slot_dev);
   GGET_LAUNCH_CHECK();
   return 0;
 }
 
 int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st,
                          bool grad_f32) {
-  if (nchunks > 0 && grad_f32)
-    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<float>, dim3(nchunks), dim3(kBlock), 0, st, (const float*)g, chunks_dev, ws + 16,
-                       (const int32_t*)nullptr);
-  else if (nchunks > 0)
-    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<bf16_t>, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, ws + 16,
-                       (const int32_t*)nullptr);
+  if (int e = k_grad_sqnorm_partials(g, chunks_dev, nullptr, nchunks, ws + 16, st, grad_f32)) return e;
   hipLaunchKernelGGL(grad_sqnorm_final2_kernel, dim3(1), dim3(kBlock), 0, st, ws, nchunks, extra, nextra);
   GGET_LAUNCH_CHECK();
   return 0;
 }
 
-int k_adamw(float* master, float* m, float* v, const void* grad, void* param, size_t n, float lr, float beta1, float beta2,
-            float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm, float* gnorm_out,
-            hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay, bool grad_f32) {
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2 = 1.0f - powf(beta2, (float)step);
-  // one pass, two float4 groups per thread (grid up to 65536 blocks): the grid-stride form with 4096 blocks ran at 5.1 TB/s of
-  // state traffic, this one at 6.0 (profiles/r02_adamw_sweep.txt); loads and the fp32 state stores are non-temporal
-  const dim3 grid(grid_for((long)(n / 8), kBlock, 65536));
-  // (grad_f32: the same launch reading the fp32 accumulator of a gradient-accumulation window - 4 gradient bytes instead of 2)
-  if (ema && grad_f32)
-    hipLaunchKernelGGL((adamw_ema_kernel<2, float>), grid, dim3(kBlock), 0, st, master, m, v, (const float*)grad, (bf16_t*)param, n, lr, beta1,
-                       beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0, ema, ema_decay);
-  else if (ema)
-    hipLaunchKernelGGL((adamw_ema_kernel<2, bf16_t>), grid, dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1,
-                       beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0, ema, ema_decay);
-  else if (grad_f32)
-    hipLaunchKernelGGL((adamw_kernel<2, float>), grid, dim3(kBlock), 0, st, master, m, v,
-                       (const float*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
-                       grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
-  else
-    hipLaunchKernelGGL((adamw_kernel<2, bf16_t>), grid, dim3(kBlock), 0, st, master, m, v,
-                       (const bf16_t*)grad, (bf16_t*)param, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm,
-                       grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
+int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, float* ws, hipStream_t st) {
+  hipLaunchKernelGGL(grad_sqnorm_slots_kernel, dim3(1), dim3(kSlotsBlock), 0, st, slots, slot_of_dev, n, ws);
   GGET_LAUNCH_CHECK();
   return 0;
+}
+
+// The one AdamW launch: `kernel` of a traversal shape picked by (gradient element type, EMA form), `work` = what the shape runs over
+// (the element count, or the item table).  The bias corrections are formed here and nowhere else.
+namespace {
+struct AdamwGridStride {
+  template <typename GT, bool EMA> static constexpr auto kernel() { return adamw_kernel<2, GT, EMA>; }
+};
+struct AdamwItems {
+  template <typename GT, bool EMA> static constexpr auto kernel() { return adamw_items_kernel<GT, EMA>; }
+};
+template <typename Shape, typename Work>
+int adamw_launch(const GgetAdamwArgs& a, dim3 grid, Work work, hipStream_t st) {
+  const float bc1 = 1.0f - powf(a.beta1, (float)a.step);
+  const float bc2 = 1.0f - powf(a.beta2, (float)a.step);
+  auto launch = [&](auto kernel, auto* grad) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, a.master, a.m, a.v, grad, (bf16_t*)a.param, work, a.lr, a.beta1, a.beta2, a.eps,
+                       a.wd, bc1, sqrtf(bc2), a.max_norm, a.grad_scale, a.sqnorm, a.gnorm_out, a.skip_nonfinite ? 1 : 0, a.ema, a.ema_decay);
+  };
+  // (grad_f32: the same launch reading the fp32 accumulator of a gradient-accumulation window - 4 gradient bytes instead of 2)
+  if (a.grad_f32 && a.ema) launch(Shape::template kernel<float, true>(), (const float*)a.grad);
+  else if (a.grad_f32) launch(Shape::template kernel<float, false>(), (const float*)a.grad);
+  else if (a.ema) launch(Shape::template kernel<bf16_t, true>(), (const bf16_t*)a.grad);
+  else launch(Shape::template kernel<bf16_t, false>(), (const bf16_t*)a.grad);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace
+
+int k_adamw(const GgetAdamwArgs& a, size_t n, hipStream_t st) {
+  // one pass, two float4 groups per thread (grid up to 65536 blocks): the grid-stride form with 4096 blocks ran at 5.1 TB/s of
+  // state traffic, this one at 6.0 (profiles/r02_adamw_sweep.txt); loads and the fp32 state stores are non-temporal
+  return adamw_launch<AdamwGridStride>(a, dim3(grid_for((long)(n / 8), kBlock, 65536)), n, st);
+}
+
+int k_adamw_items(const GgetAdamwArgs& a, const GgetSqChunk* items_dev, int nitems, hipStream_t st) {
+  if (nitems <= 0) return 0;
+  return adamw_launch<AdamwItems>(a, dim3(nitems), items_dev, st);
 }
 
 int k_grad_accumulate(const void* grad, float* acc, size_t n, bool first, hipStream_t st) {
@@ -3170,47 +3153,6 @@ int k_ema_lerp(const float* master, float* ema, size_t n, float d, hipStream_t s
 int k_ema_lerp_items(const float* master, float* ema, const GgetSqChunk* items_dev, int nitems, float d, hipStream_t st) {
   if (nitems <= 0) return 0;
   hipLaunchKernelGGL(ema_lerp_items_kernel, dim3(nitems), dim3(kBlock), 0, st, master, ema, items_dev, d);
-  GGET_LAUNCH_CHECK();
-  return 0;
-}
-
-int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st,
-                           bool grad_f32) {
-  if (nchunks <= 0) return 0;
-  if (grad_f32)
-    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<float>, dim3(nchunks), dim3(kBlock), 0, st, (const float*)g, chunks_dev, out, slot_dev);
-  else
-    hipLaunchKernelGGL(grad_sqnorm_chunks_kernel<bf16_t>, dim3(nchunks), dim3(kBlock), 0, st, (const bf16_t*)g, chunks_dev, out, slot_dev);
-  GGET_LAUNCH_CHECK();
-  return 0;
-}
-
-int k_grad_sqnorm_slots(const float* slots, const int32_t* slot_of_dev, int n, float* ws, hipStream_t st) {
-  hipLaunchKernelGGL(grad_sqnorm_slots_kernel, dim3(1), dim3(kSlotsBlock), 0, st, slots, slot_of_dev, n, ws);
-  GGET_LAUNCH_CHECK();
-  return 0;
-}
-
-int k_adamw_items(float* master, float* m, float* v, const void* grad, void* param, const GgetSqChunk* items_dev, int nitems, float lr,
-                  float beta1, float beta2, float eps, float wd, int step, float max_norm, float grad_scale, const float* sqnorm,
-                  float* gnorm_out, hipStream_t st, bool skip_nonfinite, float* ema, float ema_decay, bool grad_f32) {
-  if (nitems <= 0) return 0;
-  const float bc1 = 1.0f - powf(beta1, (float)step);      // (the constants exactly as k_adamw derives them)
-  const float bc2 = 1.0f - powf(beta2, (float)step);
-  if (ema && grad_f32)
-    hipLaunchKernelGGL(adamw_items_ema_kernel<float>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const float*)grad, (bf16_t*)param,
-                       items_dev, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out,
-                       skip_nonfinite ? 1 : 0, ema, ema_decay);
-  else if (ema)
-    hipLaunchKernelGGL(adamw_items_ema_kernel<bf16_t>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param,
-                       items_dev, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out,
-                       skip_nonfinite ? 1 : 0, ema, ema_decay);
-  else if (grad_f32)
-    hipLaunchKernelGGL(adamw_items_kernel<float>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const float*)grad, (bf16_t*)param, items_dev,
-                       lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
-  else
-    hipLaunchKernelGGL(adamw_items_kernel<bf16_t>, dim3(nitems), dim3(kBlock), 0, st, master, m, v, (const bf16_t*)grad, (bf16_t*)param, items_dev,
-                       lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), max_norm, grad_scale, sqnorm, gnorm_out, skip_nonfinite ? 1 : 0);
   GGET_LAUNCH_CHECK();
   return 0;
 }

@@ -175,12 +175,9 @@ class Engine:
 
     def bucket_train_range(self, b: int):
         """(offset, count) of bucket b's trainable share: the bucket, nothing (count 0), or the embedding bucket's gate / raw-embedding part."""
-        lo, cnt = self.buckets[b]
-        for off, n in self.train_ranges:
-            a, z = max(lo, off), min(lo + cnt, off + n)
-            if a < z:
-                return a, z - a
-        return lo, 0
+        o, c = C.c_uint64(), C.c_uint64()
+        L.check(self.lib.gget_bucket_train_range(self.h, int(b), C.byref(o), C.byref(c)))
+        return int(o.value), int(c.value)
 
     def trainable_buckets(self):
         """The exchange's view of `buckets`: every bucket cut to its trainable share (count 0 = nothing to exchange)."""
@@ -455,12 +452,17 @@ class Engine:
     def backward_end(self):
         L.check(self.lib.gget_backward_end(self.h, _stream()))
 
-    def adamw_step(self, lr, beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, grad_scale=1.0):
+    def _adamw(self, entry, slots, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale):
+        """one optimizer step through `entry` (gget_adamw_step, or gget_adamw_step_sharded with the gathered partial vector `slots`):
+        counts the step and returns the pre-clip gradient norm, a device scalar"""
         self.step_count += 1
         self._gnorm = torch.empty(1, dtype=torch.float32, device=self.device)     # (fresh per step: nothing to copy out, see forward_pretrain)
-        L.check(self.lib.gget_adamw_step(self.h, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale,
-                                         self.step_count, _ptr(self._gnorm), _stream()))
+        L.check(entry(self.h, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale, self.step_count, *slots, _ptr(self._gnorm),
+                      _stream()))
         return self._gnorm[0]
+
+    def adamw_step(self, lr, beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, grad_scale=1.0):
+        return self._adamw(self.lib.gget_adamw_step, (), lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale)
 
     # ------------------------------------------------------------------ sharded optimizer step (ZeRO stage 2)
     @staticmethod
@@ -482,15 +484,11 @@ class Engine:
             self.shard, self.shard_buckets, self.shard_slots = None, [], None
             return
         self.shard = (int(world), int(rank))
-        self.shard_buckets = self.shard_plan_of(self.cfg, world, len(self.buckets))
-        if self.frozen >= 0:    # the plan of a bucket's trainable share (gget_shard_init cuts the same ranges by the same rule)
-            chunk = L.SHARD_CHUNK
-            plans = []
-            for b in range(len(self.buckets)):
-                off, cnt = self.bucket_train_range(b)
-                sl = cnt // (int(world) * chunk) * chunk
-                plans.append((off, cnt, sl, off + int(world) * sl, cnt - int(world) * sl))
-            self.shard_buckets = plans
+        out = (C.c_uint64 * 5)()     # the handle's plan: every bucket's trainable share cut for `world` ranks (gget_shard_bucket)
+        self.shard_buckets = []
+        for b in range(len(self.buckets)):
+            L.check(self.lib.gget_shard_bucket(self.h, b, out))
+            self.shard_buckets.append(tuple(int(x) for x in out))
         self.shard_slots = torch.zeros(int(world) * n.value, dtype=torch.float32, device=self.device)
 
     def reduce_scatter_grads_async(self, bucket: int, fp32_accumulate: bool = False, stream: Optional[torch.cuda.Stream] = None):
@@ -507,14 +505,12 @@ class Engine:
     def adamw_step_sharded(self, lr, beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, grad_scale=1.0):
         """clip + AdamW over this rank's share (gget_adamw_step_sharded); the partial vector must have been gathered.  Marks the fp32
         state stale (a world-1 plan owns everything and stays coherent)."""
-        self.step_count += 1
-        self._gnorm = torch.empty(1, dtype=torch.float32, device=self.device)
-        L.check(self.lib.gget_adamw_step_sharded(self.h, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale,
-                                                 self.step_count, _ptr(self.shard_slots), _ptr(self._gnorm), _stream()))
+        gnorm = self._adamw(self.lib.gget_adamw_step_sharded, (_ptr(self.shard_slots),), lr, beta1, beta2, eps, weight_decay, max_grad_norm,
+                            grad_scale)
         if self.shard[0] > 1 and not getattr(self, "_loopback", False):    # (the loopback handle updates every rank's share itself)
             self.shard_stale = True
             self.ema_stale = self.ema is not None and self.ema_live
-        return self._gnorm[0]
+        return gnorm
 
     # ------------------------------------------------------------------ data-parallel exchange through the C ABI (RCCL)
     @staticmethod

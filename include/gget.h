@@ -362,6 +362,11 @@ int gget_set_frozen(gget_handle_t h, int frozen_layers);
  * [end of embed_tokens, start of layer 0) - empty and dropped without gate / raw-embedding parameters - and [start of layer min(k, L),
  * n_params)).  The host builds its exchange groups from them. */
 int gget_trainable_ranges(gget_handle_t h, uint64_t out[4], int32_t* n_out);
+/* replaces: the same `p.requires_grad` filter seen per gradient bucket (what DDP's reducer and DeepSpeed's partitioning skip for a frozen
+ * parameter; modules_utils.py:45-54): {offset, count} of the trainable share of bucket `bucket` of gget_bucket_range - the bucket itself,
+ * nothing (count 0, offset = the bucket's), or the embedding bucket's gate / raw-embedding parameters.  A bucket meets at most one of the
+ * trainable ranges, in one piece.  What the exchange and the shard plan cut; the rule lives here only. */
+int gget_bucket_train_range(gget_handle_t h, int bucket, uint64_t* offset, uint64_t* count);
 
 /* ------------------------------------------------------------------------------------------
  * Weight EMA (`training.optimizer.use_ema` / `ema_decay`; the reference's fine-tune launch scripts switch it on, e.g.
@@ -424,6 +429,10 @@ int gget_shard_plan(const gget_config_t* cfg, int world, int bucket, uint64_t ou
  * handle; synchronous.  With a communicator, rank / world must be its own.  *slots_per_rank (may be NULL) = entries per rank of the
  * partial vector. */
 int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* slots_per_rank);
+/* replaces: reading back DeepSpeed's partition boundaries (stage_1_and_2.py keeps them per parameter group): the ACTIVE plan of one bucket,
+ * out = {offset, count, slice, tail_offset, tail_count} as gget_shard_plan - cut from the bucket's trainable share (gget_bucket_train_range),
+ * so equal to gget_shard_plan's only while nothing is frozen.  An error when no plan is active. */
+int gget_shard_bucket(gget_handle_t h, int bucket, uint64_t out[5]);
 /* replaces: the bucketed reduce-scatter of DeepSpeed stage 2 (reduce_scatter: true in ds_config2_pt.json's zero_optimization): the body of
  * bucket `bucket` reduce-scattered in place (this rank's slice receives the sum) and the tail all-reduced, one group on `side_stream`
  * (stream protocol and fp32_accumulate as gget_allreduce_grads_async; the loopback multiplies the whole bucket by world). */

@@ -188,7 +188,7 @@ def test_replicated_step_capped_grid():
 
 @pytest.mark.parametrize("model", ["tiny", "d768"])
 def test_fused_ema_step(model):
-    """adamw_ema_kernel<2>: the same element check on master, m, v and P, and the EMA within 8u max(|ema|, |w'|) of
+    """adamw_kernel<2, .., EMA>: the same element check on master, m, v and P, and the EMA within 8u max(|ema|, |w'|) of
     w' + d32 (ema - w') against the NEW master weights read back"""
     e = _engine(model)
     e.ema_attach()

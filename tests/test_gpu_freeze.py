@@ -104,6 +104,44 @@ def _ulp_bf16(v):
     return torch.where(a > 0, torch.exp2(torch.floor(torch.log2(a.clamp_min(1e-300))) - 7), torch.zeros_like(a))
 
 
+# ------------------------------------------------------------------------------------------------ the plan, read back from the handle
+@pytest.mark.parametrize("world", [1, 2, 4])
+@pytest.mark.parametrize("frozen", [-1, 0, 1, 2])
+def test_shard_plan_of_the_handle_follows_the_written_rule(frozen, world):
+    """gget_bucket_train_range = the intersection of gget_bucket_range with gget_trainable_ranges, and gget_shard_bucket = that share cut
+    into `world` slices of whole GGET_SHARD_CHUNK chunks plus a tail - the rule written out here, with no device arithmetic.  The tiny
+    pre-train model (2 layers: frozen = 2 is num_layers) with gated aggregation: two trainable ranges, a partial embedding bucket."""
+    import ctypes as C
+    spec_mod = importlib.import_module("graph-gpt_amd.spec")
+    spec = spec_mod.spec_from_size("tiny", vocab_size=756, stacked_feat=13, next_n_token=13, gated_agg=True)
+    assert spec.num_layers == 2
+    e = importlib.import_module("graph-gpt_amd.engine").Engine(spec, max_tokens=256, max_batch=8)
+    e.comm_init_loopback(world)
+    e.set_frozen(frozen)
+    e.shard_init(world, 0)
+    if frozen >= 0:
+        assert len(e.train_ranges) == 2 and e.train_ranges[0][1] > 0
+    out, o, c = (C.c_uint64 * 5)(), C.c_uint64(), C.c_uint64()
+    partial = 0
+    for b, (lo, cnt) in enumerate(e.buckets):
+        meet = [(max(lo, off), min(lo + cnt, off + n)) for off, n in e.train_ranges]
+        meet = [(a, z - a) for a, z in meet if a < z]
+        assert len(meet) <= 1
+        want = meet[0] if meet else (lo, 0)
+        L.check(e.lib.gget_bucket_train_range(e.h, b, C.byref(o), C.byref(c)))
+        assert (o.value, c.value) == want == e.bucket_train_range(b)
+        partial += 0 < want[1] < cnt
+        off, n = want
+        sl = n // (world * R.SHARD_CHUNK) * R.SHARD_CHUNK
+        L.check(e.lib.gget_shard_bucket(e.h, b, out))
+        assert tuple(out) == (off, n, sl, off + world * sl, n - world * sl) == e.shard_buckets[b]
+        if frozen < 0:
+            L.check(e.lib.gget_shard_plan(C.byref(e.cfg), world, b, out))
+            assert tuple(out) == e.shard_buckets[b]
+    assert partial == (1 if frozen >= 0 else 0)         # (the embedding bucket keeps its gate parameters only)
+    e.comm_destroy()
+
+
 # ------------------------------------------------------------------------------------------------ the never-frozen reference, once
 _REF = {}
 

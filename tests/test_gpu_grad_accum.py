@@ -205,7 +205,7 @@ def test_boundary_step_reads_the_unrounded_fp32_sum(monkeypatch, batches):
 
 # ------------------------------------------------------------------------------------------------ 3. every launch form
 def test_boundary_step_fused_ema(monkeypatch, batches):
-    """adamw_ema_kernel on the fp32 source; the average follows the new weights (decay 0 on the first two updates: ema == master)"""
+    """adamw_kernel<.., EMA> on the fp32 source; the average follows the new weights (decay 0 on the first two updates: ema == master)"""
     e, post = _window_check(monkeypatch, batches, "fused_ema", use_ema=True)
     assert e.ema is not None and torch.equal(e.ema, post["w"])
 

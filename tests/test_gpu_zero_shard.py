@@ -77,6 +77,24 @@ def test_abi_sharded_step_world1_equals_replicated_step(reproducible):
         assert not b.shard_stale
 
 
+def test_shard_bucket_without_a_plan_is_an_error():
+    """gget_shard_bucket reads the ACTIVE plan: before gget_shard_init, and after the plan is switched off, it returns an error and a
+    message and leaves `out` alone"""
+    import ctypes as C
+    spec = importlib.import_module("graph-gpt_amd.spec").spec_from_size("tiny", vocab_size=756, stacked_feat=13, next_n_token=13, gated_agg=True)
+    e = importlib.import_module("graph-gpt_amd.engine").Engine(spec, max_tokens=256, max_batch=8)
+    out = (C.c_uint64 * 5)(7, 7, 7, 7, 7)
+    for _ in range(2):
+        assert e.lib.gget_shard_bucket(e.h, 0, out) != 0
+        assert b"no plan is active" in e.lib.gget_last_error()
+        assert list(out) == [7] * 5
+        e.shard_init(1, 0)
+        assert e.lib.gget_shard_bucket(e.h, 0, out) == 0 and tuple(out) == e.shard_buckets[0]
+        assert e.lib.gget_shard_bucket(e.h, len(e.buckets), out) != 0 and b"out of range" in e.lib.gget_last_error()
+        e.shard_init(0, 0)
+        out = (C.c_uint64 * 5)(7, 7, 7, 7, 7)
+
+
 def _loop_run(monkeypatch, world, zero, clip=0.05, k=1, backend="abi", fp32="0"):
     modeling, tr, synth = _mods()
     monkeypatch.setenv("GGET_DP_BACKEND", backend)
