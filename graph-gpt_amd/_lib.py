@@ -137,6 +137,10 @@ SIGNATURES = {
     "gget_op_ce_fwd_bwd": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, f32, i32, vp]),
     "gget_op_rank_metrics_workspace": (C.c_size_t, [i32, i32]),
     "gget_op_rank_metrics": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gget_op_link_hits_workspace": (C.c_size_t, [i32]),
+    "gget_op_link_hits": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gget_op_link_mrr_workspace": (C.c_size_t, [i32]),
+    "gget_op_link_mrr": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
 }
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -150,8 +154,8 @@ EPI_NONE, EPI_RESIDUAL, EPI_ATOMIC_F32, EPI_SLAB_F32 = 0, 1, 2, 3
 # gget_debug_set / gget_debug_get keys of the process launch menu (csrc/menu.h kMenuRows, INTEGRATION.md "Kernel-selection knobs")
 KEY_GEMM_VARIANT, KEY_GEMM_LDS_HEADROOM, KEY_GEMM_SPLIT_LAST, KEY_DETERMINISTIC, KEY_GEMM_STAGGER = 1, 2, 3, 4, 5
 KEY_GEMM_ABLATE, KEY_HEAD_DENSE, KEY_HEAD_TILE, KEY_ATTN_OPROJ_OFF, KEY_LS_NORM_BWD_WIDE = 7, 8, 9, 10, 11
-KEY_RMS_WIDE, KEY_CE_PARTS, KEY_GEMM_CU_RESERVE, KEY_OCCUPY_FAT = 13, 14, 15, 16
-MENU_KEYS = (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 13, 14, 15, 16)
+KEY_RMS_WIDE, KEY_CE_PARTS, KEY_GEMM_CU_RESERVE, KEY_OCCUPY_FAT, KEY_LINK_GRID = 13, 14, 15, 16, 18
+MENU_KEYS = (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 13, 14, 15, 16, 18)
 # KEY_GEMM_VARIANT bits (csrc/menu.h kGemm*): the first six switch a variant OFF, the last two switch one ON
 GEMM_NO_KSPLIT_ND, GEMM_NO_KSPLIT_WGRAD, GEMM_NO_192_ROWS, GEMM_NO_SPLIT_LAST, GEMM_KSPLIT_128_ONLY, GEMM_ONE_BLOCK_PER_CU = 1, 2, 4, 8, 16, 32
 GEMM_KSPLIT_DMA8, GEMM_AREA_RULE = 128, 512

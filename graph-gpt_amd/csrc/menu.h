@@ -49,6 +49,8 @@ struct LaunchMenu {
   int rms_rows;             // RMSNorm backward: rows per wave
   int ce_parts;             // cross-entropy: one partial loss sum per block instead of an atomic
   int ce_generic;           // cross-entropy: never the vectorised row kernels
+  // evaluation metrics (metrics.hip)
+  int link_grid;            // > 0: most workgroups a streaming launch of the link metrics takes (0: 1024, four per CU)
 };
 
 // gget_debug_set / gget_debug_get key 1: bits that switch GEMM kernel variants (0 = the shipped selection)
@@ -87,6 +89,7 @@ inline constexpr MenuRow kMenuRows[] = {
     {&LaunchMenu::ce_parts, 14, "GGET_CE_PARTS", false, 1, "0: cross-entropy adds its loss with one atomic per block instead of per-block partial sums"},
     {&LaunchMenu::gemm_cu_reserve, 15, nullptr, false, 0, "CUs every GEMM plan leaves free for a collective's workgroups"},
     {&LaunchMenu::occupy_fat, 16, nullptr, false, 0, "1: gget_debug_occupy's stand-in takes RCCL's register footprint"},
+    {&LaunchMenu::link_grid, 18, nullptr, false, 0, "> 0: most workgroups a streaming launch of the link metrics takes (0: 1024)"},
     {&LaunchMenu::gemm_num_cu, 0, "GGET_GEMM_NUM_CU", false, 0, "> 0: GEMM plans pretend the chip has this many CUs"},
     {&LaunchMenu::gemm_no_persist, 0, "GGET_GEMM_NO_PERSIST", true, 0, "set: no persistent GEMM kernels"},
     {&LaunchMenu::gemm_no_dyn, 0, "GGET_GEMM_NO_DYN", true, 0, "set: no persistent GEMM kernels for device-sized launches"},

@@ -235,7 +235,437 @@ RankLayout rank_layout(int n, int C) {
   return L;
 }
 
+// ------------------------------------------------------------------------------------------------ link prediction: Hits@K and MRR
+// replaces: OGB's link evaluators on the tensors the reference's metric object keeps on the device (src/utils/metrics_utils.py:38-73):
+// `_reformat_pred_for_hr_eval` + `_eval_hits` (src/utils/ogb_utils.py:141-152 behind :82-90 ogbl-ppa, :131-138 ogbl-ddi: torch.topk of the
+// negatives, then compare-and-sum) and `_reformat_pred_for_mrr_eval` + `_eval_mrr` (:155-170 behind :92-128 ogbl-citation2 / ogbl-wikikg2:
+// torch.sort by idx, mask, reshape, two compare-and-sums per row).  Integer counters only; the one fp64 sum has a fixed order.
+constexpr int kLinkBlock = 256;        // threads of the streaming launches (4 waves)
+constexpr int kLinkVec = 4;            // entries per lane and grid-stride round on the aligned body: one 16-byte score load, two label loads
+constexpr int kLinkGrid = 1024;        // workgroups at most (4 per CU of a 256-CU chip; menu key 18 overrides): the rest is grid-stride
+constexpr int kLinkBins = 256;         // 8-bit digits, most significant first: four passes over the 32-bit key
+constexpr int kLinkSeg = 256;          // entries of one partition segment of the MRR path: a wave, 4 consecutive entries per lane
+constexpr int kLinkWaves = kLinkBlock / 64;
+
+struct LinkHitsState {                 // device words between the passes (zeroed together with the histograms)
+  int n_pos, n_neg, n_bad;
+  int none;                            // fewer than K negatives: kth = -inf, the later passes return at once
+  unsigned prefix;                     // the digits chosen so far
+  int krem;                            // the K-th largest of the whole list is the krem-th largest among the entries matching prefix
+  int pad[2];
+};
+
+__device__ __forceinline__ int link_class(float s, long long y) {
+  if (!(fabsf(s) <= FLT_MAX)) return kBad;
+  return y == 1 ? kPositive : y == 0 ? kNegative : kBad;
+}
+
+// order-preserving key of a finite fp32: -0.0 becomes +0.0, then negative numbers have all bits flipped, the others the sign bit
+__device__ __forceinline__ unsigned link_key(float s) {
+  unsigned b = __float_as_uint(s);
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float link_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+// f(score, label) once for every entry of [0, n): 16-byte loads on the body that starts at the first 16-byte aligned score (when the
+// labels are 16-byte aligned there, too), single loads for the at most 3 + 3 entries in front of and behind it, or for everything
+template <typename F>
+__device__ __forceinline__ void link_for_each(const float* __restrict__ scores, const long long* __restrict__ labels, int n, F f) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nt = (long)gridDim.x * blockDim.x;
+  const int head = min(n, (int)(((16u - (unsigned)((uintptr_t)scores & 15u)) & 15u) >> 2));
+  if (((uintptr_t)(labels + head) & 15u) != 0) {
+    for (long i = tid; i < n; i += nt) f(scores[i], labels[i]);
+    return;
+  }
+  const int nvec = (n - head) / kLinkVec, rest = head + nvec * kLinkVec;
+  const float4* s4 = reinterpret_cast<const float4*>(scores + head);
+  const longlong2* y2 = reinterpret_cast<const longlong2*>(labels + head);
+  for (long v = tid; v < nvec; v += nt) {
+    const float4 s = s4[v];
+    const longlong2 a = y2[2 * v], b = y2[2 * v + 1];
+    f(s.x, a.x);
+    f(s.y, a.y);
+    f(s.z, b.x);
+    f(s.w, b.y);
+  }
+  if (tid < head) f(scores[tid], labels[tid]);                                      // (the grid holds at least 64 threads)
+  else if (tid - head < n - rest) f(scores[rest + tid - head], labels[rest + tid - head]);
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// pass `kPass` of the radix select: histogram of digit kPass of the negatives whose higher digits equal st->prefix; pass 0 classifies, too
+template <int kPass>
+__global__ void __launch_bounds__(kLinkBlock) link_hist_kernel(const float* __restrict__ scores, const long long* __restrict__ labels, int n,
+                                                               LinkHitsState* __restrict__ st, unsigned* __restrict__ hist) {
+  __shared__ unsigned bins[kLinkBins];
+  unsigned prefix = 0;
+  if (kPass > 0) {
+    if (st->none) return;                       // (uniform over the grid)
+    prefix = st->prefix;
+  }
+  for (int b = threadIdx.x; b < kLinkBins; b += kLinkBlock) bins[b] = 0;
+  __syncthreads();
+  int np = 0, nn = 0, nb = 0;
+  link_for_each(scores, labels, n, [&](float s, long long y) {
+    const int k = link_class(s, y);
+    if (kPass == 0) {
+      np += k == kPositive;
+      nn += k == kNegative;
+      nb += k == kBad;
+    }
+    if (k == kNegative) {
+      const unsigned key = link_key(s);
+      if (kPass == 0 || (key >> (32 - 8 * kPass)) == prefix) atomicAdd(&bins[(key >> (24 - 8 * kPass)) & 255u], 1u);
+    }
+  });
+  if (kPass == 0) {
+    np = wave_sum_int(np);
+    nn = wave_sum_int(nn);
+    nb = wave_sum_int(nb);
+    if ((threadIdx.x & 63) == 0) {
+      if (np) atomicAdd(&st->n_pos, np);
+      if (nn) atomicAdd(&st->n_neg, nn);
+      if (nb) atomicAdd(&st->n_bad, nb);
+    }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < kLinkBins; b += kLinkBlock)
+    if (bins[b]) atomicAdd(&hist[b], bins[b]);
+}
+
+// one wave: lane l owns the bins 255 - 4 l ... 252 - 4 l; walking from the top, the digit whose bin holds the krem-th entry extends the
+// prefix.  The last pass writes the outputs (hits = 0: link_hits_count_kernel adds to it).
+__global__ void __launch_bounds__(64) link_select_kernel(LinkHitsState* __restrict__ st, const unsigned* __restrict__ hist, int pass,
+                                                         long long K, long long* __restrict__ n_pos, long long* __restrict__ n_neg,
+                                                         float* __restrict__ kth, long long* __restrict__ hits, int* __restrict__ n_bad) {
+  const int lane = threadIdx.x;
+  const int none = pass == 0 ? (K > (long long)st->n_neg) : st->none;
+  const int krem = pass == 0 ? (none ? 0 : (int)K) : st->krem;
+  unsigned prefix = pass == 0 ? 0u : st->prefix;
+  if (!none) {
+    int h[4], sum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      h[j] = (int)hist[255 - 4 * lane - j];
+      sum += h[j];
+    }
+    const int incl = wave_incl_scan(sum, lane);
+    int acc = incl - sum, digit = 0, left = 0;
+    const bool mine = acc < krem && krem <= incl;          // true in exactly one lane: the bins hold at least krem entries
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (mine && left == 0 && krem <= acc + h[j]) {
+        digit = 255 - 4 * lane - j;
+        left = krem - acc;                                   // >= 1
+      }
+      acc += h[j];
+    }
+    const unsigned long long who = __ballot(mine);
+    const int src = who ? __ffsll((long long)who) - 1 : 0;
+    digit = __shfl(digit, src, 64);
+    left = __shfl(left, src, 64);
+    prefix = (prefix << 8) | (unsigned)digit;
+    if (lane == 0) {
+      st->prefix = prefix;
+      st->krem = left;
+    }
+  }
+  if (lane == 0) {
+    if (pass == 0) st->none = none;
+    if (pass == 3) {
+      *n_pos = st->n_pos;
+      *n_neg = st->n_neg;
+      *n_bad = st->n_bad;
+      *kth = none ? -INFINITY : link_unkey(prefix);
+      *hits = 0;
+    }
+  }
+}
+
+// positives scored above kth (a float comparison: -0.0 == +0.0); every finite score is above -inf
+__global__ void __launch_bounds__(kLinkBlock) link_hits_count_kernel(const float* __restrict__ scores, const long long* __restrict__ labels,
+                                                                     int n, const float* __restrict__ kth, unsigned long long* __restrict__ hits) {
+  const float t = *kth;
+  int c = 0;
+  link_for_each(scores, labels, n, [&](float s, long long y) { c += link_class(s, y) == kPositive && s > t; });
+  c = wave_sum_int(c);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(hits, (unsigned long long)c);
+}
+
+// ---- MRR
+enum { kMrrBadIdx = 0, kMrrBadEntry = 1, kMrrWords = 16 };       // words of the counter block behind the class marks
+
+// "sort by idx" as a scatter: entry i goes to slot idx[i].  The slot's mark (0 = empty) is claimed with a compare-and-swap and holds the
+// entry's class + 1 afterwards; a slot that is already claimed, or an index outside [0, n), is counted.
+__global__ void __launch_bounds__(kLinkBlock) mrr_scatter_kernel(const float* __restrict__ scores, const long long* __restrict__ labels,
+                                                                 const long long* __restrict__ idx, int n, float* __restrict__ sorted,
+                                                                 unsigned* __restrict__ mark, int* __restrict__ counters) {
+  const long nt = (long)gridDim.x * blockDim.x;
+  int bad = 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nt) {
+    const long long j = idx[i];
+    if (j < 0 || j >= n) {
+      ++bad;
+      continue;
+    }
+    const float s = scores[i];
+    if (atomicCAS(&mark[j], 0u, (unsigned)link_class(s, labels[i]) + 1u) != 0u) ++bad;
+    else sorted[j] = s;
+  }
+  bad = wave_sum_int(bad);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&counters[kMrrBadIdx], bad);
+}
+
+// a wave per segment of kLinkSeg slots, lane l the slots 4 l ... 4 l + 3 of it (one 16-byte load; the mark array is 16-byte aligned and
+// padded to whole segments with empty marks)
+__device__ __forceinline__ void mrr_segment_marks(const unsigned* __restrict__ mark, long seg, int lane, int (&k)[4]) {
+  const uint4 m = reinterpret_cast<const uint4*>(mark)[seg * (kLinkSeg / 4) + lane];
+  k[0] = (int)m.x - 1;
+  k[1] = (int)m.y - 1;
+  k[2] = (int)m.z - 1;
+  k[3] = (int)m.w - 1;
+}
+
+__global__ void __launch_bounds__(kLinkBlock) mrr_class_kernel(const unsigned* __restrict__ mark, int nseg, int32_t* __restrict__ seg_pos,
+                                                               int32_t* __restrict__ seg_neg, int32_t* __restrict__ seg_bad) {
+  const int lane = threadIdx.x & 63;
+  for (long seg = (long)blockIdx.x * kLinkWaves + (threadIdx.x >> 6); seg < nseg; seg += (long)gridDim.x * kLinkWaves) {
+    int k[4], np = 0, nn = 0, nb = 0;
+    mrr_segment_marks(mark, seg, lane, k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      np += k[j] == kPositive;
+      nn += k[j] == kNegative;
+      nb += k[j] == kBad;
+    }
+    np = wave_sum_int(np);
+    nn = wave_sum_int(nn);
+    nb = wave_sum_int(nb);
+    if (lane == 0) {
+      seg_pos[seg] = np;
+      seg_neg[seg] = nn;
+      seg_bad[seg] = nb;
+    }
+  }
+}
+
+// STABLE partition in slot (= idx) order: positives to list[0, n_pos), negatives to list[n_pos, n_pos + n_neg); the offsets come from
+// rank_scan_kernel over the segment counts and a wave scan inside the segment - no slot is handed out by an atomic
+__global__ void __launch_bounds__(kLinkBlock) mrr_fill_kernel(const float* __restrict__ sorted, const unsigned* __restrict__ mark, int n,
+                                                              int nseg, const int32_t* __restrict__ seg_pos, const int32_t* __restrict__ seg_neg,
+                                                              const int64_t* __restrict__ n_pos, float* __restrict__ list) {
+  const int lane = threadIdx.x & 63;
+  const int np_all = (int)*n_pos;
+  for (long seg = (long)blockIdx.x * kLinkWaves + (threadIdx.x >> 6); seg < nseg; seg += (long)gridDim.x * kLinkWaves) {
+    int k[4], np = 0, nn = 0;
+    mrr_segment_marks(mark, seg, lane, k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      np += k[j] == kPositive;
+      nn += k[j] == kNegative;
+    }
+    int ip = seg_pos[seg] + wave_incl_scan(np, lane) - np;
+    int in = np_all + seg_neg[seg] + wave_incl_scan(nn, lane) - nn;
+    const long s0 = seg * kLinkSeg + 4 * lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {       // (a marked slot lies below n; ip < n_pos and in < n_pos + n_neg <= n by the scan of the same marks)
+      if (k[j] == kPositive) list[ip++] = sorted[s0 + j];
+      else if (k[j] == kNegative) list[in++] = sorted[s0 + j];
+    }
+  }
+}
+
+// every index valid and distinct, every entry well-formed, and cnt_neg negatives per positive: then n_pos = P and the rows exist
+__device__ __forceinline__ bool mrr_ok(const int* counters, const int32_t* bad_entries, long long np, long long nn, int P, int cnt_neg) {
+  return counters[kMrrBadIdx] == 0 && *bad_entries == 0 && np == P && nn == (long long)P * cnt_neg;
+}
+
+// a wave per row: lane l takes the columns l, l + 64, ...; with two groups the even columns are group 0 and the odd ones group 1, which
+// is the lane's parity (the stride is even), so the reduction leaves out the exchange between neighbouring lanes
+__global__ void __launch_bounds__(kLinkBlock) mrr_row_kernel(const float* __restrict__ list, const int* __restrict__ counters,
+                                                             const int32_t* __restrict__ bad_entries, const int64_t* __restrict__ n_pos,
+                                                             const int64_t* __restrict__ n_neg, int P, int cnt_neg, int groups,
+                                                             int32_t* __restrict__ optimistic, int32_t* __restrict__ pessimistic) {
+  if (!mrr_ok(counters, bad_entries, *n_pos, *n_neg, P, cnt_neg)) return;
+  const int lane = threadIdx.x & 63;
+  const float* neg = list + P;
+  for (long r = (long)blockIdx.x * kLinkWaves + (threadIdx.x >> 6); r < P; r += (long)gridDim.x * kLinkWaves) {
+    const float p = list[r];
+    const float* row = neg + (size_t)r * cnt_neg;
+    int gt = 0, ge = 0;
+    for (int c = lane; c < cnt_neg; c += 64) {
+      const float v = row[c];
+      gt += v > p;
+      ge += v >= p;
+    }
+    for (int o = 32; o >= groups; o >>= 1) {
+      gt += __shfl_xor(gt, o, 64);
+      ge += __shfl_xor(ge, o, 64);
+    }
+    if (lane < groups) {
+      optimistic[(size_t)lane * P + r] = gt;
+      pessimistic[(size_t)lane * P + r] = ge;
+    }
+  }
+}
+
+// rank = (optimistic + pessimistic) / 2 + 1 over the groups * P entries in list order: thread t adds the entries t, t + 256, ..., then
+// a fixed binary tree (as rank_finish_kernel); rank <= 1 / 3 / 10 are integer tests of optimistic + pessimistic
+__global__ void __launch_bounds__(kLinkBlock) mrr_finish_kernel(const int32_t* __restrict__ optimistic, const int32_t* __restrict__ pessimistic,
+                                                                const int* __restrict__ counters, const int32_t* __restrict__ bad_entries,
+                                                                const int64_t* __restrict__ n_pos, const int64_t* __restrict__ n_neg, int P,
+                                                                int cnt_neg, int groups, int64_t* __restrict__ hits, double* __restrict__ mrr_sum,
+                                                                int32_t* __restrict__ n_bad) {
+  __shared__ int sh[3][kLinkBlock];
+  __shared__ double sd[kLinkBlock];
+  const int t = threadIdx.x;
+  const bool ok = mrr_ok(counters, bad_entries, *n_pos, *n_neg, P, cnt_neg);
+  int h1 = 0, h3 = 0, h10 = 0;
+  double d = 0.0;
+  if (ok)
+    for (long i = t; i < (long)groups * P; i += kLinkBlock) {
+      const int two = optimistic[i] + pessimistic[i];        // 2 (rank - 1)
+      h1 += two <= 0;
+      h3 += two <= 4;
+      h10 += two <= 18;
+      d += 1.0 / (0.5 * (double)two + 1.0);
+    }
+  sh[0][t] = h1;
+  sh[1][t] = h3;
+  sh[2][t] = h10;
+  sd[t] = d;
+  for (int w = kLinkBlock / 2; w > 0; w >>= 1) {
+    __syncthreads();
+    if (t < w) {
+      sh[0][t] += sh[0][t + w];
+      sh[1][t] += sh[1][t + w];
+      sh[2][t] += sh[2][t + w];
+      sd[t] += sd[t + w];
+    }
+  }
+  if (t == 0) {
+    hits[0] = sh[0][0];
+    hits[1] = sh[1][0];
+    hits[2] = sh[2][0];
+    *mrr_sum = sd[0];
+    n_bad[0] = counters[kMrrBadIdx];
+    n_bad[1] = *bad_entries ? *bad_entries : (*n_neg != *n_pos * (int64_t)cnt_neg ? -1 : 0);
+  }
+}
+
+struct MrrLayout {
+  size_t list, sorted, mark, counters, seg_pos, seg_neg, seg_bad, total;
+  int nseg;
+};
+
+MrrLayout mrr_layout(int n) {
+  MrrLayout L{};
+  L.nseg = (n + kLinkSeg - 1) / kLinkSeg;
+  const size_t cell = up256((size_t)L.nseg * kLinkSeg * 4), seg = up256((size_t)L.nseg * 4);
+  size_t o = 0;
+  L.list = o; o += cell;
+  L.sorted = o; o += cell;
+  L.mark = o; o += cell;                       // (mark and counters are zeroed by one memset)
+  L.counters = o; o += up256(kMrrWords * 4);
+  L.seg_pos = o; o += seg;
+  L.seg_neg = o; o += seg;
+  L.seg_bad = o; o += seg;
+  L.total = o;
+  return L;
+}
+
+constexpr size_t kHitsHistBytes = 4 * kLinkBins * sizeof(unsigned);
+constexpr size_t kHitsBytes = kHitsHistBytes + 256;
+
+inline int link_grid(long units) {                // workgroups for `units` workgroup-rounds of work
+  const int cap = menu().link_grid > 0 ? menu().link_grid : kLinkGrid;
+  return (int)(units < 1 ? 1 : units > cap ? cap : units);
+}
+
 }  // namespace
+
+extern "C" size_t gget_op_link_hits_workspace(int n) { return n <= 0 ? 0 : kHitsBytes; }
+
+extern "C" int gget_op_link_hits(const float* scores, const int64_t* labels, int n, int64_t K, int64_t* n_pos, int64_t* n_neg, float* kth,
+                                 int64_t* hits, int32_t* n_bad, void* workspace, size_t workspace_bytes, void* stream) {
+  GGET_REQUIRE(n >= 0, "link_hits: n = %d (the entry takes n < 2^31 entries)", n);
+  GGET_REQUIRE(K >= 1, "link_hits: K = %lld", (long long)K);
+  if (n == 0) return 0;
+  GGET_REQUIRE(scores && labels && n_pos && n_neg && kth && hits && n_bad, "link_hits: null argument");
+  GGET_REQUIRE(((uintptr_t)scores & 3) == 0 && ((uintptr_t)labels & 7) == 0, "link_hits: scores / labels not aligned to their element size");
+  GGET_REQUIRE(workspace && workspace_bytes >= kHitsBytes, "link_hits: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : 0,
+               kHitsBytes);
+  GGET_REQUIRE(((uintptr_t)workspace & 15) == 0, "link_hits: workspace not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* hist = (unsigned*)workspace;
+  LinkHitsState* state = (LinkHitsState*)((char*)workspace + kHitsHistBytes);
+  const long long* y = (const long long*)labels;
+  GGET_HIP_CHECK(hipMemsetAsync(workspace, 0, kHitsBytes, st));
+  const dim3 grid(link_grid(((long)n + kLinkBlock * kLinkVec - 1) / (kLinkBlock * kLinkVec))), block(kLinkBlock);
+#define GGET_LINK_PASS(p)                                                                                                        \
+  hipLaunchKernelGGL(link_hist_kernel<p>, grid, block, 0, st, scores, y, n, state, hist + p * kLinkBins);                        \
+  GGET_LAUNCH_CHECK();                                                                                                           \
+  hipLaunchKernelGGL(link_select_kernel, dim3(1), dim3(64), 0, st, state, hist + p * kLinkBins, p, (long long)K, (long long*)n_pos, \
+                     (long long*)n_neg, kth, (long long*)hits, n_bad);                                                           \
+  GGET_LAUNCH_CHECK()
+  GGET_LINK_PASS(0);
+  GGET_LINK_PASS(1);
+  GGET_LINK_PASS(2);
+  GGET_LINK_PASS(3);
+#undef GGET_LINK_PASS
+  hipLaunchKernelGGL(link_hits_count_kernel, grid, block, 0, st, scores, y, n, kth, (unsigned long long*)hits);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t gget_op_link_mrr_workspace(int n) { return n <= 0 ? 0 : mrr_layout(n).total; }
+
+extern "C" int gget_op_link_mrr(const float* scores, const int64_t* labels, const int64_t* idx, int n, int cnt_neg, int groups, int64_t* n_pos,
+                                int64_t* n_neg, int32_t* optimistic, int32_t* pessimistic, int64_t* hits_1_3_10, double* mrr_sum, int32_t* n_bad,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  GGET_REQUIRE(n >= 0, "link_mrr: n = %d (the entry takes n < 2^31 entries)", n);
+  GGET_REQUIRE(cnt_neg >= 1 && (groups == 1 || groups == 2), "link_mrr: cnt_neg = %d, groups = %d", cnt_neg, groups);
+  GGET_REQUIRE(cnt_neg % groups == 0, "link_mrr: cnt_neg = %d is not a multiple of groups = %d", cnt_neg, groups);
+  GGET_REQUIRE((long long)n % (1ll + cnt_neg) == 0, "link_mrr: n = %d is not a multiple of 1 + cnt_neg = %lld", n, 1ll + cnt_neg);
+  if (n == 0) return 0;
+  GGET_REQUIRE(scores && labels && idx && n_pos && n_neg && optimistic && pessimistic && hits_1_3_10 && mrr_sum && n_bad,
+               "link_mrr: null argument");
+  const MrrLayout L = mrr_layout(n);
+  GGET_REQUIRE(workspace && workspace_bytes >= L.total, "link_mrr: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : 0, L.total);
+  GGET_REQUIRE(((uintptr_t)workspace & 15) == 0, "link_mrr: workspace not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float *list = (float*)(ws + L.list), *sorted = (float*)(ws + L.sorted);
+  unsigned* mark = (unsigned*)(ws + L.mark);
+  int* counters = (int*)(ws + L.counters);
+  int32_t *seg_pos = (int32_t*)(ws + L.seg_pos), *seg_neg = (int32_t*)(ws + L.seg_neg), *seg_bad = (int32_t*)(ws + L.seg_bad);
+  int32_t* bad_entries = counters + kMrrBadEntry;
+  const int P = (int)(n / (1ll + cnt_neg));
+  const long long *y = (const long long*)labels, *ix = (const long long*)idx;
+  GGET_HIP_CHECK(hipMemsetAsync(mark, 0, L.seg_pos - L.mark, st));
+  const dim3 block(kLinkBlock), by_entry(link_grid(((long)n + kLinkBlock - 1) / kLinkBlock));
+  const dim3 by_seg(link_grid(((long)L.nseg + kLinkWaves - 1) / kLinkWaves)), by_row(link_grid(((long)P + kLinkWaves - 1) / kLinkWaves));
+  hipLaunchKernelGGL(mrr_scatter_kernel, by_entry, block, 0, st, scores, y, ix, n, sorted, mark, counters);
+  GGET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mrr_class_kernel, by_seg, block, 0, st, mark, L.nseg, seg_pos, seg_neg, seg_bad);
+  GGET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_scan_kernel, dim3(1), dim3(64), 0, st, seg_pos, seg_neg, seg_bad, L.nseg, n_pos, n_neg, bad_entries);
+  GGET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mrr_fill_kernel, by_seg, block, 0, st, sorted, mark, n, L.nseg, seg_pos, seg_neg, n_pos, list);
+  GGET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mrr_row_kernel, by_row, block, 0, st, list, counters, bad_entries, n_pos, n_neg, P, cnt_neg, groups, optimistic, pessimistic);
+  GGET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mrr_finish_kernel, dim3(1), block, 0, st, optimistic, pessimistic, counters, bad_entries, n_pos, n_neg, P, cnt_neg, groups,
+                     hits_1_3_10, mrr_sum, n_bad);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" size_t gget_op_rank_metrics_workspace(int n, int C) {
   if (n <= 0 || C <= 0) return 0;

@@ -794,17 +794,24 @@ def _check_deferred_all_ranks(model):
 
 @torch.no_grad()
 def ft_evaluate(model, loader, *, problem_type: str = "single_label_classification", num_labels: int = 2,
-                task_level: str = "task", metric_type: Optional[str] = None, dataset_name: str = "", eval_name: str = "valid"):
+                task_level: str = "task", metric_type: Optional[str] = None, dataset_name: str = "", eval_name: str = "valid",
+                cnt_neg: int = 1000):
     """Fine-tune evaluation pass, reference log_eval_dump_utils.ft_evaluate (:77-163): eval mode; per batch one forward WITH
     task labels, sample weights and position_ids; the task loss is averaged over the batches, logits feed the metric object
     (`update(task_logits, labels, idx)`); with several ranks every entry of the metric's tensor dict is gathered from all
     ranks (variable length); the dataset's OGB-style evaluator runs on the gathered dict when there is one, otherwise the
     metric object's own results are returned.  Returns (loss, metrics, eval_result, input_dict) like the reference; the
-    keyword arguments replace the fields the reference reads from its Hydra config."""
+    keyword arguments replace the fields the reference reads from its Hydra config (`cnt_neg`: the negatives per positive of the
+    ogbl-citation2 / ogbl-wikikg2 evaluators, 1000 in the reference).  A two-class single-label problem on a GPU keeps its
+    accumulations on the device, ranks there (metrics.link_hits / link_mrr / rank_metrics) and copies the tensor dict to the host once,
+    after the metrics; ogbl-citation2 / ogbl-wikikg2 are not ranked for eval_name == "train" (reference :153-160): the metric
+    object's own results are returned then."""
     from . import metrics as M
     model.eval()
     device = model.device
-    cls_metrics = M.get_metrics(metric_type or problem_type, device, num_labels=num_labels)
+    on_device = (torch.device(device).type == "cuda" and num_labels == 2
+                 and (metric_type or problem_type) == "single_label_classification")
+    cls_metrics = M.get_metrics(metric_type or problem_type, device, num_labels=num_labels, on_device=on_device)
     test_loss, j = 0, 0
     for j, data in enumerate(loader, 1):
         labels = data[f"{task_level}_labels"].to(device)
@@ -824,6 +831,20 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
     test_loss = test_loss / j
     input_dict = cls_metrics.to_dict()
     world = dist.get_world_size() if dist_ready() else 1
+    ranked = not (eval_name == "train" and dataset_name in M.MRR_DATASETS)
+    ogb = lambda d: M.evaluate_ogb(dataset_name, d, cnt_neg=cnt_neg) if ranked else None      # noqa: E731
+    if on_device:
+        # as the multi-label branch below: metrics from the device-resident accumulations, then the ONE host transfer of the tensor dict
+        sync = cls_metrics.sync_dict()
+        if world > 1:
+            gdev = device if dist.get_backend() == "nccl" else torch.device("cpu")
+            input_dict = {k: all_gather_varlen(v.to(gdev)) for k, v in input_dict.items()}
+            sync = dict(input_dict, prob=all_gather_varlen(sync["prob"].to(gdev)))
+        cls_metrics.compute(sync)
+        res = ogb(input_dict)
+        if res is None:
+            res = cls_metrics.results_in_dict()
+        return test_loss, cls_metrics, res, {k: v.cpu() for k, v in input_dict.items()}
     if isinstance(cls_metrics, M.MultiLabelClassificationMetrics):
         # rank metrics from the device-resident accumulations (the gathered tensors on the collective's device with several ranks): the HIP
         # rank kernels for CUDA tensors; the ONE host transfer of the tensor dict comes after them
@@ -842,7 +863,7 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
         cls_metrics.compute({k: all_gather_varlen(v.to(gdev)).cpu().numpy() for k, v in cls_metrics.sync_dict().items()})
     else:
         cls_metrics.compute()
-    res = M.evaluate_ogb(dataset_name, {k: v.numpy() for k, v in input_dict.items()})
+    res = ogb({k: v.numpy() for k, v in input_dict.items()})
     if res is None:
         res = cls_metrics.results_in_dict()
     return test_loss, cls_metrics, res, input_dict

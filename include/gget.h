@@ -700,6 +700,48 @@ size_t gget_op_rank_metrics_workspace(int n, int C);
 int gget_op_rank_metrics(const float* scores, int ld_s, const float* labels, int ld_y, int n, int C, int64_t* n_pos, int64_t* n_neg,
                          uint64_t* auc2, double* ap_sum, int32_t* n_bad, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Link-prediction metrics of the two-class evaluation pass (csrc/metrics.hip; the Python surface is graph-gpt_amd/metrics.py link_hits /
+ * link_mrr), on the flat device tensors the metric object holds: scores f32 [n], labels i64 [n] (1 = positive edge, 0 = negative edge),
+ * idx i64 [n].  An entry whose label is neither 0 nor 1 or whose score is not finite is "bad": counted, and left out of every other count.
+ * Both entries: n < 2^31 (a negative n is refused); n == 0 is a valid call that launches nothing (the outputs are not written);
+ * workspace = device memory of at least the bytes the _workspace(n) query returns (0 for n <= 0), 16-byte aligned, contents irrelevant -
+ * a smaller one is refused with an error before anything is launched; every launch goes to `stream`, no host sync.  Integer counters
+ * only (no floating-point atomic): every output is exact, independent of the launch geometry and bit-identical from run to run.
+ *
+ * gget_op_link_hits     replaces: `_reformat_pred_for_hr_eval` (src/utils/ogb_utils.py:141-152) + OGB `_eval_hits` (torch.topk of the negatives,
+ *                       compare-and-sum) behind `_eval_ogbl_ppa` :82-90 and `_eval_ogbl_ddi` :131-138.
+ *   n_pos, n_neg  i64   positives and negatives
+ *   kth           f32   the K-th largest negative score (-0.0 reads as +0.0); -inf when n_neg < K
+ *   hits          i64   positives with score > kth (a float comparison: -0.0 == +0.0); n_pos when n_neg < K.  Hits@K = hits / n_pos
+ *   n_bad         i32   bad entries
+ *   Exact selection without a sort: the negatives' fp32 bits become order-preserving 32-bit keys; four passes of a most-significant-digit
+ *   radix select (8-bit digits; LDS histogram per workgroup, merged with integer atomics; a one-wave step picks the digit that holds the
+ *   K-th entry), the classification fused into the first; a last pass counts the positives above kth.  K >= 1.
+ *
+ * gget_op_link_mrr      replaces: `_reformat_pred_for_mrr_eval` (src/utils/ogb_utils.py:155-170: sort by idx, mask, reshape [-1, cnt_neg]) + OGB
+ *                       `_eval_mrr` behind `_eval_ogbl_citation2` :92-102 (groups = 1) and `_eval_ogbl_wikikg2` :105-128 (groups = 2: the even
+ *                       negative columns are the head batch, the odd ones the tail batch, :112-113; cnt_neg must be even).
+ *   idx must be a permutation of 0 .. n-1: entry i takes position idx[i].  In that order the positives are p[0, P) and the negatives the rows
+ *   [r cnt_neg, (r + 1) cnt_neg), P = n / (1 + cnt_neg) (n % (1 + cnt_neg) != 0 is refused).
+ *   n_pos, n_neg             i64
+ *   optimistic, pessimistic  i32 [groups][P]   negatives of the (group, row) scored > / >= the row's positive
+ *   hits_1_3_10              i64 [3]           entries with rank <= 1 / 3 / 10, rank = (optimistic + pessimistic) / 2 + 1
+ *   mrr_sum                  f64               sum of 1 / rank over the groups * P entries in list order with a fixed tree
+ *   n_bad                    i32 [2]           [0] indices outside [0, n) or repeated; [1] bad entries, or -1 when there are none but
+ *                                              n_neg != n_pos * cnt_neg.  When either is non-zero the reference asserts; here optimistic /
+ *                                              pessimistic are not written and hits_1_3_10 / mrr_sum are 0.
+ *   Scatter by idx (a per-slot mark finds repeats), stable partition by count / scan / fill (no slot handed out by an atomic), one wave
+ *   per row, one block for the sums.
+ * ------------------------------------------------------------------------------------------ */
+size_t gget_op_link_hits_workspace(int n);
+int gget_op_link_hits(const float* scores, const int64_t* labels, int n, int64_t K, int64_t* n_pos, int64_t* n_neg, float* kth, int64_t* hits,
+                      int32_t* n_bad, void* workspace, size_t workspace_bytes, void* stream);
+size_t gget_op_link_mrr_workspace(int n);
+int gget_op_link_mrr(const float* scores, const int64_t* labels, const int64_t* idx, int n, int cnt_neg, int groups, int64_t* n_pos,
+                     int64_t* n_neg, int32_t* optimistic, int32_t* pessimistic, int64_t* hits_1_3_10, double* mrr_sum, int32_t* n_bad,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

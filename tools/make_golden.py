@@ -1076,6 +1076,31 @@ def freeze_names_fixture():
     print(f"freeze_names written: {len(cases)} cases")
 
 
+def link_reformat_fixture():
+    """Shuffled idx / y_true / y_pred of a link-prediction evaluation and what the reference's `_reformat_pred_for_hr_eval` (ogb_utils.py
+    :141-152) and `_reformat_pred_for_mrr_eval` (:155-170) return for them: the sort by idx, the masks and the reshape that
+    metrics.link_hits / link_mrr restate.  Two layouts of the idx order (every positive in front of its negatives; all positives
+    first), scores with ties.  Data only."""
+    import_reference()
+    from src.utils import ogb_utils
+    rng = np.random.RandomState(20)
+    res = {}
+    for tag, P, cnt_neg, blocked in (("a", 7, 6, False), ("b", 5, 4, True)):
+        n = P * (1 + cnt_neg)
+        y_sorted = np.concatenate([np.ones(P), np.zeros(P * cnt_neg)]) if blocked else np.tile(np.r_[1, np.zeros(cnt_neg)], P)
+        s_sorted = np.round(rng.randn(n), 1).astype(np.float32)                  # one decimal: ties between positives and negatives
+        perm = rng.permutation(n)                                                # entry i of the shuffled lists is sample perm[i]
+        d = {"idx": torch.from_numpy(perm.astype(np.int64)), "y_true": torch.from_numpy(y_sorted[perm].astype(np.int64)),
+             "y_pred": torch.from_numpy(s_sorted[perm])}
+        hr_pos, hr_neg = ogb_utils._reformat_pred_for_hr_eval(d)
+        mrr_pos, mrr_neg = ogb_utils._reformat_pred_for_mrr_eval(d, cnt_neg=cnt_neg)
+        res.update({f"{tag}_idx": d["idx"].numpy(), f"{tag}_y_true": d["y_true"].numpy(), f"{tag}_y_pred": d["y_pred"].numpy(),
+                    f"{tag}_cnt_neg": np.int64(cnt_neg), f"{tag}_hr_pos": hr_pos.numpy(), f"{tag}_hr_neg": hr_neg.numpy(),
+                    f"{tag}_mrr_pos": mrr_pos.numpy(), f"{tag}_mrr_neg": mrr_neg.numpy()})
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "link_reformat.npz"), **res)
+    print("link_reformat written:", {k: v.shape for k, v in res.items()})
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -1119,6 +1144,8 @@ def main():
         pipeline_config_fixture()
     if not only or "freeze_names" in only:
         freeze_names_fixture()
+    if not only or "link_reformat" in only:
+        link_reformat_fixture()
 
 
 if __name__ == "__main__":
