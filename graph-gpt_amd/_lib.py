@@ -135,6 +135,17 @@ SIGNATURES = {
     "gget_op_geglu_fwd": (i32, [vp, vp, i32, i32, vp]),
     "gget_op_geglu_bwd": (i32, [vp, vp, vp, i32, i32, vp]),
     "gget_op_ce_fwd_bwd": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, f32, i32, vp]),
+    "gget_op_score_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_op_score_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_op_tok_score_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_op_tok_ce": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp]),
+    "gget_op_tok_score_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_op_task_loss": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "gget_op_auc_loss": (i32, [vp, vp, i32, i32, i32, C.c_uint32, vp, vp, vp, vp]),
+    "gget_op_pool_rows": (i32, [vp, vp, vp, i32, i32, vp]),
+    "gget_op_scatter_rows_f32": (i32, [vp, vp, vp, i32, i32, vp]),
+    "gget_op_head_linear_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "gget_op_head_linear_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "gget_op_rank_metrics_workspace": (C.c_size_t, [i32, i32]),
     "gget_op_rank_metrics": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "gget_op_link_hits_workspace": (C.c_size_t, [i32]),

@@ -1772,7 +1772,6 @@ extern "C" int gget_forward_task(gget_handle_t h, const int64_t* input_ids_dev, 
     GGET_REQUIRE(loss_dev != nullptr, "loss_dev is required when task labels are given");
     if (problem_type == GGET_PROBLEM_AUC) {
       GGET_REQUIRE(C >= 2, "the AUC loss reads logits[:, 1] - logits[:, 0]");
-      GGET_REQUIRE((long)B * h->auc_num_neg <= 8192, "AUC loss: positives x num_neg is limited to 8192 pairs");
       if (int e = k_auc_loss(lg, (const int64_t*)task_labels_dev, B, C, h->auc_num_neg, h->auc_seed, loss_dev,
                              h->wsp<float>(w.tdlogits), h->wsp<int32_t>(w.auc_lists), st))
         return e;
@@ -2872,6 +2871,65 @@ extern "C" int gget_op_ce_fwd_bwd(const void* logits, int ld, const int32_t* lab
   GGET_REQUIRE(row_wgt == nullptr, "per-row weights go through the engine path (sample_wgt)");
   return k_ce_fwd_bwd(logits, ld, labels, nullptr, nullptr, 1, n_rows_dev, n_rows_cap, V, loss_sum, dlogits, grad_scale_base,
                       mean_over_rows, nullptr, (hipStream_t)stream);
+}
+// fine-tune heads and task losses: the launchers of csrc/kernels.h as they are (no arithmetic here)
+extern "C" int gget_op_score_fwd(const void* hidden, const int32_t* pool_row, const void* w, const void* bias, float* logits,
+                                 void* pooled_h, int B, int C, int d, void* stream) {
+  GGET_REQUIRE(hidden && pool_row && w && logits && B > 0 && C > 0 && d > 0, "score_fwd: null argument or empty shape");
+  return k_score_fwd(hidden, pool_row, w, bias, logits, pooled_h, B, C, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_score_bwd(const float* dlogits, const void* hidden, const int32_t* pool_row, const void* w, float* dw,
+                                 float* dbias, void* dhidden, int B, int C, int d, void* stream) {
+  GGET_REQUIRE(dlogits && hidden && pool_row && w && dw && dhidden && B > 0 && C > 0 && d > 0, "score_bwd: null argument or empty shape");
+  return k_score_bwd(dlogits, hidden, pool_row, w, dw, dbias, dhidden, B, C, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_tok_score_fwd(const void* hidden, const void* w, const void* bias, float* logits, int T, int C, int d,
+                                     void* stream) {
+  GGET_REQUIRE(hidden && w && logits && T >= 0 && C > 0, "tok_score_fwd: null argument or empty shape");
+  return k_tok_score_fwd(hidden, w, bias, logits, T, C, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_tok_ce(const float* logits, const int64_t* labels, float* dl, float* stat, float* loss_out, int T, int C,
+                              const int32_t* rows_map, int n_logical, void* stream) {
+  GGET_REQUIRE(logits && labels && dl && stat && loss_out && T >= 0 && C > 0, "tok_ce: null argument or empty shape");
+  return k_tok_ce(logits, labels, dl, stat, loss_out, T, C, (hipStream_t)stream, rows_map, n_logical);
+}
+extern "C" int gget_op_tok_score_bwd(const float* dl, const float* stat, const void* hidden, const void* w, float* dw, float* dbias,
+                                     void* dhidden, int T, int C, int d, void* stream) {
+  GGET_REQUIRE(dl && stat && hidden && w && dw && dhidden && T >= 0 && C > 0, "tok_score_bwd: null argument or empty shape");
+  GGET_REQUIRE(d % 64 == 0 && d > 0 && d <= 1024, "token-level head: d=%d unsupported", d);
+  return k_tok_score_bwd(dl, stat, hidden, w, dw, dbias, dhidden, T, C, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_task_loss(const float* logits, const void* labels, const float* sample_wgt, int problem, int B, int C,
+                                 float* loss_out, float* dlogits, void* stream) {
+  GGET_REQUIRE(logits && labels && loss_out && dlogits && B > 0 && C > 0, "task_loss: null argument or empty shape");
+  GGET_REQUIRE(problem == GGET_PROBLEM_SINGLE_LABEL || problem == GGET_PROBLEM_REGRESSION_L1 || problem == GGET_PROBLEM_REGRESSION_MSE ||
+                   problem == GGET_PROBLEM_MULTI_LABEL,
+               "task_loss: problem type %d has a kernel of its own", problem);
+  return k_task_loss(logits, labels, sample_wgt, problem, B, C, loss_out, dlogits, (hipStream_t)stream);
+}
+extern "C" int gget_op_auc_loss(const float* logits, const int64_t* labels, int B, int C, int num_neg, uint32_t seed, float* loss_out,
+                                float* dlogits, int32_t* lists, void* stream) {
+  GGET_REQUIRE(logits && labels && loss_out && dlogits && lists, "auc_loss: null argument");
+  return k_auc_loss(logits, labels, B, C, num_neg, seed, loss_out, dlogits, lists, (hipStream_t)stream);
+}
+extern "C" int gget_op_pool_rows(const void* hidden, const int32_t* pool_row, void* out, int B, int d, void* stream) {
+  GGET_REQUIRE(hidden && pool_row && out && B > 0 && d > 0, "pool_rows: null argument or empty shape");
+  return k_pool_rows(hidden, pool_row, out, B, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_scatter_rows_f32(const float* src, const int32_t* pool_row, void* dhidden, int B, int d, void* stream) {
+  GGET_REQUIRE(src && pool_row && dhidden && B > 0 && d > 0, "scatter_rows_f32: null argument or empty shape");
+  return k_scatter_rows_f32(src, pool_row, dhidden, B, d, (hipStream_t)stream);
+}
+// (head dropout off - the ElemDropArg of evaluation mode; the masks are tested through the whole model)
+extern "C" int gget_op_head_linear_fwd(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din,
+                                       int Dout, int layer, void* stream) {
+  GGET_REQUIRE(x && a && w && y && B > 0 && Din > 0 && Dout > 0, "head_linear_fwd: null argument or empty shape");
+  return k_head_linear_fwd(x, a, w, bias, y, y32, B, Din, Dout, layer, gget_engine::elem_drop(0.f, 0), (hipStream_t)stream);
+}
+extern "C" int gget_op_head_linear_bwd(const float* dy, const void* x, const void* a, const void* w, float* dw, float* dbias, float* dx,
+                                       int B, int Din, int Dout, int layer, void* stream) {
+  GGET_REQUIRE(dy && x && a && w && dw && dx && B > 0 && Din > 0 && Dout > 0, "head_linear_bwd: null argument or empty shape");
+  return k_head_linear_bwd(dy, x, a, w, dw, dbias, dx, B, Din, Dout, layer, gget_engine::elem_drop(0.f, 0), (hipStream_t)stream);
 }
 
 

@@ -1585,7 +1585,8 @@ __global__ void __launch_bounds__(kBlock) task_loss_kernel(const float* __restri
   red[threadIdx.x] = local;
   __syncthreads();
   for (int o = kBlock / 2; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) loss_out[0] = red[0];
+  // (multi-label with every label NaN: the reference's BCEWithLogitsLoss over an empty selection is NaN - so is this; dlogits are zeros)
+  if (threadIdx.x == 0) loss_out[0] = (problem == GGET_PROBLEM_MULTI_LABEL && !(wsum > 0.f)) ? __builtin_nanf("") : red[0];
 }
 
 // MLP score head (src/utils/modules_utils.py:8-34, chosen by `len(config.mlp) > 0` at modeling_finetune.py:88-97), on the pooled
@@ -3012,6 +3013,9 @@ __global__ void __launch_bounds__(kBlock) auc_loss_kernel(const float* __restric
 
 int k_auc_loss(const float* logits, const int64_t* labels, int B, int C, int num_neg, unsigned seed, float* loss_out,
                float* dlogits, int32_t* lists, hipStream_t st) {
+  // keys[] in LDS holds one entry per (positive, slot) pair; the number of positives is only known on the device, B bounds it
+  GGET_REQUIRE(B > 0 && C >= 2 && num_neg >= 1, "AUC loss: needs a batch, two logit columns and num_neg >= 1");
+  GGET_REQUIRE((long)B * num_neg <= kAucMaxPairs, "AUC loss: positives x num_neg is limited to %d pairs", kAucMaxPairs);
   hipLaunchKernelGGL(auc_loss_kernel, dim3(1), dim3(kBlock), 0, st, logits, labels, B, C, num_neg, seed, loss_out, dlogits, lists);
   GGET_LAUNCH_CHECK();
   return 0;

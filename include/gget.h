@@ -677,6 +677,43 @@ int gget_op_ce_fwd_bwd(const void* logits, int ld, const int32_t* labels, const 
                        int n_rows_cap, int V, float* loss_sum, void* dlogits, float grad_scale_base, int mean_over_rows,
                        void* stream);
 
+/* ---- fine-tune heads and task losses, one launcher each (the kernels gget_forward_task / gget_backward run after the last norm) ---- */
+/* logits[b,c] = bf16(hidden[pool_row[b]] . w[c] + bias[c]) as f32 [B,C]; pooled_h (optional) bf16 [B,d] = the gathered rows; bias may be NULL */
+int gget_op_score_fwd(const void* hidden, const int32_t* pool_row, const void* w, const void* bias, float* logits, void* pooled_h,
+                      int B, int C, int d, void* stream);
+/* dw f32 [C,d] += dlogits^T hidden[pool_row], dbias f32 [C] += column sums (NULL: none), dhidden[pool_row[b]] = bf16(dlogits[b] w): dhidden
+ * is zeroed by the caller and only the pooled rows are written */
+int gget_op_score_bwd(const float* dlogits, const void* hidden, const int32_t* pool_row, const void* w, float* dw, float* dbias,
+                      void* dhidden, int B, int C, int d, void* stream);
+/* token-level head: logits f32 [T,C] = bf16(hidden[t] . w[c] + bias[c]) on every row; d % 64 == 0 and d <= 1024, else error 2 */
+int gget_op_tok_score_fwd(const void* hidden, const void* w, const void* bias, float* logits, int T, int C, int d, void* stream);
+/* cross-entropy with ignore_index -100 over the rows: dl f32 [T,C] = softmax - onehot on labelled rows (not yet divided by their number n),
+ * zeros elsewhere; stat f32 [4] = {sum of row losses, n, 1/n (0 when n = 0), 0}; loss_out = mean, NaN when n = 0.  rows_map (optional,
+ * int32 [T]): row t reads labels[rows_map[t]], and carries no label when rows_map[t] >= n_logical */
+int gget_op_tok_ce(const float* logits, const int64_t* labels, float* dl, float* stat, float* loss_out, int T, int C,
+                   const int32_t* rows_map, int n_logical, void* stream);
+/* with g = bf16(dl * stat[2]): dhidden bf16 [T,d] = bf16(g w) (overwritten), dw f32 [C,d] += g^T hidden, dbias f32 [C] += column sums of g */
+int gget_op_tok_score_bwd(const float* dl, const float* stat, const void* hidden, const void* w, float* dw, float* dbias, void* dhidden,
+                          int T, int C, int d, void* stream);
+/* loss_out[0] and dlogits f32 [B,C] of GGET_PROBLEM_SINGLE_LABEL (labels int64 [B], optional sample_wgt f32 [B]), _REGRESSION_L1 / _MSE
+ * (labels f32 [B,C]) or _MULTI_LABEL (labels f32 [B,C], NaN = unlabelled; every label NaN: loss NaN, dlogits zeros) */
+int gget_op_task_loss(const float* logits, const void* labels, const float* sample_wgt, int problem, int B, int C, float* loss_out,
+                      float* dlogits, void* stream);
+/* AUC surrogate (see gget_set_auc) on logits f32 [B,C >= 2], labels int64 [B]; lists int32 [2B] scratch receives the ordered positive
+ * (at 0) and negative (at B) sample lists; B * num_neg <= 8192, else error 2; no positive or no negative: loss NaN, dlogits zeros */
+int gget_op_auc_loss(const float* logits, const int64_t* labels, int B, int C, int num_neg, uint32_t seed, float* loss_out,
+                     float* dlogits, int32_t* lists, void* stream);
+/* MLP score head: out bf16 [B,d] = hidden[pool_row]; dhidden[pool_row[b]] = bf16(src[b]) (other rows untouched) */
+int gget_op_pool_rows(const void* hidden, const int32_t* pool_row, void* out, int B, int d, void* stream);
+int gget_op_scatter_rows_f32(const float* src, const int32_t* pool_row, void* dhidden, int B, int d, void* stream);
+/* one Linear of the MLP head with the activation in front of it, dropout off: a bf16 [B,Din] = bf16(gelu(x)),
+ * y bf16 [B,Dout] = bf16(a w^T + bias), y32 (optional) the same values as f32 */
+int gget_op_head_linear_fwd(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din, int Dout,
+                            int layer, void* stream);
+/* its backward: dx f32 [B,Din] = (dy w) gelu'(x), dw f32 [Dout,Din] += dy^T a, dbias f32 [Dout] += column sums of dy (NULL: none) */
+int gget_op_head_linear_bwd(const float* dy, const void* x, const void* a, const void* w, float* dw, float* dbias, float* dx, int B,
+                            int Din, int Dout, int layer, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Rank metrics of the multi-label evaluation pass (csrc/metrics.hip; the Python surface is graph-gpt_amd/metrics.py rank_metrics).
  * replaces: MultiLabelClassificationMetrics.compute (src/utils/metrics_utils.py:112-114: torcheval BinaryAUROC over num_labels tasks),
