@@ -197,6 +197,7 @@ struct Ws {
   uint64_t raw_x, raw_xn, raw_rstd, raw_dxn, raw_dx, raw_flag;   // raw-embedding inputs: blended bf16 [T,e], normalised [T,e], 1/rms [T], their gradients, mask flags [T]
   uint64_t rr_cos, rr_sin, rr_ids;   // rope_range: per-token angle tables [T][32] fp32 and the identity position list [T] int64
   uint64_t tok_stat;   // token-level head: loss sum, labelled rows, 1 / rows
+  uint64_t intra_rs, intra_cls;   // intra-instance token head: first row of every sample (int32 [max_batch + 1]), cls_idx clamped (int64 [max_batch])
   uint64_t long_wgt;   // stack_method = "long": per-sample loss weights (fp32 [max_batch])
   // var-len token layout: first compact row of every sample [max_batch + 1], per compact row its sample index / position / ids, the
   // padded -> compact row map [max_tokens], a status word
@@ -327,6 +328,8 @@ Ws make_ws(const gget_config_t& c, const Plan& pl) {
     w.tlogits = b.take(std::max(Bm, T) * c.num_labels * 4);
     w.tdlogits = b.take(std::max(Bm, T) * c.num_labels * 4);
     w.tok_stat = b.take(256);
+    w.intra_rs = b.take((Bm + 1) * 4);
+    w.intra_cls = b.take(Bm * 8);
     w.auc_lists = b.take(Bm * 2 * 4);
     w.pooled_h = b.take(Bm * d * 2);
     if (pl.n_lin > 0) {
@@ -493,6 +496,7 @@ struct gget_engine {
   bool have_labels = false;
   int problem = 0;
   int auc_num_neg = 1;
+  const int64_t* cls_idx_next = nullptr;   // cls_idx of the NEXT forward_task (gget_set_cls_idx; loss_type = "token_ce_intra")
   float focal_gamma = 0.f;        // focal loss on the SMTP head (config.focal_gamma)
   bool stack_long = false;        // config.stack_method == "long" (gget_set_stack_method)
   float rope_range = 0.f;         // config.rope_range (gget_set_rope_range)
@@ -802,6 +806,12 @@ extern "C" int gget_set_auc(gget_handle_t h, int num_neg, uint32_t seed) {
   return 0;
 }
 
+extern "C" int gget_set_cls_idx(gget_handle_t h, const int64_t* cls_idx_dev) {
+  GGET_REQUIRE(h != nullptr, "null handle");
+  h->cls_idx_next = cls_idx_dev;
+  return 0;
+}
+
 extern "C" int gget_set_token_count(gget_handle_t h, int64_t n_real_tokens) {
   GGET_REQUIRE(h != nullptr, "null handle");
   h->tc_next = n_real_tokens > 0 ? (long)n_real_tokens : (n_real_tokens == GGET_TOKENS_AUTO ? (long)GGET_TOKENS_AUTO : -1);
@@ -831,8 +841,12 @@ extern "C" int gget_deferred_status(gget_handle_t h, int32_t out[2], void* strea
   int32_t* st = h->wsp<int32_t>(h->ws.vl_status);
   GGET_HIP_CHECK(hipMemcpyAsync(&out[0], st + 1, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   GGET_HIP_CHECK(hipMemcpyAsync(&out[1], st + 2, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  int32_t cls_clamped = 0;      // (vl_status[4]: a cls_idx outside its sample, raised by intra_plan_kernel)
+  GGET_HIP_CHECK(hipMemcpyAsync(&cls_clamped, st + 4, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   GGET_HIP_CHECK(hipMemsetAsync(st + 1, 0, 8, (hipStream_t)stream));
+  GGET_HIP_CHECK(hipMemsetAsync(st + 4, 0, 4, (hipStream_t)stream));
   GGET_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  if (cls_clamped) out[0] |= 2;
   return 0;
 }
 
@@ -1728,8 +1742,12 @@ extern "C" int gget_forward_task(gget_handle_t h, const int64_t* input_ids_dev, 
   GGET_REQUIRE(h != nullptr, "null argument");
   const long tc_hint = h->tc_next;   // (consumed at entry: see forward_pretrain_impl)
   h->tc_next = -1;
+  const int64_t* cls_idx_dev = h->cls_idx_next;   // (consumed the same way)
+  h->cls_idx_next = nullptr;
   GGET_REQUIRE(input_ids_dev, "null argument");
   GGET_REQUIRE(h->cfg.kind == GGET_KIND_TASK, "handle was not created as a task model");
+  const bool tok = problem_type == GGET_PROBLEM_TOKEN_CE || problem_type == GGET_PROBLEM_TOKEN_CE_INTRA;   // logits / labels per row
+  GGET_REQUIRE(problem_type != GGET_PROBLEM_TOKEN_CE_INTRA || cls_idx_dev, "the intra-instance token head needs cls_idx (gget_set_cls_idx)");
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
   CallScope scope(h);
@@ -1739,7 +1757,7 @@ extern "C" int gget_forward_task(gget_handle_t h, const int64_t* input_ids_dev, 
   const Ws& w = h->ws;
   const int d = c.hidden_size, C = c.num_labels;
   float* lg = h->wsp<float>(w.tlogits);
-  GGET_REQUIRE(problem_type != GGET_PROBLEM_TOKEN_CE || h->plan.n_lin == 0, "the token-level head is the Linear `score` (no MLP head)");
+  GGET_REQUIRE(!tok || h->plan.n_lin == 0, "the token-level head is the Linear `score` (no MLP head)");
   if (h->plan.n_lin > 0) {
     const Plan& pl = h->plan;
     if (int e = k_pool_rows(h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.pool_row), h->wsp<bf16_t>(w.pooled_h), B, d, st)) return e;
@@ -1755,11 +1773,19 @@ extern "C" int gget_forward_task(gget_handle_t h, const int64_t* input_ids_dev, 
                                 d, st))
       return e;
     if (int e = k_pool_rows(h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.pool_row), h->wsp<bf16_t>(w.pooled_h), B, d, st)) return e;
+  } else if (problem_type == GGET_PROBLEM_TOKEN_CE_INTRA) {
+    // intra-instance token head (loss_type = "token_ce_intra", modeling_finetune.py:140-165): the logits of `score` are discarded for
+    // 20 <h^_s, h^_{cls_idx + c}> inside every sample; one row-start array serves both token layouts
+    if (int e = k_intra_plan(cls_idx_dev, h->wsp<int32_t>(w.key_len), h->varlen ? h->wsp<int32_t>(w.vl_cu) : nullptr, h->wsp<int32_t>(w.intra_rs),
+                             h->wsp<int64_t>(w.intra_cls), h->wsp<int32_t>(w.vl_status) + 4, B, S, C, st))
+      return e;
+    if (int e = k_tok_intra_fwd(h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.intra_rs), h->wsp<int64_t>(w.intra_cls), lg, B, C, d, st)) return e;
+    if (int e = k_pool_rows(h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.pool_row), h->wsp<bf16_t>(w.pooled_h), B, d, st)) return e;
   } else if (int e = k_score_fwd(h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.pool_row), h->P + h->plan.score,
                                  c.score_bias ? h->P + h->plan.sbias : nullptr, lg, h->wsp<bf16_t>(w.pooled_h), B, C, d, st))
     return e;
-  const int rows = problem_type == GGET_PROBLEM_TOKEN_CE ? h->T : B;   // rows of the logits
-  const bool tok_vl = problem_type == GGET_PROBLEM_TOKEN_CE && h->varlen;   // token-level logits of compact rows: back to [B,S,C] order
+  const int rows = tok ? h->T : B;   // rows of the logits
+  const bool tok_vl = tok && h->varlen;   // token-level logits of compact rows: back to [B,S,C] order
   if (task_logits_dev && tok_vl) {
     GGET_HIP_CHECK(hipMemsetAsync(task_logits_dev, 0, (size_t)B * S * C * 4, st));      // (padded positions: zeros)
     if (int e = k_scatter_rows_map_f32(lg, h->wsp<int32_t>(w.vl_c2p), task_logits_dev, h->T, C, B * S, st)) return e;
@@ -1775,7 +1801,7 @@ extern "C" int gget_forward_task(gget_handle_t h, const int64_t* input_ids_dev, 
       if (int e = k_auc_loss(lg, (const int64_t*)task_labels_dev, B, C, h->auc_num_neg, h->auc_seed, loss_dev,
                              h->wsp<float>(w.tdlogits), h->wsp<int32_t>(w.auc_lists), st))
         return e;
-    } else if (problem_type == GGET_PROBLEM_TOKEN_CE) {
+    } else if (tok) {
       if (int e = k_tok_ce(lg, (const int64_t*)task_labels_dev, h->wsp<float>(w.tdlogits), h->wsp<float>(w.tok_stat), loss_dev, rows, C, st,
                            tok_vl ? h->wsp<int32_t>(w.vl_c2p) : nullptr, B * S))
         return e;
@@ -2125,6 +2151,12 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
       dy = dx;
     }
     if (int e = k_scatter_rows_f32(dy, h->wsp<int32_t>(w.pool_row), dhid, h->B, d, st)) return e;
+  } else if (h->problem == GGET_PROBLEM_TOKEN_CE_INTRA) {
+    // (`score` is outside the graph: its gradient stays the zero the accumulators start from, as do the var-len layout's round-up rows
+    //  behind the last sample, which belong to no workgroup of the kernel)
+    if (int e = k_tok_intra_bwd(h->wsp<float>(w.tdlogits), h->wsp<float>(w.tok_stat), h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.intra_rs),
+                                h->wsp<int64_t>(w.intra_cls), dhid, h->B, c.num_labels, d, st))
+      return e;
   } else if (h->problem == GGET_PROBLEM_TOKEN_CE) {
     if (int e = k_tok_score_bwd(h->wsp<float>(w.tdlogits), h->wsp<float>(w.tok_stat), h->wsp<bf16_t>(w.hidden), h->P + h->plan.score,
                                 s32 + h->plan.score32, c.score_bias ? s32 + h->plan.sbias32 : nullptr, dhid, h->T, c.num_labels, d, st))   // (h->T: the rows of the token-major buffers)
@@ -2887,6 +2919,16 @@ extern "C" int gget_op_tok_score_fwd(const void* hidden, const void* w, const vo
                                      void* stream) {
   GGET_REQUIRE(hidden && w && logits && T >= 0 && C > 0, "tok_score_fwd: null argument or empty shape");
   return k_tok_score_fwd(hidden, w, bias, logits, T, C, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_tok_intra_fwd(const void* hidden, const int32_t* row_start, const int64_t* cls_idx, float* logits, int B, int C,
+                                     int d, void* stream) {
+  GGET_REQUIRE(hidden && row_start && cls_idx && logits && B >= 0, "tok_intra_fwd: null argument or empty shape");
+  return k_tok_intra_fwd(hidden, row_start, cls_idx, logits, B, C, d, (hipStream_t)stream);
+}
+extern "C" int gget_op_tok_intra_bwd(const float* dl, const float* stat, const void* hidden, const int32_t* row_start,
+                                     const int64_t* cls_idx, void* dhidden, int B, int C, int d, void* stream) {
+  GGET_REQUIRE(dl && stat && hidden && row_start && cls_idx && dhidden && B >= 0, "tok_intra_bwd: null argument or empty shape");
+  return k_tok_intra_bwd(dl, stat, hidden, row_start, cls_idx, dhidden, B, C, d, (hipStream_t)stream);
 }
 extern "C" int gget_op_tok_ce(const float* logits, const int64_t* labels, float* dl, float* stat, float* loss_out, int T, int C,
                               const int32_t* rows_map, int n_logical, void* stream) {

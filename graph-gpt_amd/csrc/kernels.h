@@ -102,6 +102,16 @@ int k_rows_to_grid(const void* src, const int32_t* pad2c, void* out, long n_pos,
 int k_scatter_rows_map_f32(const float* src, const int32_t* rows_map, float* dst, int T, int C, int n_logical, hipStream_t st);
 int k_tok_score_bwd(const float* dl, const float* stat, const void* hidden, const void* w, float* dw, float* dbias, void* dhidden, int T,
                     int C, int d, hipStream_t st);
+// intra-instance token head (loss_type = "token_ce_intra"): logits[s,c] = bf16(20 <h^_s, h^_{k_b+c}>) over the rows
+// row_start[b] .. row_start[b+1] of every sample (h^ = the L2-normalised row, k_b = cls_idx[b] clamped into the sample), and its
+// backward from k_tok_ce's dl / stat (dhidden is overwritten for the rows of every sample).  d % 64 == 0, d <= 1024, 2 <= C <= 64.
+int k_tok_intra_fwd(const void* hidden, const int32_t* row_start, const int64_t* cls_idx, float* logits, int B, int C, int d,
+                    hipStream_t st);
+int k_tok_intra_bwd(const float* dl, const float* stat, const void* hidden, const int32_t* row_start, const int64_t* cls_idx,
+                    void* dhidden, int B, int C, int d, hipStream_t st);
+// row_start (cu of the var-len layout, or b S when cu is NULL) and cls_idx clamped into [0, key_len[b] - C] (*flag = 1 where it was not)
+int k_intra_plan(const int64_t* cls_idx, const int32_t* key_len, const int32_t* cu, int32_t* row_start, int64_t* cls_safe, int32_t* flag,
+                 int B, int S, int C, hipStream_t st);
 int k_pool_rows(const void* hidden, const int32_t* pool_row, void* out, int B, int d, hipStream_t st);
 int k_head_linear_fwd(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din, int Dout,
                       int layer, ElemDropArg E, hipStream_t st);

@@ -1507,6 +1507,303 @@ __global__ void __launch_bounds__(kBlock) tok_score_bwd_dw_kernel(const float* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Intra-instance token head (loss_type = "token_ce_intra", modeling_finetune.py:140-165): every row of a sample is classified against
+// label embeddings that are C rows of the SAME sample, h^_s = h_s / max(|h_s|, 1e-12), e^_c = h^_{k+c} (k = cls_idx[b]),
+// logits[s,c] = 20 <h^_s, e^_c>.  One workgroup of 8 waves per sample (rows row_start[b] .. row_start[b+1]).  The C label rows stay in
+// LDS as the bf16 values they are (C d 2 bytes <= 128 KB) with their fp32 1 / norms next to them: a product with e^_c is a product with
+// the raw row times one scalar, so nothing is rounded to bf16 on the way.  A lane holds the column pairs (128 q + 2 lane, + 1): one
+// dword per load from memory and from LDS (ds_read_b32, conflict-free).  Norms, dots and the normalise-backward are fp32; a logit and
+// a dhidden element are rounded to bf16 once.  cls_idx is clamped into [0, rows - C]; a sample of fewer than C rows gets zeros.
+// ---------------------------------------------------------------------------------------------
+constexpr int kIntraBlock = 512, kIntraWaves = kIntraBlock / 64;
+constexpr int kIntraPairs = 8;          // d <= 128 * kIntraPairs
+constexpr int kIntraChunk = 64;         // rows per round of the backward
+constexpr float kIntraInvTemp = 20.f, kIntraEps = 1e-12f;
+
+__device__ __forceinline__ void intra_load_raw(const bf16_t* __restrict__ row, int d, int lane, unsigned (&raw)[kIntraPairs]) {
+#pragma unroll
+  for (int q = 0; q < kIntraPairs; ++q) {
+    const int j = q * 128 + 2 * lane;
+    raw[q] = (row && j < d) ? *reinterpret_cast<const unsigned*>(row + j) : 0u;
+  }
+}
+__device__ __forceinline__ void intra_unpack(const unsigned (&raw)[kIntraPairs], float (&f)[2 * kIntraPairs]) {
+#pragma unroll
+  for (int q = 0; q < kIntraPairs; ++q) {
+    f[2 * q] = __uint_as_float(raw[q] << 16);
+    f[2 * q + 1] = __uint_as_float(raw[q] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ float intra_inv_norm(const float (&f)[2 * kIntraPairs]) {
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < 2 * kIntraPairs; ++i) ss = fmaf(f[i], f[i], ss);
+  return 1.0f / fmaxf(sqrtf(wave_sum(ss)), kIntraEps);
+}
+// rows rs .. rs + n of sample b and its first label row k (clamped); false: no rows, or fewer than C (zeros are written)
+__device__ __forceinline__ bool intra_sample(const int32_t* __restrict__ row_start, const int64_t* __restrict__ cls_idx, int b, int C,
+                                             int& rs, int& n, int& k) {
+  rs = row_start[b];
+  n = row_start[b + 1] - rs;
+  const int64_t v = cls_idx[b];
+  k = n >= C ? (int)(v < 0 ? 0 : (v > n - C ? n - C : v)) : 0;
+  return n >= C;
+}
+// the label rows (raw) and 1 / max(norm, eps) of each into LDS: a wave per row
+__device__ __forceinline__ void intra_stage_labels(const bf16_t* __restrict__ hidden, int rs, int k, int C, int d, bf16_t* E, float* einv) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = wave; c < C; c += kIntraWaves) {
+    unsigned raw[kIntraPairs];
+    float f[2 * kIntraPairs];
+    intra_load_raw(hidden + (size_t)(rs + k + c) * d, d, lane, raw);
+    intra_unpack(raw, f);
+    const float inv = intra_inv_norm(f);
+#pragma unroll
+    for (int q = 0; q < kIntraPairs; ++q) {
+      const int j = q * 128 + 2 * lane;
+      if (j < d) *reinterpret_cast<unsigned*>(E + (size_t)c * d + j) = raw[q];
+    }
+    if (lane == 0) einv[c] = inv;
+  }
+}
+__global__ void __launch_bounds__(kIntraBlock) tok_intra_fwd_kernel(const bf16_t* __restrict__ hidden, const int32_t* __restrict__ row_start,
+                                                                    const int64_t* __restrict__ cls_idx, float* __restrict__ logits, int C,
+                                                                    int d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char intra_lds[];
+  bf16_t* E = reinterpret_cast<bf16_t*>(intra_lds);                           // [C][d]
+  float* einv = reinterpret_cast<float*>(intra_lds + (size_t)C * d * 2);      // [64]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int rs, n, k;
+  if (!intra_sample(row_start, cls_idx, blockIdx.x, C, rs, n, k)) {
+    for (long i = threadIdx.x; i < (long)n * C; i += kIntraBlock) logits[(size_t)rs * C + i] = 0.f;
+    return;
+  }
+  intra_stage_labels(hidden, rs, k, C, d, E, einv);
+  __syncthreads();
+  for (int t0 = wave * kTokRows; t0 < n; t0 += kIntraWaves * kTokRows) {
+    float hv[kTokRows][2 * kIntraPairs], inv[kTokRows], out[kTokRows];
+#pragma unroll
+    for (int r = 0; r < kTokRows; ++r) {
+      unsigned raw[kIntraPairs];
+      intra_load_raw(t0 + r < n ? hidden + (size_t)(rs + t0 + r) * d : nullptr, d, lane, raw);
+      intra_unpack(raw, hv[r]);
+      inv[r] = intra_inv_norm(hv[r]);
+      out[r] = 0.f;
+    }
+    for (int c = 0; c < C; ++c) {      // lane c keeps class c of every row (C <= 64)
+      unsigned raw[kIntraPairs];
+      float ev[2 * kIntraPairs];
+#pragma unroll
+      for (int q = 0; q < kIntraPairs; ++q) {
+        const int j = q * 128 + 2 * lane;
+        raw[q] = j < d ? *reinterpret_cast<const unsigned*>(E + (size_t)c * d + j) : 0u;
+      }
+      intra_unpack(raw, ev);
+      const float ec = einv[c];
+#pragma unroll
+      for (int r = 0; r < kTokRows; ++r) {
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2 * kIntraPairs; ++i) a = fmaf(hv[r][i], ev[i], a);
+        a = wave_sum(a);
+        if (lane == c) out[r] = bf2f(f2bf(kIntraInvTemp * (a * inv[r] * ec)));
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kTokRows; ++r)
+      if (t0 + r < n && lane < C) logits[(size_t)(rs + t0 + r) * C + lane] = out[r];
+  }
+}
+// Backward.  z[s,c] = 20 bf16(dl[s,c] stat[2]).  Rows go through the workgroup in rounds of kIntraChunk: (a) the round's z into LDS;
+// (b) row owners (a wave, two rows at a time): 1 / norm of every row, and for a row that is no label row dh^_s = sum_c z[s,c] e^_c and
+// dh_s = (dh^_s - h^_s <h^_s, dh^_s>) / norm, written at once (zeros for a row whose z is all zero: no dot work); (c) column owners
+// (thread t: columns 2t, 2t + 1, NC accumulators each): de^_c += z[s,c] h^_s over the round's rows with a non-zero z, in row order.
+// After the last round the column owners add the label rows' own sum_c' z[k+c,c'] e^_c' onto de^_c, take <h^_{k+c}, .> through one
+// block reduction per label row and write the label rows.  Every sum has a fixed order: no atomics, two runs agree bit for bit.
+template <int NC>
+__global__ void __launch_bounds__(kIntraBlock) tok_intra_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ stat,
+                                                                    const bf16_t* __restrict__ hidden, const int32_t* __restrict__ row_start,
+                                                                    const int64_t* __restrict__ cls_idx, bf16_t* __restrict__ dhidden, int C,
+                                                                    int d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char intra_lds[];
+  bf16_t* E = reinterpret_cast<bf16_t*>(intra_lds);                           // [C][d]
+  float* einv = reinterpret_cast<float*>(intra_lds + (size_t)C * d * 2);      // [64]
+  float* zc = einv + 64;                                                      // [kIntraChunk][NC]; at the end [NC][NC]
+  float* rinv = zc + kIntraChunk * NC;                                        // [kIntraChunk]
+  int* rflag = reinterpret_cast<int*>(rinv + kIntraChunk);                    // [kIntraChunk]
+  float* red = reinterpret_cast<float*>(rflag + kIntraChunk);                 // [NC][kIntraWaves]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int rs, n, k;
+  if (!intra_sample(row_start, cls_idx, blockIdx.x, C, rs, n, k)) {
+    for (long i = tid; i < (long)n * d; i += kIntraBlock) dhidden[(size_t)rs * d + i] = 0;
+    return;
+  }
+  const float inv_n = stat[2];
+  intra_stage_labels(hidden, rs, k, C, d, E, einv);
+  for (int c = C + tid; c < 64; c += kIntraBlock) einv[c] = 0.f;
+  float acc0[NC], acc1[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) { acc0[c] = 0.f; acc1[c] = 0.f; }
+  const int jc = 2 * tid;
+  const bool own = jc < d;
+  constexpr int kRowsPerWave = kIntraChunk / kIntraWaves;
+  for (int s0 = 0; s0 < n; s0 += kIntraChunk) {
+    __syncthreads();      // (the label rows in the first round; the previous round's readers of zc / rinv / rflag after it)
+    for (int i = tid; i < kIntraChunk * NC; i += kIntraBlock) {
+      const int s = s0 + i / NC, c = i % NC;
+      zc[i] = (s < n && c < C) ? kIntraInvTemp * bf2f(f2bf(dl[(size_t)(rs + s) * C + c] * inv_n)) : 0.f;
+    }
+    __syncthreads();
+    for (int rr = 0; rr < kRowsPerWave; rr += 2) {
+      const int r0 = wave * kRowsPerWave + rr;
+      float hv[2][2 * kIntraPairs], inv[2];
+      bool work[2], plain[2];      // work: dh^ is computed; plain: the row is written here (it exists and is no label row)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int s = s0 + r0 + u;
+        unsigned raw[kIntraPairs];
+        intra_load_raw(s < n ? hidden + (size_t)(rs + s) * d : nullptr, d, lane, raw);
+        intra_unpack(raw, hv[u]);
+        inv[u] = intra_inv_norm(hv[u]);
+        const bool live = __any(lane < NC && zc[(r0 + u) * NC + (lane < NC ? lane : 0)] != 0.f) != 0;
+        plain[u] = s < n && !(s >= k && s < k + C);
+        work[u] = live && plain[u];
+        if (lane == 0) { rinv[r0 + u] = inv[u]; rflag[r0 + u] = live && s < n; }
+      }
+      float a[2][2 * kIntraPairs];
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int i = 0; i < 2 * kIntraPairs; ++i) a[u][i] = 0.f;
+      if (work[0] || work[1]) {
+        for (int c = 0; c < C; ++c) {
+          const float ec = einv[c];
+          const float z0 = work[0] ? zc[r0 * NC + c] * ec : 0.f, z1 = work[1] ? zc[(r0 + 1) * NC + c] * ec : 0.f;
+          if (z0 == 0.f && z1 == 0.f) continue;
+          unsigned raw[kIntraPairs];
+          float ev[2 * kIntraPairs];
+#pragma unroll
+          for (int q = 0; q < kIntraPairs; ++q) {
+            const int j = q * 128 + 2 * lane;
+            raw[q] = j < d ? *reinterpret_cast<const unsigned*>(E + (size_t)c * d + j) : 0u;
+          }
+          intra_unpack(raw, ev);
+#pragma unroll
+          for (int i = 0; i < 2 * kIntraPairs; ++i) {
+            a[0][i] = fmaf(z0, ev[i], a[0][i]);
+            a[1][i] = fmaf(z1, ev[i], a[1][i]);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (!plain[u]) continue;
+        bf16_t* dp = dhidden + (size_t)(rs + s0 + r0 + u) * d;
+        float dot = 0.f;
+        if (work[u]) {
+#pragma unroll
+          for (int i = 0; i < 2 * kIntraPairs; ++i) {
+            hv[u][i] *= inv[u];      // h^
+            dot = fmaf(hv[u][i], a[u][i], dot);
+          }
+          dot = wave_sum(dot);
+        }
+#pragma unroll
+        for (int q = 0; q < kIntraPairs; ++q) {
+          const int j = q * 128 + 2 * lane;
+          if (j >= d) continue;
+          unsigned o = 0u;
+          if (work[u])
+            o = pack2bf((a[u][2 * q] - hv[u][2 * q] * dot) * inv[u], (a[u][2 * q + 1] - hv[u][2 * q + 1] * dot) * inv[u]);
+          *reinterpret_cast<unsigned*>(dp + j) = o;
+        }
+      }
+    }
+    __syncthreads();
+    if (own) {
+      const int rows = min(kIntraChunk, n - s0);
+      for (int r = 0; r < rows; ++r) {
+        if (!rflag[r]) continue;
+        const unsigned raw = *reinterpret_cast<const unsigned*>(hidden + (size_t)(rs + s0 + r) * d + jc);
+        const float ri = rinv[r];
+        const float h0 = __uint_as_float(raw << 16) * ri, h1 = __uint_as_float(raw & 0xffff0000u) * ri;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const float z = zc[r * NC + c];
+          acc0[c] = fmaf(z, h0, acc0[c]);
+          acc1[c] = fmaf(z, h1, acc1[c]);
+        }
+      }
+    }
+  }
+  // the label rows: zc[c'][c] = z[k + c, c']
+  __syncthreads();
+  for (int i = tid; i < NC * NC; i += kIntraBlock) {
+    const int cp = i / NC, c = i % NC;
+    zc[i] = (cp < C && c < C) ? kIntraInvTemp * bf2f(f2bf(dl[(size_t)(rs + k + c) * C + cp] * inv_n)) : 0.f;
+  }
+  __syncthreads();
+  if (own) {
+    for (int cp = 0; cp < C; ++cp) {
+      const unsigned raw = *reinterpret_cast<const unsigned*>(E + (size_t)cp * d + jc);
+      const float ec = einv[cp];
+      const float e0 = __uint_as_float(raw << 16) * ec, e1 = __uint_as_float(raw & 0xffff0000u) * ec;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const float z = zc[cp * NC + c];
+        acc0[c] = fmaf(z, e0, acc0[c]);
+        acc1[c] = fmaf(z, e1, acc1[c]);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    if (c < C) {      // (uniform; the loop is unrolled whole: the accumulators stay in registers)
+      float p = 0.f;
+      if (own) {
+        const unsigned raw = *reinterpret_cast<const unsigned*>(E + (size_t)c * d + jc);
+        const float ec = einv[c];
+        p = fmaf(__uint_as_float(raw << 16) * ec, acc0[c], __uint_as_float(raw & 0xffff0000u) * ec * acc1[c]);
+      }
+      p = wave_sum(p);
+      if (lane == 0) red[c * kIntraWaves + wave] = p;
+    }
+  }
+  __syncthreads();
+  if (own) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      if (c < C) {
+        float dot = 0.f;
+#pragma unroll
+        for (int w = 0; w < kIntraWaves; ++w) dot += red[c * kIntraWaves + w];
+        const unsigned raw = *reinterpret_cast<const unsigned*>(E + (size_t)c * d + jc);
+        const float ec = einv[c];
+        const float h0 = __uint_as_float(raw << 16) * ec, h1 = __uint_as_float(raw & 0xffff0000u) * ec;
+        *reinterpret_cast<unsigned*>(dhidden + (size_t)(rs + k + c) * d + jc) = pack2bf((acc0[c] - h0 * dot) * ec, (acc1[c] - h1 * dot) * ec);
+      }
+    }
+  }
+}
+// row_start / clamped cls_idx of a forward: row_start[b] = cu[b] (var-len layout) or b S; cls_idx[b] into [0, len_b - C], *flag raised
+// (sticky) where it was outside or the sample has fewer than C real rows
+__global__ void __launch_bounds__(kBlock) intra_plan_kernel(const int64_t* __restrict__ cls_idx, const int32_t* __restrict__ key_len,
+                                                            const int32_t* __restrict__ cu, int32_t* __restrict__ row_start,
+                                                            int64_t* __restrict__ cls_safe, int32_t* __restrict__ flag, int B, int S, int C) {
+  bool bad = false;
+  for (int b = blockIdx.x * kBlock + threadIdx.x; b <= B; b += gridDim.x * kBlock) {
+    row_start[b] = cu ? cu[b] : b * S;
+    if (b < B) {
+      const int hi = key_len[b] - C;
+      const int64_t v = cls_idx[b];
+      bad |= hi < 0 || v < 0 || v > hi;
+      cls_safe[b] = hi < 0 || v < 0 ? 0 : (v > hi ? hi : v);
+    }
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1;
+}
+
 // task loss + dlogits (calculate_task_loss, modeling_finetune.py:167-234); single block.
 __global__ void __launch_bounds__(kBlock) task_loss_kernel(const float* __restrict__ logits, const void* __restrict__ labels,
                                                            const float* __restrict__ sample_wgt, int problem, int B, int C,
@@ -2943,6 +3240,45 @@ int k_tok_score_bwd(const float* dl, const float* stat, const void* hidden, cons
                      (const bf16_t*)w, (bf16_t*)dhidden, T, C, d);
   hipLaunchKernelGGL(tok_score_bwd_dw_kernel, dim3((T + kTokSlab - 1) / kTokSlab, (C + kTokCls - 1) / kTokCls), dim3(kBlock), 0, st, dl,
                      stat, (const bf16_t*)hidden, dw, dbias, T, C, d);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+#define GGET_INTRA_REQUIRE(C, d)                                                                                         \
+  GGET_REQUIRE((d) % 64 == 0 && (d) <= 128 * kIntraPairs && (C) >= 2 && (C) <= 64,                                       \
+               "intra-instance token head: d=%d, C=%d unsupported (d %% 64 == 0, d <= 1024, 2 <= C <= 64)", (d), (C))
+int k_tok_intra_fwd(const void* hidden, const int32_t* row_start, const int64_t* cls_idx, float* logits, int B, int C, int d,
+                    hipStream_t st) {
+  GGET_INTRA_REQUIRE(C, d);
+  if (B == 0) return 0;
+  const int lds = C * d * 2 + 64 * 4;
+  GGET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tok_intra_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(tok_intra_fwd_kernel, dim3(B), dim3(kIntraBlock), lds, st, (const bf16_t*)hidden, row_start, cls_idx, logits, C, d);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+template <int NC>
+static int tok_intra_bwd_launch(const float* dl, const float* stat, const void* hidden, const int32_t* row_start, const int64_t* cls_idx,
+                                void* dhidden, int B, int C, int d, hipStream_t st) {
+  const int lds = C * d * 2 + 64 * 4 + kIntraChunk * NC * 4 + kIntraChunk * 8 + NC * kIntraWaves * 4;
+  GGET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tok_intra_bwd_kernel<NC>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(tok_intra_bwd_kernel<NC>, dim3(B), dim3(kIntraBlock), lds, st, dl, stat, (const bf16_t*)hidden, row_start, cls_idx,
+                     (bf16_t*)dhidden, C, d);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+int k_tok_intra_bwd(const float* dl, const float* stat, const void* hidden, const int32_t* row_start, const int64_t* cls_idx,
+                    void* dhidden, int B, int C, int d, hipStream_t st) {
+  GGET_INTRA_REQUIRE(C, d);
+  if (B == 0) return 0;
+#define GGET_INTRA_BWD(NC) tok_intra_bwd_launch<NC>(dl, stat, hidden, row_start, cls_idx, dhidden, B, C, d, st)
+  return C <= 8 ? GGET_INTRA_BWD(8) : C <= 16 ? GGET_INTRA_BWD(16) : C <= 32 ? GGET_INTRA_BWD(32) : C <= 48 ? GGET_INTRA_BWD(48) : GGET_INTRA_BWD(64);
+#undef GGET_INTRA_BWD
+}
+int k_intra_plan(const int64_t* cls_idx, const int32_t* key_len, const int32_t* cu, int32_t* row_start, int64_t* cls_safe, int32_t* flag,
+                 int B, int S, int C, hipStream_t st) {
+  hipLaunchKernelGGL(intra_plan_kernel, dim3(grid_for(B + 1, kBlock, 64)), dim3(kBlock), 0, st, cls_idx, key_len, cu, row_start, cls_safe,
+                     flag, B, S, C);
   GGET_LAUNCH_CHECK();
   return 0;
 }

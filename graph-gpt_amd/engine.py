@@ -348,12 +348,12 @@ class Engine:
         pos = self._i64(position_ids, dev)
         y = None
         if task_labels is not None:
-            if problem in (L.PROBLEM_SINGLE_LABEL, L.PROBLEM_AUC, L.PROBLEM_TOKEN_CE):
+            if problem in (L.PROBLEM_SINGLE_LABEL, L.PROBLEM_AUC, L.PROBLEM_TOKEN_CE, L.PROBLEM_TOKEN_CE_INTRA):
                 y = task_labels.to(device=dev, dtype=torch.int64).contiguous()
             else:
                 y = task_labels.to(device=dev, dtype=torch.float32).contiguous()
         wgt = None if sample_wgt is None else sample_wgt.to(device=dev, dtype=torch.float32).contiguous()
-        if problem == L.PROBLEM_TOKEN_CE:   # token-level task: labels and logits per row
+        if problem in (L.PROBLEM_TOKEN_CE, L.PROBLEM_TOKEN_CE_INTRA):   # token-level task: labels and logits per row
             assert y is None or tuple(y.shape) == (B, S), f"token-level labels must be [B,S], got {tuple(y.shape)}"
             logits = torch.empty(B, S, self.spec.num_labels, dtype=torch.float32, device=dev)
         else:
@@ -425,16 +425,28 @@ class Engine:
         return bool(out.value)
 
     def deferred_status(self):
-        """(positions clamped, var-len token count / label mismatch) since the last call (gget_deferred_status); clears both; synchronises."""
+        """(positions clamped, var-len token count / label mismatch) since the last call (gget_deferred_status); clears both; synchronises.
+        `self.cls_idx_clamped` is set when a cls_idx of the intra-instance token head lay outside its sample since the last call."""
         out = (C.c_int32 * 2)()
         L.check(self.lib.gget_deferred_status(self.h, out, _stream()))
-        return bool(out[0]), bool(out[1])
+        self.cls_idx_clamped = bool(out[0] & 2)
+        return bool(out[0] & 1), bool(out[1])
 
     def varlen_status(self):
         """(ran var-len, rows, count mismatch) of the last forward; synchronises."""
         out = (C.c_int32 * 3)()
         L.check(self.lib.gget_varlen_status(self.h, out, _stream()))
         return bool(out[0]), int(out[1]), bool(out[2])
+
+    def set_cls_idx(self, cls_idx):
+        """cls_idx [B] of the NEXT forward_task(problem=PROBLEM_TOKEN_CE_INTRA): the first label row inside every sample (gget_set_cls_idx).
+        The tensor is kept alive until the next call; None clears it."""
+        if cls_idx is None:
+            self._cls_keep = None
+            L.check(self.lib.gget_set_cls_idx(self.h, None))
+            return
+        self._cls_keep = cls_idx.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        L.check(self.lib.gget_set_cls_idx(self.h, _ptr(self._cls_keep)))
 
     def set_auc(self, num_neg: int = 1, seed: int = 0):
         """Negatives per positive and the sampling seed of the NEXT forward_task(problem=PROBLEM_AUC)."""

@@ -442,6 +442,23 @@ class _GgetModel(nn.Module):
                 raise IndexError(f"position_ids must lie in [0, max_position_embeddings = {maxp}); got [{lo}, {hi}] - build the model "
                                  "with a larger max_position_embeddings")
 
+    def _check_cls_idx(self, cls_idx, attention_mask, B, S):
+        """loss_type = "token_ce_intra": the num_labels label rows cls_idx[b] .. cls_idx[b] + num_labels - 1 must be real rows of sample b
+        (the reference's advanced indexing raises IndexError past the sequence and silently reads padding inside it).  The rule of
+        _check_positions: HOST tensors are checked here, DEVICE tensors are clamped by the engine and reported by check_deferred()."""
+        assert cls_idx.numel() == B, f"cls_idx must hold one index per sample ({B}), got {tuple(cls_idx.shape)}"
+        if not (cls_idx.device.type == "cpu" or os.environ.get("GGET_CHECK_INPUTS")):
+            return
+        idx = cls_idx.reshape(-1).to(torch.int64).cpu()
+        if attention_mask.dim() == 2 and (attention_mask.device.type == "cpu" or os.environ.get("GGET_CHECK_INPUTS")):
+            lens = (attention_mask != 0).sum(-1).to(torch.int64).cpu()
+        else:
+            lens = torch.full((B,), S, dtype=torch.int64)
+        bad = (idx < 0) | (idx + self.num_labels > lens)
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise IndexError(f"cls_idx[{b}] = {int(idx[b])}: the {self.num_labels} label rows must lie inside the sample's {int(lens[b])} rows")
+
     def check_deferred(self):
         """Raise what the per-step device-side guards recorded since the last call (one stream sync): position_ids outside the RoPE
         table (IndexError, as _check_positions raises for host tensors); a var-len step whose `num_tokens` disagreed with its
@@ -451,6 +468,9 @@ class _GgetModel(nn.Module):
         if e is None:
             return
         clamped, mismatch = e.deferred_status()
+        if e.cls_idx_clamped:
+            raise IndexError(f"cls_idx outside [0, sample length - num_labels = {self.num_labels}] was passed to a forward since the last check "
+                             "(the engine clamped it into the sample: results diverge from the reference)")
         if clamped:
             raise IndexError(f"position_ids outside [0, max_position_embeddings = {self.spec.max_position}) were passed to a forward since "
                              "the last check (the engine clamped them into the RoPE table: results diverge from the reference) - build "
@@ -579,12 +599,15 @@ class GraphGPTTaskModel(_GgetModel):
         if problem == "regression":
             code = L.PROBLEM_REGRESSION_L1 if cfg.loss_type == "l1" else L.PROBLEM_REGRESSION_MSE
         elif problem in ("single_label_classification", None):
-            if cfg.loss_type == "token_ce_intra":
-                raise NotImplementedError("loss_type='token_ce_intra' (intra-instance label embeddings) is outside the hot-path scope")
-            # "token_ce" (node-level tasks): `score` and the cross-entropy on every row, task_logits [B,S,num_labels]
-            code = L.PROBLEM_TOKEN_CE if cfg.loss_type == "token_ce" else (L.PROBLEM_AUC if cfg.loss_type == "auc" else L.PROBLEM_SINGLE_LABEL)
-            if code == L.PROBLEM_TOKEN_CE and len(cfg.mlp) > 0:
-                raise NotImplementedError("loss_type='token_ce' with an MLP score head is outside the hot-path scope")
+            # "token_ce" (node-level tasks): `score` and the cross-entropy on every row, task_logits [B,S,num_labels]; "token_ce_intra": the
+            # same with every row classified against the label rows of its own sample (modeling_finetune.py:140-165)
+            code = {"token_ce": L.PROBLEM_TOKEN_CE, "token_ce_intra": L.PROBLEM_TOKEN_CE_INTRA, "auc": L.PROBLEM_AUC}.get(cfg.loss_type, L.PROBLEM_SINGLE_LABEL)
+            if code in (L.PROBLEM_TOKEN_CE, L.PROBLEM_TOKEN_CE_INTRA) and len(cfg.mlp) > 0:
+                raise NotImplementedError(f"loss_type='{cfg.loss_type}' with an MLP score head is outside the hot-path scope")
+            if code == L.PROBLEM_TOKEN_CE_INTRA:
+                if cls_idx is None:
+                    raise ValueError("loss_type='token_ce_intra' needs cls_idx [B]: the first label row of every sample")
+                self._check_cls_idx(cls_idx, attention_mask, B, S)
         else:
             code = L.PROBLEM_MULTI_LABEL   # BCE-with-logits on the labelled entries (modeling_finetune.py:227-230)
         self._check_positions(position_ids, S)
@@ -597,6 +620,8 @@ class GraphGPTTaskModel(_GgetModel):
             e.set_auc(cfg.num_neg or 1, self.last_auc_seed)
         if inputs_raw_embeds is not None:
             e.set_raw_embeds(inputs_raw_embeds)
+        if code == L.PROBLEM_TOKEN_CE_INTRA:
+            e.set_cls_idx(cls_idx)
         loss, logits, hid = e.forward_task(input_ids, attention_mask, position_ids, task_labels, sample_wgt, code, num_tokens=n_real)
         return DoubleHeadsModelOutput(pretrain_loss=None, task_loss=self._wrap_loss(loss), pretrain_logits=None,
                                       task_logits=logits, task_hidden_states=hid,

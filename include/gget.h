@@ -36,6 +36,7 @@ extern "C" {
 #define GGET_PROBLEM_REGRESSION_L1 1 /* L1Loss  (modeling_finetune.py:183-197) */
 #define GGET_PROBLEM_REGRESSION_MSE 2 /* MSELoss */
 #define GGET_PROBLEM_TOKEN_CE 5 /* loss_type = "token_ce" (node-level tasks, modeling_finetune.py:162-164, :198-202): `score` on EVERY row, task_labels int64 [B,S] with -100 = unlabelled, mean cross-entropy over the labelled rows; task_logits_dev is then f32 [B,S,num_labels] (the reference hands the all-row logits back as `task_logits`), with or without labels */
+#define GGET_PROBLEM_TOKEN_CE_INTRA 6 /* loss_type = "token_ce_intra" (modeling_finetune.py:140-165, :198-202): as GGET_PROBLEM_TOKEN_CE, but the logits of `score` are replaced by 20 <h^_s, h^_{cls_idx[b]+c}>, h^ = the L2-normalised final hidden row - every row against the num_labels label rows of its own sample; needs gget_set_cls_idx before the forward; `score` gets a zero gradient */
 #define GGET_PROBLEM_AUC 4 /* pairwise squared-hinge AUC surrogate on logit[:,1]-logit[:,0] (src/utils/loss_utils.py:25-53, modeling_finetune.py:203-207); see gget_set_auc */
 #define GGET_PROBLEM_MULTI_LABEL 3 /* BCEWithLogitsLoss on the non-NaN entries of float labels [B,num_labels] (modeling_finetune.py:227-230) */
 
@@ -167,6 +168,7 @@ int gget_varlen_status(gget_handle_t h, int32_t out[3], void* stream);
  * mask contradicted, or met a label at a padded position (see gget_set_token_count).  replaces: the IndexError / shape error the
  * reference's nn.Embedding / rotary embedding raise synchronously for such inputs. */
 int gget_deferred_status(gget_handle_t h, int32_t out[2], void* stream);
+/* (out[0] is a bit set: 1 = position_ids clamped, 2 = a cls_idx of gget_set_cls_idx lay outside its sample and was clamped) */
 
 /* replaces: `embed_pdrop` / `mlp_pdrop` of the config + model.train()/eval(): nn.Dropout on the gathered token embeddings
  * (modeling_helpers.py:96-98) and the two dropouts of the decoder MLP - on act(gate)*up and on down_proj's output
@@ -206,6 +208,13 @@ int gget_set_focal_gamma(gget_handle_t h, float gamma);
  * positive and the seed of the counter-hash permutation the NEXT gget_forward_task(problem_type = GGET_PROBLEM_AUC) draws its
  * negative samples with (idx = perm(P * num_neg) % N_neg; perm = rank of the hashed keys). */
 int gget_set_auc(gget_handle_t h, int num_neg, uint32_t seed);
+
+/* replaces: the `cls_idx` argument of GraphGPTTaskModel.forward (modeling_finetune.py:236-250; tokenizer_utils.py:729-747 appends the
+ * label tokens and records where they start): int64 [B] on the device, the first of the num_labels label rows inside every sample, read
+ * by the NEXT gget_forward_task(problem_type = GGET_PROBLEM_TOKEN_CE_INTRA), which keeps its own clamped copy for the backward (the
+ * pointer is consumed by that forward: set it before every call; such a forward without it is error 2).  0 <= cls_idx[b] and cls_idx[b] + num_labels <= the sample's real row
+ * count; a value outside is clamped into that range and reported by gget_deferred_status (bit 2 of out[0]). */
+int gget_set_cls_idx(gget_handle_t h, const int64_t* cls_idx_dev);
 
 /* replaces: load_state_dict + `.to(bfloat16)`: refresh the bf16 compute copy from the fp32 master. */
 int gget_sync_params(gget_handle_t h, void* stream);
@@ -695,6 +704,17 @@ int gget_op_tok_ce(const float* logits, const int64_t* labels, float* dl, float*
 /* with g = bf16(dl * stat[2]): dhidden bf16 [T,d] = bf16(g w) (overwritten), dw f32 [C,d] += g^T hidden, dbias f32 [C] += column sums of g */
 int gget_op_tok_score_bwd(const float* dl, const float* stat, const void* hidden, const void* w, float* dw, float* dbias, void* dhidden,
                           int T, int C, int d, void* stream);
+/* intra-instance token head (GGET_PROBLEM_TOKEN_CE_INTRA).  Sample b owns the rows row_start[b] .. row_start[b+1] (int32 [B+1]; gaps
+ * between samples are allowed: b S on a padded grid) of hidden bf16 [rows,d]; k_b = cls_idx[b] (int64 [B]) clamped into [0, rows_b - C].
+ * logits f32 [rows,C]: logits[s,c] = bf16(20 <h^_s, h^_{k_b+c}>), h^ = h / max(|h|, 1e-12), for the rows of every sample (other rows are
+ * not written; a sample of fewer than C rows gets zeros).  d % 64 == 0, d <= 1024, 2 <= C <= 64, else error 2 ("unsupported"). */
+int gget_op_tok_intra_fwd(const void* hidden, const int32_t* row_start, const int64_t* cls_idx, float* logits, int B, int C, int d,
+                          void* stream);
+/* with z = 20 bf16(dl * stat[2]) (dl, stat of gget_op_tok_ce): dh^_s = sum_c z[s,c] h^_{k+c}, + sum_s' z[s',c] h^_s' on label row k + c;
+ * dhidden bf16 [rows,d] = bf16((dh^ - h^ <h^, dh^>) / max(|h|, 1e-12)), overwritten for the rows of every sample (zeros where nothing
+ * flows).  No atomics: two calls give the same bits. */
+int gget_op_tok_intra_bwd(const float* dl, const float* stat, const void* hidden, const int32_t* row_start, const int64_t* cls_idx,
+                          void* dhidden, int B, int C, int d, void* stream);
 /* loss_out[0] and dlogits f32 [B,C] of GGET_PROBLEM_SINGLE_LABEL (labels int64 [B], optional sample_wgt f32 [B]), _REGRESSION_L1 / _MSE
  * (labels f32 [B,C]) or _MULTI_LABEL (labels f32 [B,C], NaN = unlabelled; every label NaN: loss NaN, dlogits zeros) */
 int gget_op_task_loss(const float* logits, const void* labels, const float* sample_wgt, int problem, int B, int C, float* loss_out,

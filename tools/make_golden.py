@@ -811,6 +811,48 @@ def token_ce_fixture():
     print(f"ft_tiny_tokence written: loss {res['loss']:.6f}, logits {res['logits'].shape}, labelled rows {(lab >= 0).sum()}")
 
 
+def token_ce_intra_fixture():
+    """Intra-instance token head (config.loss_type = "token_ce_intra", modeling_finetune.py:140-165; the tokenizer appends the label
+    tokens and records cls_idx, src/utils/tokenizer_utils.py:729-747): every row against the L2-normalised hidden states of the C label
+    rows of its own sample, here its last C real rows.  5 classes; labels -100 on the label rows and the pads, about a third of the other
+    real rows labelled, one sample without any labelled row.  `score` is outside the graph: its gradient is None, recorded as 0."""
+    PT, FT, Cfg = import_reference()
+    C = 5
+    spec = spec_mod.spec_from_size("tiny", kind=spec_mod.KIND_TASK, vocab_size=756, stacked_feat=13, next_n_token=1, num_labels=C)
+    state = weights_mod.make_state_dict(spec, seed=1511, std=0.06, head_std=0.3)
+    batch = synth.make_task_batch(B=10, S=24, F=13, V=756, seed=151)
+    lens = batch.pop("lengths").astype(np.int64)
+    assert int(lens.min()) >= C + 2
+    cls_idx = lens - C
+    rs = np.random.RandomState(15)
+    pos = np.arange(24)[None, :]
+    other = pos < cls_idx[:, None]                     # the real rows in front of the label rows
+    lab = rs.randint(0, C, size=other.shape).astype(np.int64)
+    lab[~other | (rs.uniform(size=other.shape) > 0.35)] = -100
+    lab[3] = -100                                      # a sample without a labelled row
+    batch["task_labels"] = lab
+    batch["cls_idx"] = cls_idx
+    tb = {k: torch.from_numpy(v) for k, v in batch.items()}
+    model = FT(ref_config(Cfg, spec, num_labels=C, loss_type="token_ce_intra", problem_type="single_label_classification"))
+    load_weights(model, state)
+    model.eval()
+    o = model(input_ids=tb["input_ids"], attention_mask=tb["attention_mask"], position_ids=tb["position_ids"],
+              task_labels=tb["task_labels"], cls_idx=tb["cls_idx"])
+    model.zero_grad()
+    o.task_loss.backward()
+    names = list(state.keys())
+    g = dict(model.named_parameters())
+    assert g["score.weight"].grad is None
+    res = {"loss": np.float64(o.task_loss.item()), "logits": o.task_logits.detach().float().numpy(), "cls_idx": cls_idx,
+           "grad_norms": grad_norms(model, names), "names": np.array(names),
+           "grad_l1_down": g["model.layers.1.mlp.down_proj.weight"].grad.numpy().copy(),
+           "meta_spec": np.array(spec.as_c_ints(), np.int64), "meta_init": np.array([1511, 0.06, 0.3])}
+    for k, v in batch.items():
+        res["in_" + k] = v
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "ft_tiny_tokence_intra.npz"), **res)
+    print(f"ft_tiny_tokence_intra written: loss {res['loss']:.6f}, logits {res['logits'].shape}, labelled rows {(lab >= 0).sum()}")
+
+
 def rope_range_fixture():
     """config.rope_range = 6 (utils_graphgpt.reset_pos_ids :574-581): the fine-tune model with arbitrary position ids per row,
     rescaled to [0, 6) before the rotary embedding - fractional positions."""
@@ -1134,6 +1176,8 @@ def main():
         long_fixture()
     if not only or "ft_tiny_tokence" in only:
         token_ce_fixture()
+    if not only or "ft_tiny_tokence_intra" in only:
+        token_ce_intra_fixture()
     if not only or "ft_tiny_roperange" in only:
         rope_range_fixture()
     if not only or "tiny_rawembed" in only:
