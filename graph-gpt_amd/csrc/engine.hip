@@ -2904,6 +2904,48 @@ extern "C" int gget_op_ce_fwd_bwd(const void* logits, int ld, const int32_t* lab
   return k_ce_fwd_bwd(logits, ld, labels, nullptr, nullptr, 1, n_rows_dev, n_rows_cap, V, loss_sum, dlogits, grad_scale_base,
                       mean_over_rows, nullptr, (hipStream_t)stream);
 }
+// test-only entries of the RMSNorm and cross-entropy families: every argument of the launcher, no arithmetic here
+extern "C" int gget_op_rmsnorm_bwd_copies(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
+                                          float* dw_accum, int T, int d, int copies, uint64_t copy_stride, void* stream) {
+  GGET_REQUIRE(dy && x && w && rstd && dx && dw_accum && T >= 0 && copies >= 1 && copy_stride >= (uint64_t)d, "rmsnorm_bwd_copies: bad arguments");
+  return k_rmsnorm_bwd(dy, x, w, rstd, dres, dx, dw_accum, T, d, (hipStream_t)stream, copies, copy_stride);
+}
+extern "C" int gget_op_rmsnorm_dw(const void* dy, const void* x, const float* rstd, float* dw_accum, int T, int d, int copies,
+                                  uint64_t copy_stride, void* stream) {
+  GGET_REQUIRE(dy && x && rstd && dw_accum && T >= 0 && copies >= 1 && copy_stride >= (uint64_t)d, "rmsnorm_dw: bad arguments");
+  return k_rmsnorm_dw(dy, x, rstd, dw_accum, T, d, (hipStream_t)stream, copies, copy_stride);
+}
+extern "C" int gget_op_ls_rmsnorm_fwd(const void* res, const void* y, const void* lam, void* out, const void* w, void* xn, float* rstd, int T,
+                                      int d, float eps, void* stream) {
+  GGET_REQUIRE(res && y && out && w && xn && rstd && T >= 0, "ls_rmsnorm_fwd: null argument");
+  GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "ls_rmsnorm_fwd: d=%d unsupported", d);
+  if (T == 0) return 0;
+  return ls_rmsnorm_fwd((const bf16_t*)res, (const bf16_t*)y, (const bf16_t*)lam, (bf16_t*)out, (const bf16_t*)w, (bf16_t*)xn, rstd, T, d, eps,
+                        PathDropArg{0.f, 0u, 1, nullptr}, ElemDropArg{0, 1.f, 0}, (hipStream_t)stream);
+}
+extern "C" int gget_op_accum_layout(int d, int* copies, uint64_t* copy_stride) {
+  GGET_REQUIRE(copies && copy_stride && d > 0, "accum_layout: bad arguments");
+  *copies = kAccumCopies;
+  *copy_stride = align_up((uint64_t)d, 128);
+  return 0;
+}
+extern "C" int gget_op_rmsnorm_bwd_ls(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
+                                      float* dw_accum, const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d,
+                                      void* stream) {
+  GGET_REQUIRE(dy && x && w && rstd && dx && dw_accum && y && dsc && T >= 0, "rmsnorm_bwd_ls: null argument");
+  GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "rmsnorm_bwd_ls: d=%d unsupported", d);
+  return rmsnorm_bwd_ls((const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, dw_accum, (const bf16_t*)y,
+                        (const bf16_t*)lam, (bf16_t*)dsc, dlam_accum, T, d, PathDropArg{0.f, 0u, 1, nullptr}, ElemDropArg{0, 1.f, 0},
+                        (hipStream_t)stream);
+}
+extern "C" int gget_op_ce_full(const void* logits, int ld, const int32_t* labels, const int32_t* sel_tok, const float* sample_wgt, int S,
+                               const int32_t* n_rows_dev, int n_rows_cap, int V, float* loss_sum, void* dlogits, float scale_base,
+                               int mean_over_rows, float* loss_out, float focal_gamma, float* loss_part, int loss_part_cap, void* stream) {
+  GGET_REQUIRE(logits && labels && loss_sum && n_rows_cap >= 0 && V >= 1 && ld >= V, "ce_full: bad arguments");
+  GGET_REQUIRE(!sample_wgt || (sel_tok && S >= 1), "ce_full: sample weights need sel_tok and S >= 1");
+  return k_ce_fwd_bwd(logits, ld, labels, sel_tok, sample_wgt, S, n_rows_dev, n_rows_cap, V, loss_sum, dlogits, scale_base, mean_over_rows,
+                      loss_out, (hipStream_t)stream, focal_gamma, loss_part, loss_part_cap);
+}
 // fine-tune heads and task losses: the launchers of csrc/kernels.h as they are (no arithmetic here)
 extern "C" int gget_op_score_fwd(const void* hidden, const int32_t* pool_row, const void* w, const void* bias, float* logits,
                                  void* pooled_h, int B, int C, int d, void* stream) {

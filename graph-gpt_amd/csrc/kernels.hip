@@ -1323,8 +1323,10 @@ __global__ void __launch_bounds__(kBlock) ce_rows_kernel(const bf16_t* __restric
 
 // loss_part != nullptr: the blocks of ce_rows_kernel left one partial sum each (n_part of them) - summed here in a fixed order, the total
 // also goes to loss_sum[0] (what the atomics of the other form accumulate)
-__global__ void __launch_bounds__(256) finalize_loss_kernel(float* loss_sum, const int32_t* n_rows_dev, float scale_base, int mean_over_rows,
-                                                            float* loss_out, const float* __restrict__ loss_part, int n_part) {
+// n_rows = min(n_rows_cap, *n_rows_dev) as the row kernels count it (n_rows_dev may be nullptr: n_rows_cap rows).
+__global__ void __launch_bounds__(256) finalize_loss_kernel(float* loss_sum, const int32_t* n_rows_dev, int n_rows_cap, float scale_base,
+                                                            int mean_over_rows, float* loss_out, const float* __restrict__ loss_part,
+                                                            int n_part) {
   __shared__ float red[4];
   if (loss_part) {
     float a = 0.f;
@@ -1336,7 +1338,8 @@ __global__ void __launch_bounds__(256) finalize_loss_kernel(float* loss_sum, con
     __syncthreads();
   }
   if (threadIdx.x == 0 && loss_out) {
-    const float sc = mean_over_rows ? (*n_rows_dev > 0 ? 1.0f / (float)(*n_rows_dev) : 0.f) : scale_base;
+    const int n_rows = min(n_rows_cap, n_rows_dev ? *n_rows_dev : n_rows_cap);
+    const float sc = mean_over_rows ? (n_rows > 0 ? 1.0f / (float)n_rows : 0.f) : scale_base;
     loss_out[0] = loss_sum[0] * sc;
   }
 }
@@ -3191,8 +3194,8 @@ int k_ce_fwd_bwd(const void* logits, int ld, const int32_t* labels, const int32_
 #undef GGET_CE_ARGS
   }
   if (loss_out || parts)
-    hipLaunchKernelGGL(finalize_loss_kernel, dim3(1), dim3(256), 0, st, loss_sum, n_rows_dev, scale_base, mean_over_rows, loss_out,
-                       parts ? loss_part : nullptr, (int)grid.x);
+    hipLaunchKernelGGL(finalize_loss_kernel, dim3(1), dim3(256), 0, st, loss_sum, n_rows_dev, n_rows_cap, scale_base, mean_over_rows,
+                       loss_out, parts ? loss_part : nullptr, (int)grid.x);
   GGET_LAUNCH_CHECK();
   return 0;
 }

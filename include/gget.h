@@ -529,7 +529,8 @@ int gget_op_gemm_grouped(int mode, int count, const void* const* A, const void* 
  *   per CU, same bits).  key 14 = 0: the engine's cross-entropy launch adds its loss with one atomic per block (1, default: one partial sum
  *   per block, summed in block order by the finalising launch).  key 15 = R: every GEMM launch plan counts the device's CUs minus R (0,
  *   default: the whole chip; a data-parallel handle sets its own with gget_set_dp_menu).  key 16 = 1: gget_debug_occupy's stand-in takes
- *   the register footprint of RCCL's kernel (264 registers per lane) besides the LDS asked for. */
+ *   the register footprint of RCCL's kernel (264 registers per lane) besides the LDS asked for.  key 19 = 1: the cross-entropy launch never
+ *   takes the row-in-registers kernels (what the presence of GGET_CE_GENERIC selects at load). */
 int gget_debug_set(int key, int value);
 int gget_debug_get(int key, int* value);
 /* measurement aid: with enable != 0 the engine brackets, with HIP events on the launch stream, the grouped weight-gradient launch
@@ -685,6 +686,38 @@ int gget_op_geglu_bwd(const void* gu, const void* dh, void* dgu, int T, int ff, 
 int gget_op_ce_fwd_bwd(const void* logits, int ld, const int32_t* labels, const float* row_wgt, const int32_t* n_rows_dev,
                        int n_rows_cap, int V, float* loss_sum, void* dlogits, float grad_scale_base, int mean_over_rows,
                        void* stream);
+
+/* ---- test-only entries of the RMSNorm and cross-entropy kernel families: the launcher with every argument, no arithmetic of their own ---- */
+/* gget_op_rmsnorm_bwd with the replicated accumulator: block b adds its weight-gradient partial to dw_accum[(b % copies) * copy_stride + j]
+ * (dw_accum: copies * copy_stride floats, copy_stride >= d; the weight gradient is the sum of the replicas).  In the reproducible mode
+ * (gget_debug_set(4, 1)) the sum goes into the first replica in block order. */
+int gget_op_rmsnorm_bwd_copies(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, float* dw_accum,
+                               int T, int d, int copies, uint64_t copy_stride, void* stream);
+/* the weight gradient of gget_op_rmsnorm_bwd_copies alone: dw[j] += sum_r dy[r,j] * (x[r,j] * rstd[r]); no dx.  In the reproducible mode
+ * the bits are those of the full backward's 4-wave form. */
+int gget_op_rmsnorm_dw(const void* dy, const void* x, const float* rstd, float* dw_accum, int T, int d, int copies, uint64_t copy_stride,
+                       void* stream);
+/* out = bf16(res + bf16(lam * y)) (lam bf16 [d] or NULL = 1), then xn = w * bf16(out * rstd), rstd[r] = rsqrt(mean(out[r]^2) + eps) on the
+ * ROUNDED out, in one launch; DropPath and element dropout off.  d % 8 == 0, d <= 2048. */
+int gget_op_ls_rmsnorm_fwd(const void* res, const void* y, const void* lam, void* out, const void* w, void* xn, float* rstd, int T, int d,
+                           float eps, void* stream);
+/* the layout gget_op_rmsnorm_bwd_ls accumulates into: *copies replicas (kAccumCopies), *copy_stride = align_up(d, 128) floats apart */
+int gget_op_accum_layout(int d, int* copies, uint64_t* copy_stride);
+/* RMSNorm backward fused with the LayerScale backward behind it: dx = bf16(dres + rstd (dy w - xhat mean(dy w xhat))) (dres may be NULL),
+ * dsc = bf16(lam * dx) on the rounded dx (lam may be NULL = 1), dw_accum += sum_r dy xhat, dlam_accum += sum_r dx y (dlam_accum may be
+ * NULL); dropout off.  BOTH accumulators are [kAccumCopies][align_up(d, 128)] floats (gget_op_accum_layout returns the two numbers); the
+ * gradient is the sum of the replicas. */
+int gget_op_rmsnorm_bwd_ls(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, float* dw_accum,
+                           const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d, void* stream);
+/* gget_op_ce_fwd_bwd with every argument of the launcher: row weight sample_wgt[sel_tok[row] / S] (f32, both NULL = 1) times the focal
+ * weight (1 - p_label)^focal_gamma (0 = off); n = min(n_rows_cap, *n_rows_dev) rows (n_rows_dev NULL: n_rows_cap); loss_sum[0] = the
+ * weighted sum of the row losses; dlogits bf16 [n_rows_cap, ld] (may be NULL) = (softmax - onehot) * weight * (mean_over_rows ? 1 / n :
+ * scale_base) on the first n rows, zeros in the columns V..ld, rows past n untouched; loss_out (may be NULL) = loss_sum * that scale.
+ * loss_part (may be NULL; loss_part_cap floats): one partial sum per block instead of an atomic when the row-in-registers kernels run and
+ * the grid fits into it. */
+int gget_op_ce_full(const void* logits, int ld, const int32_t* labels, const int32_t* sel_tok, const float* sample_wgt, int S,
+                    const int32_t* n_rows_dev, int n_rows_cap, int V, float* loss_sum, void* dlogits, float scale_base, int mean_over_rows,
+                    float* loss_out, float focal_gamma, float* loss_part, int loss_part_cap, void* stream);
 
 /* ---- fine-tune heads and task losses, one launcher each (the kernels gget_forward_task / gget_backward run after the last norm) ---- */
 /* logits[b,c] = bf16(hidden[pool_row[b]] . w[c] + bias[c]) as f32 [B,C]; pooled_h (optional) bf16 [B,d] = the gathered rows; bias may be NULL */
