@@ -225,3 +225,7 @@ int k_unmask_origin(int64_t* x, const int64_t* cand, int B, int N, float p_trans
 int k_token_confidence(const void* logits, int ld, int R, int V, int mode, float* conf, int64_t* tok, hipStream_t st);
 int k_smtp_rows(const int64_t* ids_in, const int32_t* lengths, int64_t* ids_out, int64_t* labels_out, float* wgt_out, int B, int S,
                 int F, double umr_min, double umr_max, double power, unsigned seed, hipStream_t st);
+// Evaluation metrics (metrics.hip) launch from their own C-ABI entries: gget_op_rank_metrics, gget_op_link_hits, gget_op_link_mrr and
+// gget_op_cluster_metrics (include/gget.h).  The last keeps four int32 class tables of C entries beside one staging tile in dynamic LDS:
+constexpr int kClusterMaxC = GGET_CLUSTER_MAX_C;
+static_assert(4 * 4 * kClusterMaxC == 32 * 1024, "gget_op_cluster_metrics: the class tables are budgeted at 32 KiB of LDS");

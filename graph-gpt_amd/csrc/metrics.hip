@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "kernels.h"
 #include "../../include/gget.h"
 
 namespace {
@@ -588,7 +589,219 @@ inline int link_grid(long units) {                // workgroups for `units` work
   return (int)(units < 1 ? 1 : units > cap ? cap : units);
 }
 
+// ------------------------------------------------------------------------------------------------ graph clustering: token-level heads
+// replaces: GraphClusteringMetrics.update (src/utils/metrics_utils.py:231-295: torch.argmax, two .nonzero() per sample) and
+// `get_acc_per_graph` (:340-348: per distinct label and per distinct prediction one .nonzero(), one .unique() and one len(...) - a
+// device-to-host synchronisation each, inside a Python loop over the samples).  As counts: over the kept positions of a sample (selected:
+// raw_node_idx != -100; kept: selected and label != -100), recall = t_r / n_r with n_r = distinct labels and t_r = those whose positions
+// all carry one prediction; precision = t_p / n_p with the roles swapped.  No sort and no ordered atomic: four int32 tables of C entries
+// in LDS - per label value the min and max prediction seen, per prediction value the min and max label seen - filled with LDS integer
+// min / max atomics; a value is present when its max was written, its group uniform when min == max.  Every output is an exact integer,
+// independent of lane order and launch geometry.
+//
+// One launch, one workgroup per sample (grid-stride over samples).  The arg-max (first index of the maximum, a NaN is maximal and the
+// first NaN wins, -0.0 ties +0.0) has two lane mappings:
+//   C <= kClusterStageC  the sample's logits are one contiguous run of S * C floats: tiles of whole rows (at most kClusterTile floats)
+//                        are copied to LDS with adjacent lanes on adjacent addresses - 16-byte loads on the tile's 16-byte aligned body,
+//                        the LDS image shifted by the pointer's misalignment so that the 16-byte LDS stores are aligned too - then a
+//                        lane scans one row out of LDS.  For an even C lane t starts its row at column t % C and wraps, which spreads the
+//                        lanes of a bank group over the banks (row stride C dwords); the comparison carries the column, so the order of
+//                        the scan does not matter.
+//   C >  kClusterStageC  a wave per row, lane l the columns l, l + 64, ... straight from global memory, then a wave reduction.
+constexpr int kClusterBlock = 256;
+constexpr int kClusterWaves = kClusterBlock / 64;
+constexpr int kClusterTile = 4096;       // floats of one LDS tile (16 KiB): 64 rows at C = 64, 512 at C = 8
+constexpr int kClusterStageC = 64;
+constexpr long long kClusterIgnore = -100;
+
+// the arg-max order: does (v, j) go in front of (best, bj)?
+__device__ __forceinline__ bool cluster_gt(float v, float best) { return v > best || (v != v && best == best); }
+__device__ __forceinline__ bool cluster_before(float v, int j, float best, int bj) {
+  return cluster_gt(v, best) || (!cluster_gt(best, v) && j < bj);
+}
+
+struct ClusterTables {
+  int *lab_min, *lab_max, *prd_min, *prd_max;
+};
+
+// one position with its prediction: totals in registers, the four tables through LDS atomics
+__device__ __forceinline__ void cluster_visit(long long pred, long long lab, long long raw, int C, bool check_pred, const ClusterTables& T,
+                                              int (&tot)[4]) {
+  if (raw == kClusterIgnore) return;
+  const bool labelled = lab != kClusterIgnore;
+  if ((labelled && (lab < 0 || lab >= C)) || (check_pred && (pred < 0 || pred >= C))) {
+    ++tot[3];
+    return;
+  }
+  ++tot[2];
+  if (!labelled) return;
+  ++tot[1];
+  tot[0] += pred == lab;
+  const int p = (int)pred, y = (int)lab;       // both inside [0, C): the table indices are in bounds
+  atomicMin(&T.lab_min[y], p);
+  atomicMax(&T.lab_max[y], p);
+  atomicMin(&T.prd_min[p], y);
+  atomicMax(&T.prd_max[p], y);
+}
+
+__global__ void __launch_bounds__(kClusterBlock) cluster_kernel(const void* __restrict__ pred_or_logits, int is_logits,
+                                                                const long long* __restrict__ labels, const long long* __restrict__ raw_node_idx,
+                                                                int B, int S, int C, long long* __restrict__ y_pred,
+                                                                int32_t* __restrict__ counts, unsigned long long* __restrict__ totals) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char cluster_smem[];
+  float* tile = reinterpret_cast<float*>(cluster_smem);                         // kClusterTile + 4 floats
+  int* cnt = reinterpret_cast<int*>(cluster_smem) + kClusterTile + 4;           // t_r, n_r, t_p, n_p of the sample
+  int* blk = cnt + 4;                                                           // the workgroup's share of the four totals
+  ClusterTables T;
+  T.lab_min = blk + 4;
+  T.lab_max = T.lab_min + C;
+  T.prd_min = T.lab_max + C;
+  T.prd_max = T.prd_min + C;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int tot[4] = {0, 0, 0, 0};                                                    // n_correct, n_kept, n_selected, n_bad of this thread
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const size_t row0 = (size_t)b * S;
+    const long long* lab_b = labels + row0;
+    const long long* raw_b = raw_node_idx + row0;
+    long long* out_b = y_pred + row0;
+    for (int c = t; c < C; c += kClusterBlock) {
+      T.lab_min[c] = T.prd_min[c] = 0x7fffffff;
+      T.lab_max[c] = T.prd_max[c] = -1;
+    }
+    if (t < 4) cnt[t] = 0;          // (thread t read cnt[t] of the previous sample itself: program order)
+    __syncthreads();
+    if (!is_logits) {
+      const long long* pr = reinterpret_cast<const long long*>(pred_or_logits) + row0;
+      for (int s = t; s < S; s += kClusterBlock) {
+        const long long p = pr[s];
+        out_b[s] = p;
+        cluster_visit(p, lab_b[s], raw_b[s], C, true, T, tot);
+      }
+    } else if (C <= kClusterStageC) {
+      const float* lg = reinterpret_cast<const float*>(pred_or_logits) + row0 * C;
+      const int rows_per_tile = kClusterTile / C;                              // >= 64
+      for (int r0 = 0; r0 < S; r0 += rows_per_tile) {
+        const int nrows = min(rows_per_tile, S - r0), n = nrows * C;           // n <= kClusterTile floats at g[0, n)
+        const float* g = lg + (size_t)r0 * C;
+        const int pad = (int)(((uintptr_t)g >> 2) & 3u);                       // g + head is 16-byte aligned, and so is img + head
+        const int head = min(n, (4 - pad) & 3);
+        const int nvec = (n - head) >> 2, rest = head + 4 * nvec;
+        float* img = tile + pad;                                                // img[0, n): the last index is pad + n - 1 <= kClusterTile + 2
+        const float4* g4 = reinterpret_cast<const float4*>(g + head);
+        long long lab0 = 0, raw0 = kClusterIgnore;                              // the lane's first row of the tile: asked for with the logits
+        if (t < nrows) {
+          lab0 = lab_b[r0 + t];
+          raw0 = raw_b[r0 + t];
+        }
+        for (int v = t; v < nvec; v += kClusterBlock) *reinterpret_cast<float4*>(img + head + 4 * v) = g4[v];
+        if (t < head) img[t] = g[t];
+        else if (t - head < n - rest) img[rest + t - head] = g[rest + t - head];
+        __syncthreads();
+        for (int r = t; r < nrows; r += kClusterBlock) {
+          const float* row = img + r * C;
+          int j = (C & 1) ? 0 : t % C;
+          float best = row[j];
+          int bj = j;
+          for (int k = 1; k < C; ++k) {
+            j = j + 1 == C ? 0 : j + 1;
+            const float v = row[j];
+            if (cluster_before(v, j, best, bj)) {
+              best = v;
+              bj = j;
+            }
+          }
+          const int s = r0 + r;
+          out_b[s] = bj;
+          cluster_visit(bj, r == t ? lab0 : lab_b[s], r == t ? raw0 : raw_b[s], C, false, T, tot);
+        }
+        __syncthreads();                                                        // the tile is overwritten by the next round
+      }
+    } else {
+      const float* lg = reinterpret_cast<const float*>(pred_or_logits) + row0 * C;
+      for (int s = wave; s < S; s += kClusterWaves) {
+        const float* row = lg + (size_t)s * C;
+        float best = row[lane];                                                 // C > 64: every lane owns a column
+        int bj = lane;
+        for (int j = lane + 64; j < C; j += 64) {
+          const float v = row[j];
+          if (cluster_gt(v, best)) {                                            // (rising columns: a tie keeps the earlier one)
+            best = v;
+            bj = j;
+          }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float v = __shfl_xor(best, o, 64);
+          const int j = __shfl_xor(bj, o, 64);
+          if (cluster_before(v, j, best, bj)) {
+            best = v;
+            bj = j;
+          }
+        }
+        if (lane == 0) {
+          out_b[s] = bj;
+          cluster_visit(bj, lab_b[s], raw_b[s], C, false, T, tot);
+        }
+      }
+    }
+    __syncthreads();
+    int c4[4] = {0, 0, 0, 0};
+    for (int c = t; c < C; c += kClusterBlock) {
+      const bool has_l = T.lab_max[c] >= 0, has_p = T.prd_max[c] >= 0;
+      c4[0] += has_l && T.lab_min[c] == T.lab_max[c];
+      c4[1] += has_l;
+      c4[2] += has_p && T.prd_min[c] == T.prd_max[c];
+      c4[3] += has_p;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      c4[k] = wave_sum_int(c4[k]);
+      if (lane == 0 && c4[k]) atomicAdd(&cnt[k], c4[k]);
+    }
+    __syncthreads();                                                            // every table read and every add to cnt lies behind
+    if (t < 4) counts[(size_t)b * 4 + t] = cnt[t];
+  }
+  // one global atomic per workgroup and non-zero counter: every workgroup adds to the same four words, and adds to one address queue up
+  if (t < 4) blk[t] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int v = wave_sum_int(tot[k]);      // a workgroup's share of one launch stays below 2^31 positions (B * S < 2^31 is required)
+    if (lane == 0 && v) atomicAdd(&blk[k], v);
+  }
+  __syncthreads();
+  if (t < 4 && blk[t]) atomicAdd(&totals[t], (unsigned long long)blk[t]);
+}
+
+inline size_t cluster_lds_bytes(int C) { return (size_t)(kClusterTile + 4 + 4 + 4) * 4 + (size_t)C * 16; }
+
+// one workgroup per sample up to 8 per CU of a 256-CU chip (the work of a sample is a chain of dependent round trips: residency hides
+// it); menu key 18 sets another cap, as for the link metrics
+inline int cluster_grid(int B) {
+  const int cap = menu().link_grid > 0 ? menu().link_grid : 2048;
+  return B < 1 ? 1 : B > cap ? cap : B;
+}
+
 }  // namespace
+
+extern "C" int gget_op_cluster_metrics(const void* pred_or_logits, int is_logits, const int64_t* labels, const int64_t* raw_node_idx, int B,
+                                       int S, int C, int64_t* y_pred, int32_t* counts, int64_t* totals, void* stream) {
+  GGET_REQUIRE(B >= 0 && S >= 0 && C >= 1, "cluster_metrics: B = %d, S = %d, C = %d", B, S, C);
+  GGET_REQUIRE(C <= kClusterMaxC, "cluster_metrics: C = %d classes, above GGET_CLUSTER_MAX_C = %d (four int32 tables of C entries in LDS)",
+               C, kClusterMaxC);
+  GGET_REQUIRE((long long)B * S < (1ll << 31) && (long long)S * C < (1ll << 31), "cluster_metrics: B * S = %lld, S * C = %lld (both below 2^31)",
+               (long long)B * S, (long long)S * C);
+  if (B == 0 || S == 0) return 0;
+  GGET_REQUIRE(pred_or_logits && labels && raw_node_idx && y_pred && counts && totals, "cluster_metrics: null argument");
+  GGET_REQUIRE(((uintptr_t)pred_or_logits & (is_logits ? 3 : 7)) == 0 && ((uintptr_t)labels & 7) == 0 && ((uintptr_t)raw_node_idx & 7) == 0 &&
+                   ((uintptr_t)y_pred & 7) == 0 && ((uintptr_t)counts & 3) == 0 && ((uintptr_t)totals & 7) == 0,
+               "cluster_metrics: an argument is not aligned to its element size");
+  hipLaunchKernelGGL(cluster_kernel, dim3(cluster_grid(B)), dim3(kClusterBlock), cluster_lds_bytes(C), (hipStream_t)stream, pred_or_logits,
+                     is_logits ? 1 : 0, (const long long*)labels, (const long long*)raw_node_idx, B, S, C, (long long*)y_pred, counts,
+                     (unsigned long long*)totals);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" size_t gget_op_link_hits_workspace(int n) { return n <= 0 ? 0 : kHitsBytes; }
 

@@ -5,9 +5,10 @@
   RegressionMetrics / _eval_pcqm4mv2 (MAE)  reference src/utils/metrics_utils.py:143-189, src/utils/ogb_utils.py:199-204
   MultiLabelClassificationMetrics           reference src/utils/metrics_utils.py:91-140     (per-task ROC-AUC of sigmoid(logits))
   _eval_rocauc / OGB _eval_ap               reference src/utils/ogb_utils.py:13-29, :71-79, :173-195 (ogbn-proteins, ogbg-molhiv, ogbg-molpcba)
+  GraphClusteringMetrics                    reference src/utils/metrics_utils.py:211-348     (token-level heads: accuracy, clustering recall / precision)
 The reference delegates to `torchmetrics` / `ogb` (not installed here); these are plain NumPy statements of the
 published definitions, pinned in tests against scikit-learn and closed-form cases.  CUDA tensors take the HIP kernels of
-csrc/metrics.hip (`rank_metrics`, `link_hits`, `link_mrr`); host arrays take the NumPy statements."""
+csrc/metrics.hip (`rank_metrics`, `link_hits`, `link_mrr`, `cluster_metrics`); host arrays take the NumPy statements."""
 from __future__ import annotations
 
 import numpy as np
@@ -307,6 +308,98 @@ def link_mrr(scores, labels, idx, cnt_neg: int = 1000, groups: int = 1):
     return dict(res, optimistic=opt, pessimistic=pes)
 
 
+# ----------------------------------------------------------------------------- graph clustering: token-level heads (nodev2)
+IGNORE = -100       # an unlabelled position in `labels`; a position that is not the one counted occurrence of a node in `raw_node_idx`
+
+
+def _argmax_first(logits: np.ndarray) -> np.ndarray:
+    """torch.argmax over the last axis, stated: the first index of the maximum; a NaN is maximal and the first NaN wins; -0.0 ties +0.0.
+    (np.argmax has the same rule; the NaN half of it is spelled out here so that it does not rest on NumPy's propagation.)"""
+    lg = np.asarray(logits)
+    nan = np.isnan(lg)
+    return np.where(nan.any(-1), nan.argmax(-1), np.where(nan, -np.inf, lg).argmax(-1)).astype(np.int64)
+
+
+def _cluster_numpy(pred_or_logits, labels, raw_node_idx, num_labels):
+    """The count form of include/gget.h `gget_op_cluster_metrics` in NumPy (the host path, and what the GPU tests compare the kernel
+    with): (y_pred i64 [B,S], counts i32 [B,4] = (t_r, n_r, t_p, n_p), totals i64 [4] = (n_correct, n_kept, n_selected, n_bad)).
+    Per (sample, label) the min and max prediction over the kept positions and per (sample, prediction) the min and max label: a value
+    is present when its max was written, its group uniform when min == max."""
+    p, y, raw = np.asarray(pred_or_logits), np.asarray(labels).astype(np.int64), np.asarray(raw_node_idx).astype(np.int64)
+    C = int(num_labels)
+    is_logits = p.ndim == 3
+    y_pred = _argmax_first(p) if is_logits else p.astype(np.int64)
+    B = y.shape[0]
+    sel, lab = raw != IGNORE, y != IGNORE
+    bad = sel & (lab & ((y < 0) | (y >= C)) | (False if is_logits else (y_pred < 0) | (y_pred >= C)))
+    sel = sel & ~bad
+    kept = sel & lab
+    totals = np.array([(kept & (y_pred == y)).sum(), kept.sum(), sel.sum(), bad.sum()], np.int64)
+    b_of = np.broadcast_to(np.arange(B)[:, None], y.shape)[kept]
+    yk, pk = y[kept], y_pred[kept]
+    counts = np.zeros((B, 4), np.int32)
+    for col, key, val in ((0, yk, pk), (2, pk, yk)):
+        lo, hi = np.full(B * C, np.iinfo(np.int64).max), np.full(B * C, -1, np.int64)
+        np.minimum.at(lo, b_of * C + key, val)
+        np.maximum.at(hi, b_of * C + key, val)
+        present = (hi >= 0).reshape(B, C)
+        counts[:, col] = (present & (lo == hi).reshape(B, C)).sum(1)
+        counts[:, col + 1] = present.sum(1)
+    return y_pred, counts, totals
+
+
+def _cluster_hip(pred_or_logits, labels, raw_node_idx, num_labels, totals=None):
+    """The same three results from the HIP kernel for CUDA tensors, as device tensors: one launch on the current stream, no
+    synchronisation, no copy.  `totals` (i64 [4] on the device) is added to.  No fallback: a library without the entry is an error."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    is_logits = pred_or_logits.dim() == 3
+    dev = pred_or_logits.device
+    p = (pred_or_logits.detach().float() if is_logits else pred_or_logits.detach().long()).contiguous()
+    y, raw = labels.detach().to(dev).long().contiguous(), raw_node_idx.detach().to(dev).long().contiguous()
+    B, S = y.shape
+    y_pred = torch.empty(B, S, dtype=torch.int64, device=dev)
+    counts = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+    totals = torch.zeros(4, dtype=torch.int64, device=dev) if totals is None else totals
+    with torch.cuda.device(dev):
+        _lib.check(lib.gget_op_cluster_metrics(p.data_ptr(), int(is_logits), y.data_ptr(), raw.data_ptr(), B, S, int(num_labels),
+                                               y_pred.data_ptr(), counts.data_ptr(), totals.data_ptr(),
+                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return y_pred, counts, totals
+
+
+def cluster_metrics(pred_or_logits, labels, raw_node_idx, num_labels: int, totals=None):
+    """What GraphClusteringMetrics.update takes from one batch (reference src/utils/metrics_utils.py:231-295 and `get_acc_per_graph`
+    :340-348), as exact integer counts (include/gget.h `gget_op_cluster_metrics`).  pred_or_logits: logits [B,S,C] (prediction = arg-max,
+    torch's rule) or integer predictions [B,S]; labels [B,S], -100 = unlabelled; raw_node_idx [B,S], -100 = not a counted position.
+    Returns {"y_pred" i64 [B,S], "counts" i32 [B,4] = (t_r, n_r, t_p, n_p) per sample, "totals" i64 [4] = (n_correct, n_kept, n_selected,
+    n_bad)}; a `totals` that is passed in is added to and returned.  CUDA tensors go through the HIP kernel and stay on the device (one
+    launch, no synchronisation); CPU tensors and arrays through the NumPy statement of the same counts (tensors in, tensors out).  CUDA
+    tensors with num_labels above the kernel's class limit (`_lib.CLUSTER_MAX_C`) take the NumPy statement too, through a host copy, and
+    come back as device tensors."""
+    from . import _lib
+    shape = tuple(labels.shape)
+    if len(shape) != 2 or tuple(raw_node_idx.shape) != shape or tuple(pred_or_logits.shape[:2]) != shape or len(pred_or_logits.shape) not in (2, 3):
+        raise ValueError(f"cluster_metrics: pred_or_logits {tuple(pred_or_logits.shape)}, labels {shape} and raw_node_idx "
+                         f"{tuple(raw_node_idx.shape)} must be [B,S,C] or [B,S], [B,S] and [B,S]")
+    if len(pred_or_logits.shape) == 3 and pred_or_logits.shape[2] != num_labels:
+        raise ValueError(f"cluster_metrics: logits of {pred_or_logits.shape[2]} classes, num_labels = {num_labels}")
+    if _is_cuda(pred_or_logits) and num_labels <= _lib.CLUSTER_MAX_C:
+        y_pred, counts, totals = _cluster_hip(pred_or_logits, labels, raw_node_idx, num_labels, totals)
+        return {"y_pred": y_pred, "counts": counts, "totals": totals}
+    y_pred, counts, tot = _cluster_numpy(_to_np(pred_or_logits), _to_np(labels), _to_np(raw_node_idx), num_labels)
+    if hasattr(pred_or_logits, "detach"):
+        import torch
+        dev = pred_or_logits.device
+        y_pred, counts, tot = torch.from_numpy(y_pred).to(dev), torch.from_numpy(counts).to(dev), torch.from_numpy(tot).to(dev)
+    if totals is not None:
+        totals += tot
+        tot = totals
+    return {"y_pred": y_pred, "counts": counts, "totals": tot}
+
+
 # ----------------------------------------------------------------------------- accumulating metric objects of the fine-tune evaluation pass
 class SingleLabelClassificationMetrics:
     """Counterpart of the reference class of the same name (src/utils/metrics_utils.py:17-80): per batch `update(logits,
@@ -467,9 +560,108 @@ class MultiLabelClassificationMetrics:
         return f"{prefix} mean AUROC: {self.auroc_mean}, detailed AUROC: {','.join(self.auroc_vec.astype(str))}"
 
 
+class GraphClusteringMetrics:
+    """Counterpart of the reference class of the same name (src/utils/metrics_utils.py:211-348; `metric_type = "graph_clustering"`, the
+    metric of the token-level heads): per batch `update(logits, labels, (idx, raw_node_idx))` with logits [B,S,C] (or integer predictions
+    [B,S]), labels [B,S] (-100 = unlabelled), idx [B] and raw_node_idx [B,S] (-100 at every position that is not the one counted
+    occurrence of a node).  A position is selected when raw_node_idx != -100 and kept when it is selected and labelled.
+      acc        n_correct / n_kept over all batches: the micro accuracy of torchmetrics' multiclass `Accuracy`, which the reference
+                 uses.  torchmetrics is not installed where this package is tested, so this one rule is restated, not pinned against it.
+      recall     mean over the samples of t_r / n_r (fp32 quotient, as the reference's mean of an fp32 0 / 1 list): n_r distinct labels
+                 among the sample's kept positions, t_r those whose positions all carry one prediction.
+      precision  the same with the roles of label and prediction swapped (t_p / n_p).
+    A sample without a kept position gives 0 / 0 = NaN on both sides and makes the means NaN, as in the reference (mean of an empty
+    tensor); `n_empty` counts such samples.  The reference raises IndexError for a sample with exactly ONE selected position (squeeze()
+    to 0-dim, then indexing, :271-280); here such a sample is defined by the count form: 1 / 1 if the position is kept, NaN if not.
+    `update` keeps everything on the device it arrives on - predictions, labels, raw_node_idx, idx, the per-sample counts and one
+    `totals` tensor for the whole pass (`cluster_metrics`: one kernel launch per batch for CUDA tensors) - and never synchronises;
+    `compute` makes the one host transfer (counts and totals in one tensor), takes the means in fp64 over the fp32 per-sample
+    quotients, and raises ValueError when a selected position carried a label outside [0, num_labels) (or, for integer predictions, a
+    prediction outside it).  `sync_dict` returns the per-sample counts and the totals, so `compute(gathered)` on the concatenation from
+    all ranks gives the means over ALL samples - deliberately different from the reference, whose recall / precision stay per rank and
+    whose accuracy alone is synchronised (by torchmetrics)."""
+
+    def __init__(self, device=None, num_labels: int = 2, **kwargs):
+        self.device, self.num_labels = device, num_labels
+        self.acc = self.recall = self.precision = self.n_empty = None
+        self.ls_recall = self.ls_precision = None             # fp32 per-sample quotients, after compute()
+        self.totals = None
+        self.ls_pred, self.ls_labels, self.ls_idx, self.ls_node_idx, self.ls_counts = [], [], [], [], []
+
+    def update(self, logits, labels, idx):
+        assert isinstance(idx, tuple), f"idx type should be tuple, but it is {type(idx)}"
+        idx, raw_node_idx = idx
+        assert len(logits.shape) in {2, 3}, f"logits shape: {logits.shape}"
+        assert len(labels.shape) == 2, f"labels shape: {labels.shape}"
+        logits, labels = logits.detach(), labels.detach()
+        raw_node_idx, idx = raw_node_idx.detach().to(logits.device), idx.detach().to(logits.device)
+        r = cluster_metrics(logits, labels, raw_node_idx, self.num_labels, totals=self.totals)
+        self.totals = r["totals"]
+        self.ls_pred.append(r["y_pred"].reshape(-1))
+        self.ls_labels.append(labels.reshape(-1))
+        self.ls_node_idx.append(raw_node_idx.reshape(-1))
+        self.ls_idx.append(idx.reshape(-1, 1).expand(-1, labels.shape[1]).reshape(-1))       # metrics_utils.py:261-263
+        self.ls_counts.append(r["counts"])
+
+    def sync_dict(self):
+        """what compute() needs from every rank: counts i32 [N,4] per sample, totals i64 [4]"""
+        import torch
+        return {"counts": torch.cat(self.ls_counts), "totals": self.totals}
+
+    def compute(self, gathered=None):
+        """`gathered`: {"counts" [N,4], "totals" [4 k]} concatenated from ALL ranks (tensors or arrays); None = this rank's own."""
+        import torch
+        d = self.sync_dict() if gathered is None else gathered
+        counts, totals = torch.as_tensor(d["counts"]), torch.as_tensor(d["totals"])
+        flat = torch.cat([counts.reshape(-1).long(), totals.reshape(-1).long().to(counts.device)]).cpu().numpy()      # the one transfer
+        n4 = counts.numel()
+        c, tot = flat[:n4].reshape(-1, 4), flat[n4:].reshape(-1, 4).sum(0)
+        n_correct, n_kept, _, n_bad = (int(v) for v in tot)
+        if n_bad:
+            raise ValueError(f"GraphClusteringMetrics: {n_bad} selected positions with a label (or a given prediction) outside "
+                             f"[0, {self.num_labels})")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.ls_recall = c[:, 0].astype(np.float32) / c[:, 1].astype(np.float32)
+            self.ls_precision = c[:, 2].astype(np.float32) / c[:, 3].astype(np.float32)
+        nan = float("nan")
+        self.recall = float(self.ls_recall.astype(np.float64).mean()) if len(c) else nan
+        self.precision = float(self.ls_precision.astype(np.float64).mean()) if len(c) else nan
+        self.n_empty = int((c[:, 1] == 0).sum())
+        self.acc = n_correct / n_kept if n_kept else nan
+
+    def to_dict(self):
+        """y_true, y_pred, idx (the sample's idx repeated) and node_idx over the selected positions in row-major order - one boolean
+        index per tensor, on the device the batches arrived on"""
+        import torch
+        node = torch.cat(self.ls_node_idx)
+        sel = node != IGNORE
+        return {"y_true": torch.cat(self.ls_labels)[sel], "y_pred": torch.cat(self.ls_pred)[sel], "idx": torch.cat(self.ls_idx)[sel],
+                "node_idx": node[sel]}
+
+    def get_output_shape(self, dim, key=None):
+        return dim
+
+    def results_in_tuple(self):
+        return self.acc, self.recall, self.precision
+
+    def results_in_str_tuple(self):
+        return str(self.acc), str(self.recall), str(self.precision)
+
+    def results_in_details(self, prefix=""):
+        return f"{prefix} Recall: {self.recall}, {prefix} Precision: {self.precision}, {prefix} ACC: {self.acc}"
+
+    def results_in_dict(self, prefix=""):
+        r, p = self.recall, self.precision
+        return {f"{prefix} ACC": self.acc, f"{prefix} Recall": r, f"{prefix} Precision": p,
+                "EMA F1": 2 * r * p / (r + p) if r + p != 0 else float("nan")}
+
+
 def get_metrics(metric_type: str, device=None, num_labels: int = 2, on_device: bool = False):
-    """reference `get_metrics` registry (metrics_utils.py:11-13): the two problem types of the BASELINE configs and the multi-label one.
-    `on_device`: the two-class single-label object keeps its accumulations on the device (the multi-label one always does)."""
+    """reference `get_metrics` registry (metrics_utils.py:11-13): the two problem types of the BASELINE configs, the multi-label one and
+    the graph-clustering one of the token-level heads.
+    `on_device`: the two-class single-label object keeps its accumulations on the device (the multi-label and clustering ones always do)."""
+    if metric_type == "graph_clustering":
+        return GraphClusteringMetrics(device, num_labels=num_labels)
     if metric_type == "single_label_classification":
         return SingleLabelClassificationMetrics(device, num_labels=num_labels, on_device=on_device and num_labels == 2)
     if metric_type == "regression":
@@ -498,6 +690,8 @@ def evaluate_ogb(dataset_name: str, input_dict, cnt_neg: int = 1000):
     if dataset_name in HITS_DATASETS and _is_cuda(input_dict["y_pred"]):
         k = HITS_DATASETS[dataset_name]
         return {f"hits@{k}": link_hits(input_dict["y_pred"], input_dict["y_true"], k)["hits@k"]}
+    if dataset_name not in HITS_DATASETS and dataset_name != "PCQM4Mv2":      # (before the host copies below: device tensors stay put)
+        return None
     y_true, y_pred = np.asarray(_to_np(input_dict["y_true"])), np.asarray(_to_np(input_dict["y_pred"]), np.float64)
     if dataset_name in HITS_DATASETS:
         k = HITS_DATASETS[dataset_name]

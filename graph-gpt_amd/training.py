@@ -805,7 +805,8 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
     ogbl-citation2 / ogbl-wikikg2 evaluators, 1000 in the reference).  A two-class single-label problem on a GPU keeps its
     accumulations on the device, ranks there (metrics.link_hits / link_mrr / rank_metrics) and copies the tensor dict to the host once,
     after the metrics; ogbl-citation2 / ogbl-wikikg2 are not ranked for eval_name == "train" (reference :153-160): the metric
-    object's own results are returned then."""
+    object's own results are returned then.  A batch with a "raw_node_idx" column (token-level heads, metric_type
+    "graph_clustering") hands `(idx, raw_node_idx)` to `update`, as the reference does (:130-131)."""
     from . import metrics as M
     model.eval()
     device = model.device
@@ -823,6 +824,8 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
                     position_ids=data["position_ids"].to(device) if "position_ids" in data else None)
         test_loss = test_loss + res.task_loss.detach()
         idx = data["idx"].to(device) if "idx" in data else torch.arange(labels.shape[0], device=device) + (j - 1) * labels.shape[0]
+        if "raw_node_idx" in data:        # the nodev2 collator's column: the clustering metric takes (idx, raw_node_idx), log_eval_dump_utils.py:130-131
+            idx = (idx, data["raw_node_idx"].to(device))
         cls_metrics.update(res.task_logits, labels, idx)
     model.train()
     _check_deferred_all_ranks(model)      # (a collective itself: every rank raises together, none is left inside the gathers below)
@@ -842,6 +845,19 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
             sync = dict(input_dict, prob=all_gather_varlen(sync["prob"].to(gdev)))
         cls_metrics.compute(sync)
         res = ogb(input_dict)
+        if res is None:
+            res = cls_metrics.results_in_dict()
+        return test_loss, cls_metrics, res, {k: v.cpu() for k, v in input_dict.items()}
+    if isinstance(cls_metrics, M.GraphClusteringMetrics):
+        # as the multi-label branch below: per-sample counts and totals were taken on the device batch by batch (metrics.cluster_metrics);
+        # compute() makes their one host transfer, the tensor dict follows in one copy at the end
+        sync = cls_metrics.sync_dict()
+        if world > 1:
+            gdev = device if dist.get_backend() == "nccl" else torch.device("cpu")
+            input_dict = {k: all_gather_varlen(v.to(gdev)) for k, v in input_dict.items()}
+            sync = {k: all_gather_varlen(v.to(gdev)) for k, v in sync.items()}
+        cls_metrics.compute(sync)
+        res = M.evaluate_ogb(dataset_name, input_dict)
         if res is None:
             res = cls_metrics.results_in_dict()
         return test_loss, cls_metrics, res, {k: v.cpu() for k, v in input_dict.items()}

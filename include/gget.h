@@ -832,6 +832,35 @@ int gget_op_link_mrr(const float* scores, const int64_t* labels, const int64_t* 
                      int64_t* n_neg, int32_t* optimistic, int32_t* pessimistic, int64_t* hits_1_3_10, double* mrr_sum, int32_t* n_bad,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Graph-clustering metrics of the token-level heads (loss_type "token_ce" / "token_ce_intra"; csrc/metrics.hip; the Python surface is
+ * graph-gpt_amd/metrics.py cluster_metrics / GraphClusteringMetrics).
+ * replaces: GraphClusteringMetrics.update (src/utils/metrics_utils.py:231-295: torch.argmax, then per sample two .nonzero()) and
+ * `get_acc_per_graph` (:340-348: per distinct label and per distinct prediction a .nonzero(), a .unique() and a len(...), each a
+ * device-to-host synchronisation inside a Python loop).
+ *   pred_or_logits  is_logits = 1: f32 [B][S][C], rows contiguous; prediction = arg-max over C with torch's rule (the first index of the
+ *                   maximum; a NaN is maximal and the first NaN wins; -0.0 ties +0.0).  is_logits = 0: i64 [B][S], the predictions.
+ *   labels          i64 [B][S], -100 = unlabelled
+ *   raw_node_idx    i64 [B][S], -100 at every position that is not the one counted occurrence of a node (padding included)
+ * A position is SELECTED when raw_node_idx != -100 and KEPT when it is selected and its label != -100.  A selected position is BAD when
+ * its label is neither -100 nor in [0, C), or (is_logits = 0) its prediction is outside [0, C): it is counted in n_bad and left out of
+ * every other count.
+ *   y_pred  i64 [B][S]   the arg-max, or a copy of the given predictions, at every position, selected or not
+ *   counts  i32 [B][4]   (t_r, n_r, t_p, n_p) over the sample's kept positions: n_r distinct labels, t_r those whose positions all carry
+ *                        one and the same prediction; n_p distinct predictions, t_p those whose positions all carry one label.
+ *                        recall = t_r / n_r, precision = t_p / n_p; a sample without a kept position gets four zeros
+ *   totals  i64 [4]      (n_correct, n_kept, n_selected, n_bad): the call ADDS to these (integer atomics); the caller zeroes them once
+ *                        per evaluation pass.  n_correct: kept positions with prediction == label; accuracy = n_correct / n_kept
+ * One launch on `stream`, one workgroup per sample (grid-stride), no workspace, no host sync.  Per label value the min and max
+ * prediction and per prediction value the min and max label are kept in four int32 LDS tables of C entries (LDS integer min / max
+ * atomics): every output is an exact integer, independent of lane order and launch geometry and bit-identical from run to run.  The
+ * tables bound C: C > GGET_CLUSTER_MAX_C is refused with an error naming the limit.  B * S and S * C below 2^31; B == 0 or S == 0 is a
+ * valid call that launches nothing (the outputs are not written).
+ * ------------------------------------------------------------------------------------------ */
+#define GGET_CLUSTER_MAX_C 2048 /* 4 tables x 2048 x 4 bytes = 32 KiB of LDS */
+int gget_op_cluster_metrics(const void* pred_or_logits, int is_logits, const int64_t* labels, const int64_t* raw_node_idx, int B, int S,
+                            int C, int64_t* y_pred, int32_t* counts, int64_t* totals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

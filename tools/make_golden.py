@@ -1143,6 +1143,76 @@ def link_reformat_fixture():
     print("link_reformat written:", {k: v.shape for k, v in res.items()})
 
 
+def cluster_metrics_fixture():
+    """Three batches (B = 8, S = 24, C = 5) through the reference's GraphClusteringMetrics (metrics_utils.py:211-348) and what it
+    returns: the per-sample fp32 recall / precision lists, acc / recall / precision, the four `to_dict` arrays and `results_in_dict()`.
+    Logits are rounded to one decimal so that ties occur; samples with unlabelled nodes, repeated nodes marked -100, one all-uniform
+    sample and one where every node has its own label.  torcheval / torchmetrics are absent: stand-in modules, and for `Accuracy` a
+    counting class of our own (micro accuracy, the quotient in fp32 as torchmetrics returns it).  Every sample has at least two selected
+    positions and one kept position: the reference raises IndexError for a single selected one (:271-280).  Data only."""
+    import_reference()
+
+    class CountingAccuracy:
+        def __init__(self, *a, **k):
+            self.correct = self.total = 0
+
+        def to(self, device):
+            return self
+
+        def update(self, preds, target):
+            self.correct += int((preds == target).sum())
+            self.total += int(target.numel())
+
+        def compute(self):
+            return torch.tensor(self.correct, dtype=torch.float32) / torch.tensor(self.total, dtype=torch.float32)
+
+    blank = type("Blank", (), {"__init__": lambda self, *a, **k: None})
+    for name, attrs in (("torcheval", {}), ("torcheval.metrics", {}), ("torchmetrics", {"MeanAbsoluteError": blank, "MeanSquaredError": blank}),
+                        ("torchmetrics.classification", {"BinaryAccuracy": blank, "BinaryAUROC": blank, "Accuracy": CountingAccuracy})):
+        m = types.ModuleType(name)
+        m.__path__ = []
+        m.__dict__.update(attrs)
+        sys.modules[name] = m
+    sys.modules["torcheval"].metrics = sys.modules["torcheval.metrics"]
+    from src.utils import metrics_utils
+    B, S, C, n_batches = 8, 24, 5, 3
+    rng = np.random.RandomState(31)
+    obj = metrics_utils.get_metrics("graph_clustering", device="cpu", num_labels=C)
+    res = {}
+    for k in range(n_batches):
+        logits = np.round(rng.randn(B, S, C), 1).astype(np.float32)
+        labels = rng.randint(0, C, (B, S)).astype(np.int64)
+        raw = np.tile(np.arange(S, dtype=np.int64), (B, 1)) + 100 * k
+        real = rng.randint(6, S + 1, B)                                      # padding behind the sample's tokens
+        for b in range(B):
+            raw[b, real[b]:] = -100
+            raw[b, rng.rand(S) < 0.25] = -100                                # repeated occurrences of a node: not counted
+            labels[b, rng.rand(S) < 0.2] = -100                              # unlabelled nodes
+            raw[b, :2], labels[b, 0] = (100 * k, 100 * k + 1), rng.randint(0, C)      # at least two selected, one kept
+        if k == 0:                                                           # all-uniform: one label, one prediction
+            labels[1, labels[1] != -100] = 3
+            logits[1, :, 2] = 9.0
+        if k == 1:                                                           # every kept node its own label (at most C of them are kept)
+            raw[2], labels[2] = -100, -100
+            raw[2, :C], labels[2, :C] = np.arange(C) + 100, rng.permutation(C)
+        sel = raw != -100
+        assert (sel.sum(1) >= 2).all() and ((labels != -100) & sel).sum(1).min() >= 1
+        idx = np.arange(B, dtype=np.int64) + B * k
+        obj.update(torch.from_numpy(logits), torch.from_numpy(labels), (torch.from_numpy(idx), torch.from_numpy(raw)))
+        res.update({f"logits_{k}": logits, f"labels_{k}": labels, f"raw_node_idx_{k}": raw, f"idx_{k}": idx})
+    obj.compute()
+    d = obj.to_dict()
+    res.update({"ls_recall": torch.hstack(obj.ls_recall).numpy(), "ls_precision": torch.hstack(obj.ls_precision).numpy(),
+                "acc": np.float64(obj.acc), "recall": np.float64(obj.recall), "precision": np.float64(obj.precision),
+                "y_true": d["y_true"].numpy(), "y_pred": d["y_pred"].numpy(), "idx": d["idx"].numpy(), "node_idx": d["node_idx"].numpy()})
+    rd = obj.results_in_dict(prefix="valid")
+    res["results_keys"] = np.array(list(rd.keys()))
+    res["results_values"] = np.array([float(v) for v in rd.values()], np.float64)
+    assert res["ls_recall"].dtype == np.float32 and len(res["ls_recall"]) == B * n_batches and np.isfinite(res["ls_recall"]).all()
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "cluster_metrics.npz"), **res)
+    print("cluster_metrics written:", {k: v.shape for k, v in res.items()}, rd)
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -1190,6 +1260,8 @@ def main():
         freeze_names_fixture()
     if not only or "link_reformat" in only:
         link_reformat_fixture()
+    if not only or "cluster_metrics" in only:
+        cluster_metrics_fixture()
 
 
 if __name__ == "__main__":
