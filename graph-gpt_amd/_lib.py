@@ -140,6 +140,10 @@ SIGNATURES = {
     "gget_op_ls_rmsnorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "gget_op_accum_layout": (i32, [i32, C.POINTER(i32), C.POINTER(u64)]),
     "gget_op_rmsnorm_bwd_ls": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "gget_op_rope_table": (i32, [vp, vp, i32, f32, vp]),
+    "gget_op_rope_range_table": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp]),
+    "gget_op_clamp_positions": (i32, [vp, vp, vp, i64, i32, vp]),
+    "gget_op_embed_long_ratio": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "gget_op_ce_full": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, f32, i32, vp, f32, vp, i32, vp]),
     "gget_op_score_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "gget_op_score_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
@@ -177,7 +181,8 @@ EPI_NONE, EPI_RESIDUAL, EPI_ATOMIC_F32, EPI_SLAB_F32 = 0, 1, 2, 3
 KEY_GEMM_VARIANT, KEY_GEMM_LDS_HEADROOM, KEY_GEMM_SPLIT_LAST, KEY_DETERMINISTIC, KEY_GEMM_STAGGER = 1, 2, 3, 4, 5
 KEY_GEMM_ABLATE, KEY_HEAD_DENSE, KEY_HEAD_TILE, KEY_ATTN_OPROJ_OFF, KEY_LS_NORM_BWD_WIDE = 7, 8, 9, 10, 11
 KEY_RMS_WIDE, KEY_CE_PARTS, KEY_GEMM_CU_RESERVE, KEY_OCCUPY_FAT, KEY_LINK_GRID, KEY_CE_GENERIC = 13, 14, 15, 16, 18, 19
-MENU_KEYS = (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 13, 14, 15, 16, 18, 19)
+KEY_EMBED_SORTED = 20
+MENU_KEYS = (1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 13, 14, 15, 16, 18, 19, 20)
 # KEY_GEMM_VARIANT bits (csrc/menu.h kGemm*): the first six switch a variant OFF, the last two switch one ON
 GEMM_NO_KSPLIT_ND, GEMM_NO_KSPLIT_WGRAD, GEMM_NO_192_ROWS, GEMM_NO_SPLIT_LAST, GEMM_KSPLIT_128_ONLY, GEMM_ONE_BLOCK_PER_CU = 1, 2, 4, 8, 16, 32
 GEMM_KSPLIT_DMA8, GEMM_AREA_RULE = 128, 512

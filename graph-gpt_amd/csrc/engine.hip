@@ -2779,6 +2779,9 @@ extern "C" int gget_op_embed_fwd(const int64_t* ids, const void* emb, const void
 }
 extern "C" int gget_op_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb_accum,
                                  float* dgate_accum, int T, int F, int ldF, int d, int V, int pad_id, void* stream) {
+  // (before the workspaces are sized from them; the launchers check again)
+  GGET_REQUIRE(ids && dx && demb_accum && (!gate || (emb && dgate_accum)), "embed_bwd: null argument");
+  GGET_REQUIRE(T >= 0 && F >= 1 && ldF >= F && d > 0 && d % 8 == 0 && V >= 1, "embed_bwd: bad shape T %d F %d ldF %d d %d V %d", T, F, ldF, d, V);
   int32_t* ws = nullptr;
   GGET_HIP_CHECK(hipMalloc(&ws, k_embed_bwd_ws_elems((size_t)T * F, (size_t)V) * sizeof(int32_t)));  // test-only entry point
   void* cnt = nullptr;   // (GGET_EMBED_SORTED=1 forces the sorted scatter-add)
@@ -2903,6 +2906,23 @@ extern "C" int gget_op_ce_fwd_bwd(const void* logits, int ld, const int32_t* lab
   GGET_REQUIRE(row_wgt == nullptr, "per-row weights go through the engine path (sample_wgt)");
   return k_ce_fwd_bwd(logits, ld, labels, nullptr, nullptr, 1, n_rows_dev, n_rows_cap, V, loss_sum, dlogits, grad_scale_base,
                       mean_over_rows, nullptr, (hipStream_t)stream);
+}
+// test-only entries of the element-wise kernels: every argument of the launcher, no arithmetic here
+extern "C" int gget_op_rope_table(float* cos_tab, float* sin_tab, int max_pos, float theta, void* stream) {
+  GGET_REQUIRE(cos_tab && sin_tab && max_pos >= 1 && theta > 0.f, "rope_table: bad arguments");
+  return k_rope_table(cos_tab, sin_tab, max_pos, theta, (hipStream_t)stream);
+}
+extern "C" int gget_op_rope_range_table(const int64_t* pos, float* cos_tab, float* sin_tab, int64_t* ids, int B, int S, float range, float theta,
+                                        void* stream) {
+  GGET_REQUIRE(pos && cos_tab && sin_tab && ids && B >= 0 && S >= 1 && range > 0.f && theta > 0.f, "rope_range_table: bad arguments");
+  return k_rope_range_table(pos, cos_tab, sin_tab, ids, B, S, range, theta, (hipStream_t)stream);
+}
+extern "C" int gget_op_clamp_positions(const int64_t* pos, int64_t* out, int32_t* flag, int64_t n, int max_pos, void* stream) {
+  GGET_REQUIRE(pos && out && flag && n >= 0 && max_pos >= 1, "clamp_positions: bad arguments");
+  return k_clamp_positions(pos, out, flag, (long)n, max_pos, (hipStream_t)stream);
+}
+extern "C" int gget_op_embed_long_ratio(const int64_t* ids, void* x, int T, int F, int ldF, int d, void* stream) {
+  return k_embed_long_ratio(ids, x, T, F, ldF, d, (hipStream_t)stream);
 }
 // test-only entries of the RMSNorm and cross-entropy families: every argument of the launcher, no arithmetic here
 extern "C" int gget_op_rmsnorm_bwd_copies(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,

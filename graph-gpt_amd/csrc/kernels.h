@@ -179,7 +179,7 @@ struct GgetZeroRanges {
 };
 int k_zero_ranges(const GgetZeroRanges& R, hipStream_t st);   // every range cleared by one launch (kernels.hip)
 int k_f32_to_bf16(const float* src, void* dst, size_t n, hipStream_t st);
-int k_slab_reduce(const float* slabs, long slab_stride, int nslab, void* dst, size_t n, hipStream_t st, bool f32_out = false);  // dst: bf16, or fp32 (overwritten)
+int k_slab_reduce(const float* slabs, long slab_stride, int nslab, void* dst, size_t n, hipStream_t st, bool f32_out = false);  // dst: bf16 (overwritten), or fp32 (added to)
 int k_convert_segments(const float* scratch, void* grads, const GgetSegment* segs_dev, int nseg, hipStream_t st);
 
 // attention.hip

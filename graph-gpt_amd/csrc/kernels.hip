@@ -2307,7 +2307,7 @@ __global__ void __launch_bounds__(kBlock) f32_to_bf16_kernel(const float* __rest
   }
 }
 
-// sum of `nslab` fp32 slabs (split-K partial products) -> bf16; rows beyond *rows_dev (if given) are left as they are
+// sum of `nslab` fp32 slabs (split-K partial products) -> bf16, or added to an fp32 accumulator; rows beyond *rows_dev (if given) are left as they are
 template <bool F32_OUT>
 __global__ void __launch_bounds__(kBlock) slab_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int nslab,
                                                              void* __restrict__ dst_, size_t n) {
@@ -2318,7 +2318,9 @@ __global__ void __launch_bounds__(kBlock) slab_reduce_kernel(const float* __rest
       const float4 b = reinterpret_cast<const float4*>(slabs + (size_t)s * slab_stride)[i];
       a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
     }
-    if (F32_OUT) {
+    if (F32_OUT) {   // an fp32 destination is an accumulator (the embedding gradient's): added to, as the sorted form does
+      const float4 o = reinterpret_cast<const float4*>(dst_)[i];
+      a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
       reinterpret_cast<float4*>(dst_)[i] = a;
     } else {
       uint2 o;
@@ -2686,6 +2688,8 @@ int k_elem_dropout(void* x, long T, int n, unsigned stream, ElemDropArg E, hipSt
 
 int k_embed_fwd(const int64_t* ids, const void* emb, const void* gate, void* out, int T, int F, int ldF, int d,
                 hipStream_t st, ElemDropArg E) {
+  GGET_REQUIRE(ids && emb && out, "embed_fwd: null argument");
+  GGET_REQUIRE(T >= 0 && F >= 1 && ldF >= F && d > 0 && d % 8 == 0, "embed_fwd: bad shape T %d F %d ldF %d d %d (d must be a multiple of 8)", T, F, ldF, d);
   if (T == 0) return 0;
   hipLaunchKernelGGL(embed_fwd_kernel, dim3(T), dim3(128), 0, st, ids, (const bf16_t*)emb, (const bf16_t*)gate,
                      (bf16_t*)out, T, F, ldF, d, E);
@@ -2709,6 +2713,8 @@ int k_raw_tok_grad(const void* dx, const int32_t* flag, float* dtok, int T, int 
 }
 
 int k_embed_long_ratio(const int64_t* ids, void* x, int T, int F, int ldF, int d, hipStream_t st) {
+  GGET_REQUIRE(ids && x, "embed_long_ratio: null argument");
+  GGET_REQUIRE(T >= 0 && F >= 1 && ldF >= F && d > 0 && d % 8 == 0, "embed_long_ratio: bad shape T %d F %d ldF %d d %d (d must be a multiple of 8)", T, F, ldF, d);
   if (T == 0) return 0;
   hipLaunchKernelGGL(embed_long_ratio_kernel, dim3(T), dim3(128), 0, st, ids, (bf16_t*)x, F, ldF, d);
   GGET_LAUNCH_CHECK();
@@ -2724,6 +2730,9 @@ int k_sample_mask_wgt(const int64_t* labels, float* w, int B, int cells, hipStre
 
 int k_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb, float* dgate, int T,
                 int F, int ldF, int d, int V, int pad_id, int32_t* sort_ws, hipStream_t st, ElemDropArg E) {
+  GGET_REQUIRE(ids && dx && demb && sort_ws && (!gate || (emb && dgate)), "embed_bwd: null argument");
+  GGET_REQUIRE(T >= 0 && F >= 1 && ldF >= F && d > 0 && d % 8 == 0 && V >= 1, "embed_bwd: bad shape T %d F %d ldF %d d %d V %d (d must be a multiple of 8)", T, F,
+               ldF, d, V);
   if (T == 0) return 0;
   // sort_ws: hist[V] | offs[V+1] | cursor[V] | cell_sorted[T*F] | id_sorted[T*F]
   const long ncell = (long)T * F;
@@ -2759,6 +2768,8 @@ int k_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void*
 }
 
 int k_embed_count(const int64_t* ids, void* cnt, int T, int F, int ldF, int ldc, int pad_id, hipStream_t st) {
+  GGET_REQUIRE(ids && cnt, "embed_count: null argument");
+  GGET_REQUIRE(T >= 0 && F >= 1 && ldF >= F && ldc >= 1, "embed_count: bad shape T %d F %d ldF %d ldc %d", T, F, ldF, ldc);
   if (T == 0) return 0;
   GGET_REQUIRE(F <= 256, "embed_count: counts above 256 are not exact in bf16 (F=%d)", F);
   hipLaunchKernelGGL(embed_count_kernel, dim3((int)(((long)T * F + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ids, (bf16_t*)cnt, T, F, ldF,
@@ -2869,6 +2880,8 @@ int k_ordered_colsum(float* part, int nblk, int d, float* dst, hipStream_t st) {
 
 int k_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H,
            int inverse, hipStream_t st) {
+  GGET_REQUIRE(qkv && cos_tab && sin_tab, "rope: null argument");
+  GGET_REQUIRE(T >= 0 && H >= 1 && S >= 1, "rope: bad shape T %d S %d H %d", T, S, H);
   if (T == 0) return 0;
   hipLaunchKernelGGL(rope_kernel, dim3(grid_for((long)T * 8 * H)), dim3(kBlock), 0, st, (bf16_t*)qkv, cos_tab, sin_tab,
                      position_ids, T, S, H, inverse);
@@ -2892,6 +2905,8 @@ int k_rope_range_table(const int64_t* pos, float* cos_t, float* sin_t, int64_t* 
 }
 
 int k_geglu_fwd(const void* gu, void* h, int T, int ff, hipStream_t st) {
+  GGET_REQUIRE(gu && h, "geglu_fwd: null argument");
+  GGET_REQUIRE(T >= 0 && ff > 0 && ff % 8 == 0, "geglu_fwd: bad shape T %d ff %d (ff must be a multiple of 8)", T, ff);
   if (T == 0) return 0;
   hipLaunchKernelGGL(geglu_fwd_kernel, dim3(grid_for((long)T * (ff / 8))), dim3(kBlock), 0, st, (const bf16_t*)gu,
                      (bf16_t*)h, (long)T, ff);
@@ -2900,6 +2915,8 @@ int k_geglu_fwd(const void* gu, void* h, int T, int ff, hipStream_t st) {
 }
 
 int k_geglu_bwd(const void* gu, const void* dh, void* dgu, int T, int ff, hipStream_t st) {
+  GGET_REQUIRE(gu && dh && dgu, "geglu_bwd: null argument");
+  GGET_REQUIRE(T >= 0 && ff > 0 && ff % 8 == 0, "geglu_bwd: bad shape T %d ff %d (ff must be a multiple of 8)", T, ff);
   if (T == 0) return 0;
   hipLaunchKernelGGL(geglu_bwd_kernel, dim3(grid_for((long)T * (ff / 8))), dim3(kBlock), 0, st, (const bf16_t*)gu,
                      (const bf16_t*)dh, (bf16_t*)dgu, (long)T, ff);

@@ -111,7 +111,7 @@ inline constexpr MenuRow kMenuRows[] = {
     {&LaunchMenu::no_ls_norm_fusion, 0, "GGET_NO_LS_NORM_FUSION", true, 0, "set: LayerScale residual and the next RMSNorm as separate launches"},
     {&LaunchMenu::no_varlen, 0, "GGET_NO_VARLEN", true, 0, "set: the padded token grid instead of the var-len layout"},
     {&LaunchMenu::count_copy, 0, "GGET_COUNT_COPY", false, 0, "1: token count back by device-to-host copy + event instead of a polled host word"},
-    {&LaunchMenu::embed_sorted, 0, "GGET_EMBED_SORTED", true, 0, "set: embedding backward always as the sorted scatter-add"},
+    {&LaunchMenu::embed_sorted, 20, "GGET_EMBED_SORTED", true, 0, "set: embedding backward always as the sorted scatter-add"},
     {&LaunchMenu::rms_rows, 0, "GGET_RMS_ROWS", false, 4, "RMSNorm backward rows per wave"},
     {&LaunchMenu::ce_generic, 19, "GGET_CE_GENERIC", true, 0, "set: cross-entropy never on the vectorised row kernels"},
 };

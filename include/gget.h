@@ -530,7 +530,8 @@ int gget_op_gemm_grouped(int mode, int count, const void* const* A, const void* 
  *   per block, summed in block order by the finalising launch).  key 15 = R: every GEMM launch plan counts the device's CUs minus R (0,
  *   default: the whole chip; a data-parallel handle sets its own with gget_set_dp_menu).  key 16 = 1: gget_debug_occupy's stand-in takes
  *   the register footprint of RCCL's kernel (264 registers per lane) besides the LDS asked for.  key 19 = 1: the cross-entropy launch never
- *   takes the row-in-registers kernels (what the presence of GGET_CE_GENERIC selects at load). */
+ *   takes the row-in-registers kernels (what the presence of GGET_CE_GENERIC selects at load).  key 20 = 1: the embedding backward always
+ *   as the sorted scatter-add, never the count-matrix product (what the presence of GGET_EMBED_SORTED selects at load). */
 int gget_debug_set(int key, int value);
 int gget_debug_get(int key, int* value);
 /* measurement aid: with enable != 0 the engine brackets, with HIP events on the launch stream, the grouped weight-gradient launch
@@ -587,8 +588,12 @@ int gget_op_smtp_rows(const int64_t* ids_in, const int32_t* lengths, int64_t* id
 int gget_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int T, int d, float eps, void* stream);
 int gget_op_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres,
                         void* dx, float* dw_accum, int T, int d, void* stream);
+/* the element-wise entries (embed, rope, geglu) check their shapes on the host and return an error before any launch: non-NULL pointers,
+ * d > 0 and d % 8 == 0, F >= 1, ldF >= F, V >= 1, H >= 1, S >= 1, ff > 0 and ff % 8 == 0 */
 int gget_op_embed_fwd(const int64_t* ids, const void* emb, const void* gate, void* out, int T, int F, int ldF,
                       int d, void* stream);
+/* demb_accum [V][d] (and dgate_accum [F][d] with a gate) fp32 are ADDED to, in the sorted scatter-add and in the count-matrix form alike;
+ * the pad_id row receives nothing */
 int gget_op_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb_accum,
                       float* dgate_accum, int T, int F, int ldF, int d, int V, int pad_id, void* stream);
 int gget_op_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B, int S,
@@ -718,6 +723,19 @@ int gget_op_rmsnorm_bwd_ls(const void* dy, const void* x, const void* w, const f
 int gget_op_ce_full(const void* logits, int ld, const int32_t* labels, const int32_t* sel_tok, const float* sample_wgt, int S,
                     const int32_t* n_rows_dev, int n_rows_cap, int V, float* loss_sum, void* dlogits, float scale_base, int mean_over_rows,
                     float* loss_out, float focal_gamma, float* loss_part, int loss_part_cap, void* stream);
+
+/* ---- test-only entries of the element-wise kernels: the launcher with every argument, no arithmetic of their own ---- */
+/* the RoPE angle tables every handle builds at creation: cos / sin [max_pos][32] fp32 of pos * theta^(-2j/64) (angle in fp32) */
+int gget_op_rope_table(float* cos_tab, float* sin_tab, int max_pos, float theta, void* stream);
+/* config.rope_range: per-token tables cos / sin [B*S][32] of the positions rescaled per row, float(p) * range / float(max_s p + 1), and the
+ * identity position list ids[b*S + s] = b*S + s that addresses them */
+int gget_op_rope_range_table(const int64_t* pos, float* cos_tab, float* sin_tab, int64_t* ids, int B, int S, float range, float theta,
+                             void* stream);
+/* out[i] = pos[i] clamped to [0, max_pos); *flag = 1 when any position was clamped, otherwise left as it was */
+int gget_op_clamp_positions(const int64_t* pos, int64_t* out, int32_t* flag, int64_t n, int max_pos, void* stream);
+/* stack_method = "long", in place: x[t,:] = bf16(x[t,:] * ratio_t), ratio_t = min(1, bf16(1 / (nnz_t + 1e-7f))), nnz_t the non-zero ids among
+ * ids[t*ldF .. t*ldF + F); rows with ratio 1 are not written */
+int gget_op_embed_long_ratio(const int64_t* ids, void* x, int T, int F, int ldF, int d, void* stream);
 
 /* ---- fine-tune heads and task losses, one launcher each (the kernels gget_forward_task / gget_backward run after the last norm) ---- */
 /* logits[b,c] = bf16(hidden[pool_row[b]] . w[c] + bias[c]) as f32 [B,C]; pooled_h (optional) bf16 [B,d] = the gathered rows; bias may be NULL */
