@@ -3162,6 +3162,160 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_fused64_kernel(const bf16_t* 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Attention weights of one layer (`output_attentions=True`; reference: the attn_weights hf eager_attention_forward returns,
+// modeling_llama.py:191-214, after its dropout in training mode):
+//   out[b, h, q, k] = bf16(m * exp(<q_bhq, k_bhk> / 8 - lse[b, h, q]))  for an allowed key, 0 otherwise;  out bf16 [B, H, S, S].
+// The forward kernels never hold a row of probabilities, so the scores are recomputed here (S^T = K Q^T on 32x32x16 bf16 MFMA, fp32
+// accumulators, q and k as they sit in qkv: rotated already) and normalised with the log-sum-exp the forward saved.
+// lse convention - the same in EVERY producer (attn_fwd_kernel, attn_fwd_rows64_kernel, attn_oproj_fwd_kernel, attn_fwd64_kernel with and
+// without key ranges, attn_fwd_dense_kernel): lse[(b * H + h) * S + q] = NATURAL log of sum_k exp(score / 8) over the allowed keys, taken
+// before dropout ((m + log2 l) / log2 e of the log2-domain online softmax); 0 for a query without keys; not written for rows behind a
+// sample on the var-len layout (never read here: such rows are zero by the rule).
+// Allowed keys: right padding (either token layout) q < len_b, k < len_b, k <= q when causal - rows of padding queries are ZERO, where the
+// padded-layout forward computes a softmax nothing consumes; packed rows lo[b,q] <= k <= hi[b,q] (and k <= q when causal).
+// m: the forward's keep multiplier (drop_mul_x with the forward's hash coordinates (seed, b * H + h, q, k)), 1 when D.thresh == 0.
+// The launch is bound by its stores (2 B written per 128 FLOP): a block = NW query tiles of one (b, h) walks the keys 64 at a time, the K
+// rows staged once per block; a wave transposes its 32 x 64 probabilities through a private LDS tile so that a lane stores 16 bytes along
+// the key axis and eight lanes cover the 128 contiguous bytes of a row - four 16-byte store instructions per lane and step.  Every element
+// of out is written (zeros included); no atomics: reruns are bit-identical.  vec == 0 (S % 8 != 0 or an unaligned out): element stores.
+template <int NW, bool PK>
+__global__ void __launch_bounds__(NW * 64) attn_probs_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ lse, KeyRange KR,
+                                                             bf16_t* __restrict__ out, int B, int S, int H, int causal, Drop D, int vec) {
+  constexpr int kPitch = 144;   // bytes per staged row: 64 keys + one 16-byte piece, so the lanes' 16-byte reads of 8 rows spread over the banks
+  __shared__ __attribute__((aligned(16))) unsigned char kt[2][4096];
+  __shared__ __attribute__((aligned(16))) unsigned char pt[NW][32 * kPitch];
+  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int h = blockIdx.y, b = blockIdx.z;
+  const int len = KR.key_len ? max(min(KR.key_len[b], S), 0) : S;
+  const int rb = KR.row_base ? KR.row_base[b] : b * S;
+  const int SL = KR.row_base ? len : S;      // rows the sample owns in the token-major buffer: no load leaves them (clamp_row)
+  const int q0 = (blockIdx.x * NW + wave) * 32;
+  const int d = H * 64;
+  const size_t pitch = (size_t)3 * d;
+  const bf16_t* qb = qkv + (size_t)rb * pitch + h * 64;
+  const bf16_t* kb = qb + d;
+  const int qrow = q0 + l31;
+  const Rope Rnone{nullptr, nullptr, nullptr, S};
+  // per-lane inclusive key range [qlo, qhi] (empty: qhi < qlo); uhi = the wave's largest allowed key
+  int qlo = 0, qhi = (qrow < len) ? len - 1 : -1;
+  if constexpr (PK) {
+    const bool v = qrow < S;
+    qlo = v ? max(KR.lo[(size_t)b * S + qrow], 0) : 0;
+    qhi = v ? min(KR.hi[(size_t)b * S + qrow], S - 1) : -1;
+  }
+  const bool row_live = qhi >= qlo;
+  const int uhi = wave_imax(row_live ? qhi + 1 : 0) - 1;
+  // keys every lane of the wave allows, [ilo, ihi]: a tile inside (and below the diagonal) needs no mask; empty when a lane has no keys
+  const int ilo = wave_imax(row_live ? qlo : S), ihi = wave_imin(row_live ? qhi + 1 : 0) - 1;
+  const int klen = PK ? S : len;
+  const int kend_blk = SL > 0 ? (causal ? min(klen, (int)(blockIdx.x + 1) * NW * 32) : klen) : 0;   // keys the block stages
+  const int kend = SL > 0 ? min(uhi + 1, causal ? q0 + 32 : S) : 0;                                  // keys this wave computes (<= kend_blk)
+  bf16x8_t qf[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(bf16x8_t, make_uint4(0u, 0u, 0u, 0u));
+  if (kend > 0) frags_global_rope(qf, qb, qrow, SL, pitch, lane, Rnone, b);
+  const float nlse2 = row_live ? -lse[((size_t)b * H + h) * S + qrow] * kLog2e : 0.f;
+  const unsigned dbase = drop_base(D, b * H + h, qrow, 0);
+  bf16_t* obase = out + (size_t)(b * H + h) * S * S;
+  unsigned char* mypt = pt[wave];
+  constexpr bool PF = NW > 1;    // one-wave blocks (S < 64) take one step: nothing to prefetch, and the registers are better spent on occupancy
+  TilePref<NW * 64> pk[2];
+  if constexpr (PF) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (32 * j < kend_blk) tile_fetch<NW * 64>(pk[j], kb, 32 * j, SL, pitch, tid, Rnone);
+  }
+  for (int k0 = 0; k0 < S; k0 += 64) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (k0 + 32 * j < kend_blk) {
+        if constexpr (PF) tile_commit<NW * 64>(kt[j], pk[j], k0 + 32 * j, SL, tid, Rnone, b);
+        else load_tile_coop<NW * 64>(kt[j], kb, k0 + 32 * j, SL, pitch, tid, Rnone, b);
+      }
+    __syncthreads();
+    if constexpr (PF) {            // the next step's K rows fly while this one is computed and stored
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        if (k0 + 64 + 32 * j < kend_blk) tile_fetch<NW * 64>(pk[j], kb, k0 + 64 + 32 * j, SL, pitch, tid, Rnone);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int kk = k0 + 32 * j;
+      f32x16_t sc = zero16();
+      if (kk < kend) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(kt[j], s, lane), qf[s], sc, 0, 0, 0);
+        // the mask is evaluated only on tiles that touch a key-range end or the diagonal (the loop is VALU work beside the stores)
+        const bool edge = kk < ilo || kk + 31 > ihi || (causal && kk + 31 > q0);
+        if (edge) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = kk + acc_row(r, hi);
+            const bool ok = key >= qlo && key <= qhi && (!causal || key <= qrow);
+            const float p = fast_exp2(fmaf(sc[r], kScaleL2, nlse2)) * drop_mul_x(D, dbase + (unsigned)(key >> 1) * 0xC2B2AE3Du, key & 1);
+            sc[r] = ok ? p : 0.f;
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            sc[r] = fast_exp2(fmaf(sc[r], kScaleL2, nlse2)) * drop_mul_x(D, dbase + (unsigned)((kk + acc_row(r, hi)) >> 1) * 0xC2B2AE3Du, r & 1);
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {      // registers [4g, 4g + 4) = keys kk + 8g + 4hi .. + 3 of the lane's query: 8 bytes of its row
+        uint2 v;
+        v.x = pack2bf(sc[4 * g + 0], sc[4 * g + 1]);
+        v.y = pack2bf(sc[4 * g + 2], sc[4 * g + 3]);
+        *reinterpret_cast<uint2*>(mypt + l31 * kPitch + (32 * j + 8 * g + 4 * hi) * 2) = v;
+      }
+    }
+    __syncthreads();     // the block is done with kt (next step's loads may land) and every wave's tile is complete in LDS
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 8 * i + (lane >> 3), c = lane & 7;
+      const int q = q0 + r, k = k0 + 8 * c;
+      if (q < S && k < S) {
+        const uint4 v = *reinterpret_cast<const uint4*>(mypt + r * kPitch + c * 16);
+        bf16_t* dst = obase + (size_t)q * S + k;
+        if (vec) {
+          typedef __attribute__((ext_vector_type(4))) unsigned nt_u32x4_t;
+          const nt_u32x4_t nv = {v.x, v.y, v.z, v.w};
+          __builtin_nontemporal_store(nv, reinterpret_cast<nt_u32x4_t*>(dst));      // S % 8 == 0: the piece ends inside the row; written once, not re-read here
+        } else {
+          const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (k + e < S) dst[e] = (bf16_t)(e & 1 ? w[e >> 1] >> 16 : w[e >> 1] & 0xffffu);
+        }
+      }
+    }
+  }
+}
+
+// rotated q|k|v of one layer as [B, S, w] (w = 3 d): rows of a sample from either token layout, zeros behind its tokens (packed rows: at
+// tokens without keys); one thread per 16-byte piece
+__global__ void __launch_bounds__(256) qkv_grid_kernel(const bf16_t* __restrict__ src, KeyRange KR, bf16_t* __restrict__ out, int B, int S, int w) {
+  const int cpr = w / 8;
+  const long n = (long)B * S * cpr;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long pos = i / cpr;
+    const int c = (int)(i % cpr);
+    const int b = (int)(pos / S), s = (int)(pos % S);
+    bool live;
+    long row = pos;
+    if (KR.lo) live = KR.lo[pos] <= KR.hi[pos];
+    else {
+      live = s < (KR.key_len ? KR.key_len[b] : S);
+      if (KR.row_base) row = (long)KR.row_base[b] + s;
+    }
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (live) v = *reinterpret_cast<const uint4*>(src + (size_t)row * w + c * 8);
+    *reinterpret_cast<uint4*>(out + (size_t)pos * w + c * 8) = v;
+  }
+}
+
 // waves (= 32-row tiles) per block: long sequences share each K/V (or Q/dO) tile among 4 waves through LDS
 int attn_waves(int S) { return S >= 128 ? 4 : (S >= 64 ? 2 : 1); }
 // GGET_ATTN_BY_SAMPLE=0: the S-keyed launches of rounds 1 - 5 for 32 < S <= 64 (A/B switch of the per-sample dispatch)
@@ -3216,6 +3370,38 @@ int k_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, i
   if (key_lo) { if (nw == 4) GGET_ATTN_FWD(4, true); else if (nw == 2) GGET_ATTN_FWD(2, true); else GGET_ATTN_FWD(1, true); }
   else { if (nw == 4) GGET_ATTN_FWD(4, false); else if (nw == 2) GGET_ATTN_FWD(2, false); else GGET_ATTN_FWD(1, false); }
 #undef GGET_ATTN_FWD
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+// attention weights of one layer from its rotated q | k and the forward's log-sum-exp (attn_probs_kernel); writes all of out [B,H,S,S]
+int k_attn_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                 const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed, hipStream_t st) {
+  GGET_REQUIRE(qkv && lse && out, "attn_probs: null argument");
+  GGET_REQUIRE(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attn_probs: bad shape B %d S %d H %d", B, S, H);
+  GGET_REQUIRE(!key_lo == !key_hi, "attn_probs: half a key range");
+  GGET_REQUIRE(!row_base || (key_len && !key_lo), "attn_probs: the var-len token layout needs key_len and excludes per-token key ranges");
+  GGET_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attn_probs: dropout_p %g outside [0, 1)", (double)dropout_p);
+  const KeyRange KR{key_lo ? nullptr : key_len, key_lo, key_hi, row_base};
+  const Drop D = make_drop(dropout_p, dropout_seed);
+  const int vec = (S % 8 == 0) && (((uintptr_t)out & 15) == 0);
+  const int nw = attn_waves(S);
+  dim3 grid((S + 32 * nw - 1) / (32 * nw), H, B);
+#define GGET_ATTN_PROBS(NW, PK) hipLaunchKernelGGL((attn_probs_kernel<NW, PK>), grid, dim3(NW * 64), 0, st, (const bf16_t*)qkv, lse, KR, \
+                                                   (bf16_t*)out, B, S, H, causal, D, vec)
+  if (key_lo) { if (nw == 4) GGET_ATTN_PROBS(4, true); else if (nw == 2) GGET_ATTN_PROBS(2, true); else GGET_ATTN_PROBS(1, true); }
+  else { if (nw == 4) GGET_ATTN_PROBS(4, false); else if (nw == 2) GGET_ATTN_PROBS(2, false); else GGET_ATTN_PROBS(1, false); }
+#undef GGET_ATTN_PROBS
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+// rotated q | k | v rows of a layer -> [B, S, w] (qkv_grid_kernel); w a multiple of 8
+int k_qkv_grid(const void* src, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo, const int32_t* key_hi, void* out,
+               int B, int S, int w, hipStream_t st) {
+  GGET_REQUIRE(src && out && B > 0 && S > 0 && w > 0 && w % 8 == 0, "qkv_grid: bad arguments");
+  const KeyRange KR{key_lo ? nullptr : key_len, key_lo, key_hi, row_base};
+  const long n = (long)B * S * (w / 8);
+  hipLaunchKernelGGL(qkv_grid_kernel, dim3((unsigned)std::min<long>(4096, (n + 255) / 256)), dim3(256), 0, st, (const bf16_t*)src, KR, (bf16_t*)out, B, S, w);
   GGET_LAUNCH_CHECK();
   return 0;
 }

@@ -2623,6 +2623,31 @@ extern "C" int gget_hidden_states_grid(gget_handle_t h, int layer, void* out_dev
   return k_rows_to_grid(src, h->wsp<int32_t>(h->ws.vl_pad2c), out_dev, n_pos, d, (hipStream_t)stream);
 }
 
+// Attention weights of decoder layer `layer` of the last forward (hf `output_attentions=True`, eager_attention_forward
+// modeling_llama.py:191-214): recomputed from the layer's rotated q | k and its log-sum-exp, both of which every forward mode keeps
+// in the workspace for the backward (pre-train, packed, fine-tune; either token layout; with or without labels).  The key masking, the
+// causal flag, the token layout and - apply_dropout != 0 - the dropout mask (probability and per-layer seed, attn_drop_seed + 0x9E37 *
+// layer) are those of that forward.  out_dev: bf16 [B, H, S, S].
+extern "C" int gget_attention_probs(gget_handle_t h, int layer, void* out_dev, int apply_dropout, void* stream) {
+  GGET_REQUIRE(h && out_dev, "null argument");
+  GGET_REQUIRE(h->fwd_valid && h->B > 0 && h->S > 0, "attention_probs: no valid forward has run on this handle");
+  GGET_REQUIRE(layer >= 0 && layer < h->cfg.num_layers, "attention_probs: layer %d out of range [0, %d)", layer, h->cfg.num_layers);
+  const LayerWs& lw = h->ws.lw[layer];
+  return k_attn_probs(h->wsp<bf16_t>(lw.qkv), h->wsp<float>(lw.lse), h->packed ? nullptr : h->wsp<int32_t>(h->ws.key_len), h->row_base(),
+                      h->klo(), h->khi(), out_dev, h->B, h->S, h->cfg.num_heads, h->cfg.causal, apply_dropout ? h->attn_drop_p : 0.f,
+                      h->attn_drop_seed + 0x9E37u * (unsigned)layer, (hipStream_t)stream);
+}
+
+// The rotated q | k | v of decoder layer `layer` of the last forward as a copy in the [B, S, 3 d] layout, from either token layout (the
+// twin of gget_hidden_states_grid for the operands of gget_attention_probs); zeros behind a sample's tokens.
+extern "C" int gget_layer_qkv_grid(gget_handle_t h, int layer, void* out_dev, void* stream) {
+  GGET_REQUIRE(h && out_dev, "null argument");
+  GGET_REQUIRE(h->fwd_valid && h->B > 0 && h->S > 0, "layer_qkv_grid: no valid forward has run on this handle");
+  GGET_REQUIRE(layer >= 0 && layer < h->cfg.num_layers, "layer_qkv_grid: layer %d out of range [0, %d)", layer, h->cfg.num_layers);
+  return k_qkv_grid(h->wsp<bf16_t>(h->ws.lw[layer].qkv), h->packed ? nullptr : h->wsp<int32_t>(h->ws.key_len), h->row_base(), h->klo(),
+                    h->khi(), out_dev, h->B, h->S, 3 * h->cfg.hidden_size, (hipStream_t)stream);
+}
+
 // ================================================================================================
 // operator-level entry points
 // ================================================================================================
@@ -2844,6 +2869,11 @@ extern "C" int gget_op_attn_bwd_ranges(const void* qkv, const void* out, const v
   GGET_REQUIRE(key_lo && key_hi, "attn_bwd_ranges: null ranges");
   return k_attn_bwd(qkv, out, dout, lse, nullptr, dqkv, delta_ws, B, S, H, causal, nullptr, nullptr, nullptr, 0, dropout_p,
                     dropout_seed, (hipStream_t)stream, key_lo, key_hi);
+}
+extern "C" int gget_op_attn_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                                  const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, uint32_t dropout_seed,
+                                  void* stream) {
+  return k_attn_probs(qkv, lse, key_len, row_base, key_lo, key_hi, out, B, S, H, causal, dropout_p, dropout_seed, (hipStream_t)stream);
 }
 extern "C" int gget_op_ranges_from_mask3d(const int64_t* mask3d, int32_t* key_lo, int32_t* key_hi, int B, int S, void* stream) {
   GGET_REQUIRE(mask3d && key_lo && key_hi, "ranges_from_mask3d: null argument");

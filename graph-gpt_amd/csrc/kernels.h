@@ -189,6 +189,13 @@ int k_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, i
                const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
                unsigned dropout_seed, hipStream_t st, const int32_t* key_lo = nullptr, const int32_t* key_hi = nullptr,
                const int32_t* row_base = nullptr, const int32_t* long_list = nullptr);
+// attention weights of one layer, bf16 [B,H,S,S] = m * exp(q k / 8 - lse) on the allowed keys, 0 elsewhere (attention.hip:
+// attn_probs_kernel); qkv holds rotated q | k; row_base != NULL: var-len token layout; key_lo / key_hi != NULL: packed rows
+int k_attn_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                 const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed, hipStream_t st);
+// q | k | v rows of a layer copied into the [B, S, w] grid from either token layout, zeros behind a sample's tokens
+int k_qkv_grid(const void* src, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo, const int32_t* key_hi, void* out,
+               int B, int S, int w, hipStream_t st);
 // S <= 32: attention (all heads of a sample), the o projection + residual add and the RMSNorm behind it in one launch, one workgroup
 // per sample (attention.hip: attn_oproj_fwd_kernel).  qkv rotated [rows, 3d]; writes attn_out [rows, d] (kept for the backward), lse,
 // x_mid = x_in + attn_out Wo^T, xn = rmsnorm(x_mid) * nw, rstd [rows].  *taken = 1 when it ran (S <= 32, H in {2, 4, 8, 12, 16},

@@ -598,6 +598,20 @@ class Engine:
         """bf16 [B,S,d] residual stream entering decoder layer `layer` (num_layers = leaving the last one) of the last forward (a copy)."""
         return self._hidden_grid(int(layer), B, S)
 
+    def attention_probs(self, layer: int, B: int, S: int, apply_dropout: bool = False) -> torch.Tensor:
+        """bf16 [B,H,S,S] attention weights of decoder layer `layer` of the last forward (gget_attention_probs: recomputed from the layer's
+        rotated q | k and log-sum-exp; either token layout, packed rows too).  apply_dropout: with that forward's dropout mask applied."""
+        out = torch.empty(B, self.spec.num_heads, S, S, dtype=torch.bfloat16, device=self.device)
+        L.check(self.lib.gget_attention_probs(self.h, int(layer), _ptr(out), int(bool(apply_dropout)), _stream()))
+        return out
+
+    def layer_qkv(self, layer: int, B: int, S: int) -> torch.Tensor:
+        """bf16 [B,S,3d] rotated q | k | v of decoder layer `layer` of the last forward (a copy; either token layout; zeros behind a
+        sample's tokens - gget_layer_qkv_grid)."""
+        out = torch.empty(B, S, 3 * self.spec.hidden_size, dtype=torch.bfloat16, device=self.device)
+        L.check(self.lib.gget_layer_qkv_grid(self.h, int(layer), _ptr(out), _stream()))
+        return out
+
     def _hidden_grid(self, layer: int, B: int, S: int) -> torch.Tensor:
         out = torch.empty(B, S, self.spec.hidden_size, dtype=torch.bfloat16, device=self.device)
         L.check(self.lib.gget_hidden_states_grid(self.h, layer, _ptr(out), _stream()))

@@ -516,6 +516,21 @@ class _GgetModel(nn.Module):
         e = self._engine
         return tuple(e.layer_hidden_states(i, B, S) for i in range(self.spec.num_layers)) + (e.hidden_states(B, S),)
 
+    def _want_attentions(self, output_attentions):
+        """hf resolve: the call's flag, else config.output_attentions (modeling_helpers.resolve_forward_defaults)."""
+        if output_attentions is None:
+            output_attentions = getattr(self.config, "output_attentions", False)
+        return bool(output_attentions)
+
+    def _collect_attentions(self, B, S):
+        """`outputs.attentions` of the reference's backbone with output_attentions=True: a tuple of L tensors [B,H,S,S], the softmax
+        weights of hf eager_attention_forward (modeling_llama.py:191-214) - after the attention dropout exactly when the reference applies
+        it (training mode and attention_dropout > 0).  bf16, recomputed by gget_attention_probs from what the forward kept; rows of padding
+        queries read as zero (the reference computes a softmax there that nothing uses)."""
+        e = self._engine
+        drop = bool(self.training) and float(self.config.attention_dropout) > 0.0
+        return tuple(e.attention_probs(i, B, S, apply_dropout=drop) for i in range(self.spec.num_layers))
+
     def _wrap_loss(self, loss):
         if loss is None:
             return None
@@ -565,6 +580,8 @@ class GraphGPTPretrainBase(_GgetModel):
         out = _PretrainOutput(self._wrap_loss(loss), _LazyLogits(self))
         if want_hs:
             out.hidden_states = self._collect_hidden_states(B, S)       # modeling_pretrain.py:264 (outputs.hidden_states)
+        if self._want_attentions(output_attentions):
+            out.attentions = self._collect_attentions(B, S)             # modeling_pretrain.py:265 (outputs.attentions)
         return out
 
 
@@ -625,7 +642,8 @@ class GraphGPTTaskModel(_GgetModel):
         loss, logits, hid = e.forward_task(input_ids, attention_mask, position_ids, task_labels, sample_wgt, code, num_tokens=n_real)
         return DoubleHeadsModelOutput(pretrain_loss=None, task_loss=self._wrap_loss(loss), pretrain_logits=None,
                                       task_logits=logits, task_hidden_states=hid,
-                                      hidden_states=self._collect_hidden_states(B, S) if want_hs else None)   # modeling_finetune.py:323
+                                      hidden_states=self._collect_hidden_states(B, S) if want_hs else None,   # modeling_finetune.py:323
+                                      attentions=self._collect_attentions(B, S) if self._want_attentions(output_attentions) else None)   # :325
 
 
 def freeze_llama_layers(model, freeze_layer_count: int = 0):

@@ -476,6 +476,23 @@ int gget_layer_hidden_states(gget_handle_t h, int layer, const void** hidden_dev
  * stream entering that layer (hf LlamaModel.forward :401-414).  After a var-len forward the rows go back to their (b, s) positions;
  * positions behind a sample's tokens read as zero.  out_dev: bf16 [B * S * hidden] for the last forward's B and S. */
 int gget_hidden_states_grid(gget_handle_t h, int layer, void* out_dev, void* stream);
+/* replaces: `output_attentions=True` - `outputs.attentions` as the model classes hand it through (modeling_pretrain.py:265,
+ * modeling_finetune.py:325, documented at modeling_common.py:79): the softmax weights of hf eager_attention_forward (modeling_llama.py
+ * :191-214) of decoder layer `layer` of the LAST forward, recomputed from that layer's rotated q | k and its log-sum-exp, which every
+ * forward mode keeps in the workspace - pre-train, packed and fine-tune forwards, either token layout, with or without labels: no mode is
+ * refused.  out_dev: bf16 [B, H, S, S] for that forward's B and S, every element written (the caller may pass uninitialised memory).
+ * apply_dropout != 0: the weights after the attention dropout of that forward (its mask, kept elements times 1 / (1 - p), what the
+ * reference returns in training mode); no effect when that forward's attention dropout was 0.  The probability and seed are the ones
+ * gget_set_dropout holds: as for the backward, do not change them between the forward and this call.
+ * One stated difference: the rows of padding queries (q >= the sample's length; a packed token without keys) read as ZERO, where the
+ * reference returns a softmax of meaningless queries that nothing consumes (gget_hidden_states_grid follows the same rule).
+ * Error (text in gget_last_error) and no launch: no valid forward on the handle, `layer` outside [0, num_layers). */
+int gget_attention_probs(gget_handle_t h, int layer, void* out_dev, int apply_dropout, void* stream);
+/* replaces: the query_states / key_states / value_states of hf LlamaAttention.forward (modeling_llama.py:243-281) behind
+ * apply_rotary_pos_emb, of decoder layer `layer` of the last forward: a COPY of the layer's q | k | v (q and k rotated) in the
+ * [B, S, 3 hidden] layout (q | k | v, head h at column h * 64 of each third), after a forward on either token layout; zeros behind a
+ * sample's tokens.  The twin of gget_hidden_states_grid for the operands of gget_attention_probs.  out_dev: bf16 [B * S * 3 * hidden]. */
+int gget_layer_qkv_grid(gget_handle_t h, int layer, void* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Operator-level entry points (the individual HIP kernels), used by the parity tests and by
@@ -669,6 +686,19 @@ int gget_op_attn_bwd_ranges(const void* qkv, const void* out, const void* dout, 
                             const int32_t* key_hi, void* dqkv, float* delta_ws, int B, int S, int H, int causal,
                             float dropout_p, uint32_t dropout_seed, void* stream);
 int gget_op_ranges_from_mask3d(const int64_t* mask3d, int32_t* key_lo, int32_t* key_hi, int B, int S, void* stream);
+/* replaces: the attn_weights hf eager_attention_forward returns (modeling_llama.py:191-214: softmax of the masked scores in fp32, cast, then
+ * dropout) - the operator behind gget_attention_probs with every argument:
+ *   out[b,h,q,k] = bf16(m * exp(<q_bhq, k_bhk> / 8 - lse[b,h,q])) for an allowed key, 0 otherwise;  out bf16 [B, H, S, S], all written.
+ * qkv holds ROTATED q | k (the engine's layout; v is not read), [B * S, 3 * 64 H] or - row_base != NULL, int32 [B] - the var-len token
+ * layout of gget_op_attn_fwd_varlen.  lse: f32 [B, H, S] as every forward entry writes it - the NATURAL log of sum_k exp(score / 8) over
+ * the allowed keys, before dropout.  Allowed keys: k < key_len[b] for queries q < key_len[b] (key_len NULL = S), k <= q when causal;
+ * or - key_lo / key_hi != NULL, int32 [B, S], packed rows - key_lo[b,q] <= k <= key_hi[b,q] (an empty range gives a zero row).
+ * m = 1 for dropout_p = 0, else the keep multiplier 0 or 1 / (1 - p) of the forward run with the same (dropout_p, dropout_seed).
+ * MFMA scores with fp32 accumulation, fp32 exponent, one rounding to bf16; no atomics (reruns are bit-identical).  NULL qkv / lse / out,
+ * B, S or H <= 0 and half a key range are errors and launch nothing. */
+int gget_op_attn_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                       const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, uint32_t dropout_seed,
+                       void* stream);
 /* gget_op_attn_bwd / _ranges (no RoPE) through the ONE-PASS long-sequence backward (S >= 256; shorter rows run the usual kernels and leave
  * the workspace alone): S, dP and the softmax backward are evaluated once, dK / dV and dQ come out of the same pass (5 matmuls of hf
  * eager_attention_forward's autograd graph, modeling_llama.py:191-214, instead of the 7 of the two-kernel form).  dq_ws: bf16
