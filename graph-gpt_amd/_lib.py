@@ -162,6 +162,20 @@ SIGNATURES = {
     "gget_op_scatter_rows_f32": (i32, [vp, vp, vp, i32, i32, vp]),
     "gget_op_head_linear_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "gget_op_head_linear_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "gget_op_lengths": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp]),
+    "gget_op_sum_lengths": (i32, [vp, i32, vp, vp]),
+    "gget_op_varlen_plan": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "gget_op_rows_to_grid": (i32, [vp, vp, vp, i64, i32, vp]),
+    "gget_op_head_compact_ws_bytes": (u64, [i32]),
+    "gget_op_head_compact": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gget_op_head_slot_sort": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]),
+    "gget_op_head_cell_sum": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_op_gather_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_op_gather_rows_remap": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "gget_op_sample_mask_wgt": (i32, [vp, vp, i32, i32, vp]),
+    "gget_op_raw_blend": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp]),
+    "gget_op_raw_tok_grad": (i32, [vp, vp, vp, i32, i32, vp]),
+    "gget_op_gemm_indexed": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
     "gget_op_rank_metrics_workspace": (C.c_size_t, [i32, i32]),
     "gget_op_rank_metrics": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "gget_op_link_hits_workspace": (C.c_size_t, [i32]),

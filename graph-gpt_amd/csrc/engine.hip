@@ -3065,6 +3065,96 @@ extern "C" int gget_op_head_linear_bwd(const float* dy, const void* x, const voi
   GGET_REQUIRE(dy && x && a && w && dw && dx && B > 0 && Din > 0 && Dout > 0, "head_linear_bwd: null argument or empty shape");
   return k_head_linear_bwd(dy, x, a, w, dw, dbias, dx, B, Din, Dout, layer, gget_engine::elem_drop(0.f, 0), (hipStream_t)stream);
 }
+// batch layout and SMTP-head index kernels: the launchers of csrc/kernels.h as they are (tests/test_gpu_plan.py)
+extern "C" int gget_op_lengths(const int64_t* mask, const int64_t* ids, int ldF, int pad_id, int32_t* key_len, int32_t* pool_row, int B,
+                               int S, void* stream) {
+  GGET_REQUIRE((key_len || pool_row) && (!pool_row || ids) && B > 0 && S > 0 && (!ids || ldF >= 1), "lengths: null argument or empty shape");
+  return k_lengths(mask, ids, ldF, pad_id, key_len, pool_row, B, S, (hipStream_t)stream);
+}
+extern "C" int gget_op_sum_lengths(const int32_t* key_len, int B, int32_t* out, void* stream) {
+  GGET_REQUIRE(key_len && out && B > 0, "sum_lengths: null argument or empty shape");
+  return k_sum_lengths(key_len, B, out, (hipStream_t)stream, nullptr);
+}
+extern "C" int gget_op_varlen_plan(const int64_t* ids, int ldF, int F, const int64_t* pos, int32_t* key_len, int32_t* pool_row, int32_t* cu,
+                                   int64_t* ids_c, int64_t* pos_c, int32_t* row_b, int32_t* pad2c, int32_t* c2p, int32_t* status, int B,
+                                   int S, int tc, int t_rows, int pad_id, int32_t* long_list, void* stream) {
+  GGET_REQUIRE(ids && key_len && cu && ids_c && pos_c && row_b && pad2c && c2p && status, "varlen_plan: null argument");
+  GGET_REQUIRE(B > 0 && S > 0 && F >= 1 && ldF >= F && tc >= 0 && t_rows >= tc, "varlen_plan: bad shape B %d S %d F %d ldF %d tc %d t_rows %d", B, S,
+               F, ldF, tc, t_rows);
+  return k_varlen_plan(ids, ldF, F, pos, key_len, pool_row, cu, ids_c, pos_c, row_b, pad2c, c2p, status, B, S, tc, t_rows, pad_id,
+                       (hipStream_t)stream, long_list);
+}
+extern "C" int gget_op_rows_to_grid(const void* src, const int32_t* pad2c, void* out, int64_t n_pos, int d, void* stream) {
+  GGET_REQUIRE(src && pad2c && out && n_pos >= 0 && d > 0 && d % 8 == 0, "rows_to_grid: null argument or bad shape (d must be a multiple of 8)");
+  return k_rows_to_grid(src, pad2c, out, (long)n_pos, d, (hipStream_t)stream);
+}
+extern "C" uint64_t gget_op_head_compact_ws_bytes(int T) { return T > 0 ? (uint64_t)k_head_compact_ws_bytes(T) : 0; }
+extern "C" int gget_op_head_compact(const int64_t* labels, int T, int n, int32_t* cnt, int32_t* m_off, int32_t* l_off, int32_t* counts,
+                                    int32_t* row_idx, int32_t* sel_src, int32_t* sel_label, int32_t* sel_tok, int32_t* ws,
+                                    int32_t* slot_hist, void* stream) {
+  GGET_REQUIRE(cnt && m_off && l_off && counts && row_idx && sel_src && sel_label && sel_tok && ws, "head_compact: null argument");
+  GGET_REQUIRE(T > 0 && n >= 1, "head_compact: bad shape T %d n %d", T, n);
+  return k_head_compact(labels, T, n, cnt, m_off, l_off, counts, row_idx, sel_src, sel_label, sel_tok, ws, slot_hist, (hipStream_t)stream);
+}
+extern "C" int gget_op_head_slot_sort(const int32_t* sel_src, const int32_t* row_idx, const int32_t* lm_count, int32_t* slot_state,
+                                      int32_t* a_tok, int32_t* a_cell, int32_t* c_l, int32_t* cellpos, int32_t* tile_off, int32_t* total_p,
+                                      int cap, int n, int64_t slot_elems, int tile_rows, void* stream) {
+  GGET_REQUIRE(sel_src && row_idx && lm_count && slot_state && a_tok && a_cell && c_l && cellpos && tile_off && total_p,
+               "head_slot_sort: null argument");
+  GGET_REQUIRE(cap > 0 && n >= 1 && tile_rows > 0 && slot_elems >= 0, "head_slot_sort: bad shape cap %d n %d tile_rows %d", cap, n, tile_rows);
+  return k_head_slot_sort(sel_src, row_idx, lm_count, slot_state, a_tok, a_cell, c_l, cellpos, tile_off, total_p, cap, n, (long)slot_elems,
+                          tile_rows, (hipStream_t)stream);
+}
+extern "C" int gget_op_head_cell_sum(const void* dxs, const int32_t* cellpos, const int32_t* cnt, const int32_t* l_off, const int32_t* pad2c,
+                                     void* dhid, int TP, int d, int pad_row, void* stream) {
+  GGET_REQUIRE(dxs && cellpos && cnt && l_off && dhid && TP > 0 && d > 0 && d % 8 == 0 && pad_row >= 0,
+               "head_cell_sum: null argument or bad shape (d must be a multiple of 8)");
+  return k_head_cell_sum(dxs, cellpos, cnt, l_off, pad2c, dhid, TP, d, pad_row, (hipStream_t)stream);
+}
+extern "C" int gget_op_gather_rows(const void* src, const int32_t* idx, const int32_t* count, void* dst, int cap, int d, int scatter,
+                                   void* stream) {
+  GGET_REQUIRE(src && idx && count && dst && cap >= 0 && d > 0 && d % 8 == 0, "gather_rows: null argument or bad shape (d must be a multiple of 8)");
+  return k_gather_rows(src, idx, count, dst, cap, d, scatter, (hipStream_t)stream);
+}
+extern "C" int gget_op_gather_rows_remap(const void* src, int32_t* idx, const int32_t* count, const int32_t* pad2c, void* dst, int cap, int d,
+                                         int pad_row, int32_t* status, void* stream) {
+  GGET_REQUIRE(src && idx && count && pad2c && dst && cap >= 0 && d > 0 && d % 8 == 0 && pad_row >= 0,
+               "gather_rows_remap: null argument or bad shape (d must be a multiple of 8)");
+  return k_gather_rows_remap(src, idx, count, pad2c, dst, cap, d, pad_row, status, (hipStream_t)stream);
+}
+extern "C" int gget_op_sample_mask_wgt(const int64_t* labels, float* w, int B, int cells, void* stream) {
+  GGET_REQUIRE(labels && w && B >= 0 && cells >= 1, "sample_mask_wgt: null argument or empty shape");
+  return k_sample_mask_wgt(labels, w, B, cells, (hipStream_t)stream);
+}
+extern "C" int gget_op_raw_blend(const float* raw, const int64_t* labels, int n, int first_only, const void* tok, void* out, int32_t* flag,
+                                 int T, int e, const int32_t* rows_map, int n_logical, void* stream) {
+  GGET_REQUIRE(raw && tok && out && flag && T >= 0 && e > 0 && (!labels || n >= 1) && (!rows_map || n_logical >= 0),
+               "raw_blend: null argument or bad shape");
+  return k_raw_blend(raw, labels, n, first_only != 0, tok, out, flag, T, e, (hipStream_t)stream, rows_map, n_logical);
+}
+extern "C" int gget_op_raw_tok_grad(const void* dx, const int32_t* flag, float* dtok, int T, int e, void* stream) {
+  GGET_REQUIRE(dx && flag && dtok && T >= 0 && e > 0, "raw_tok_grad: null argument or empty shape");
+  return k_raw_tok_grad(dx, flag, dtok, T, e, (hipStream_t)stream);
+}
+extern "C" int gget_op_gemm_indexed(int mode, const void* A, const void* B, void* C, int M_cap, int N, int K, int lda, int ldb, int ldc,
+                                    const int32_t* m_dev, const int32_t* a_rows, const int32_t* b_tile_off, int b_tile_rows,
+                                    const int32_t* c_rows, void* stream) {
+  GGET_REQUIRE(A && B && C && M_cap >= 0 && N > 0 && K > 0, "gemm_indexed: null argument or empty shape");
+  if (!a_rows && !b_tile_off)
+    return gget_gemm_single(mode, GGET_EPI_NONE, A, B, C, nullptr, M_cap, N, K, lda, ldb, ldc, m_dev, nullptr, 1, (hipStream_t)stream, false,
+                            c_rows);
+  GGET_REQUIRE(b_tile_rows == 128 || b_tile_rows == 256, "gemm_indexed: b_tile_rows %d is neither 128 nor 256", b_tile_rows);
+  GemmGroup g;
+  memset(&g, 0, sizeof(g));
+  g.count = 1;
+  GemmProblem& p = g.p[0];
+  p.A = static_cast<const bf16_t*>(A); p.B = static_cast<const bf16_t*>(B); p.C = C;
+  p.M = M_cap; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+  p.m_dev = m_dev;
+  p.a_rows = a_rows; p.b_tile_off = b_tile_off; p.c_rows = c_rows;
+  p.b_tile_rows = b_tile_rows;
+  return gget_gemm_launch(mode, GGET_EPI_NONE, g, 1, (hipStream_t)stream);
+}
 
 
 // ================================================================================================

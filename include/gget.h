@@ -816,6 +816,82 @@ int gget_op_head_linear_bwd(const float* dy, const void* x, const void* a, const
                             int Din, int Dout, int layer, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The integer machinery of a pre-training step, one launcher at a time (csrc/kernels.h; no arithmetic in the wrappers): the padding-free
+ * token layout, the SMTP head's compaction / slot sort / scatter, the indexed GEMM that feeds the sorted head, and the small
+ * row-selection kernels.  tests/test_gpu_plan.py holds every output integer-exact or bit for bit (tests/_plan_ref.py states each
+ * operation); INTEGRATION.md "The batch-layout and SMTP-head index kernels" lists the contract each entry is held to.
+ * ------------------------------------------------------------------------------------------ */
+/* key_len[b] (may be NULL) = non-zeros of mask int64 [B,S] (mask NULL: S); pool_row[b] (may be NULL, needs ids) = b S + (p - 1 + S) % S with
+ * p = entries of ids[b, :, 0] (int64 [B,S,ldF]) that differ from pad_id - an all-pad row gives b S + S - 1 */
+int gget_op_lengths(const int64_t* mask, const int64_t* ids, int ldF, int pad_id, int32_t* key_len, int32_t* pool_row, int B, int S,
+                    void* stream);
+/* *out = sum of key_len int32 [B] (one block, any B >= 1) */
+int gget_op_sum_lengths(const int32_t* key_len, int B, int32_t* out, void* stream);
+/* Var-len layout of a right-padded batch on tc token rows rounded up to t_rows.  cu int32 [B+1] = exclusive scan of key_len (cu[B] = the
+ * total), every sample cut at tc (key_len is rewritten where it was cut); ids_c int64 [t_rows,F], pos_c int64 [t_rows] (pos NULL: the
+ * token's s), row_b int32 [t_rows], c2p int32 [t_rows] (= b S + s) of compact row cu[b] + s; pad2c int32 [B S] = compact row or -1; tail
+ * rows [tc, t_rows): pad_id, position 0, sample 0, c2p = B S + (r - tc).  pool_row (may be NULL; b S + p on entry) becomes
+ * cu[b] + clamp(p, 0, len - 1).  long_list (may be NULL) int32 [3 B + 1]: [0] = number of samples of 33 .. 64 rows, then their indices,
+ * first rows (at 1 + B) and row counts (at 1 + 2 B) in batch order.  status int32 [3]: [0] = 1 if sum(key_len) != tc else 0, [2] = 1
+ * (sticky, never cleared here) in the same case, [1] untouched.  With tc > sum the rows [sum, tc) are not written. */
+int gget_op_varlen_plan(const int64_t* ids, int ldF, int F, const int64_t* pos, int32_t* key_len, int32_t* pool_row, int32_t* cu,
+                        int64_t* ids_c, int64_t* pos_c, int32_t* row_b, int32_t* pad2c, int32_t* c2p, int32_t* status, int B, int S, int tc,
+                        int t_rows, int pad_id, int32_t* long_list, void* stream);
+/* out bf16 [n_pos,d] = src[pad2c[i]], a zero row where pad2c[i] < 0; d % 8 == 0 */
+int gget_op_rows_to_grid(const void* src, const int32_t* pad2c, void* out, int64_t n_pos, int d, void* stream);
+/* SMTP head compaction over labels int64 [T,n] (NULL: every cell selected; -100 = unlabelled), in (token, slot) order: cnt[t] = labelled
+ * cells of token t, m_off[t] / l_off[t] = selected tokens / labelled cells before t, counts = (M, Lm); row_idx[m] = token of selected row
+ * m; per labelled cell l: sel_src[l] = m n + f, sel_label[l], sel_tok[l] = t.  Entries at or behind M / Lm are not written.  slot_hist
+ * (may be NULL) int32 [n]: the cells of every slot are ADDED to it when n <= 32, it is left alone when n > 32.  ws: int32 scratch of
+ * gget_op_head_compact_ws_bytes(T) bytes.  T >= 1. */
+uint64_t gget_op_head_compact_ws_bytes(int T);
+int gget_op_head_compact(const int64_t* labels, int T, int n, int32_t* cnt, int32_t* m_off, int32_t* l_off, int32_t* counts,
+                         int32_t* row_idx, int32_t* sel_src, int32_t* sel_label, int32_t* sel_tok, int32_t* ws, int32_t* slot_hist,
+                         void* stream);
+/* Sorts the min(cap, *lm_count) labelled cells by slot f = sel_src % n, every slot padded to a multiple of tile_rows.  slot_state int32
+ * [3 n + 2]: [0, n) the cells per slot on entry (gget_op_head_compact's slot_hist), [n, 2 n) cursors and [3 n + 1] a ticket, zero on entry;
+ * on return [0, 2 n) and the ticket are zero again (self-clearing: the next call needs no memset) and [2 n, 3 n] hold the padded slot
+ * starts.  Position p of slot f's range [start_f, start_f + cells_f): a_cell[p] = the cell's sel_src, a_tok[p] = row_idx[a_cell[p] / n],
+ * c_l[p] = its l, cellpos[l] = p - the ORDER INSIDE A SLOT IS FREE (it comes from atomics).  Pad positions up to start_{f+1}: a_tok =
+ * a_cell = 0, c_l = -1.  tile_off[t] = f * slot_elems for every tile_rows-row tile of slot f; *total_p = the padded total.  n <= 32,
+ * cap >= 1; a_tok / a_cell / c_l hold cap + n * tile_rows entries. */
+int gget_op_head_slot_sort(const int32_t* sel_src, const int32_t* row_idx, const int32_t* lm_count, int32_t* slot_state, int32_t* a_tok,
+                           int32_t* a_cell, int32_t* c_l, int32_t* cellpos, int32_t* tile_off, int32_t* total_p, int cap, int n,
+                           int64_t slot_elems, int tile_rows, void* stream);
+/* dhid bf16 row r(t) = bf16_rne(fp32 sum over j = 0 .. cnt[t] - 1, in that order, of dxs[cellpos[l_off[t] + j]]) for every token t < TP
+ * with cnt[t] > 0 (cnt <= 64); r(t) = t, or pad2c[t] (pad_row where that is negative) when pad2c is given; rows of tokens with cnt == 0
+ * are not written.  d % 8 == 0. */
+int gget_op_head_cell_sum(const void* dxs, const int32_t* cellpos, const int32_t* cnt, const int32_t* l_off, const int32_t* pad2c,
+                          void* dhid, int TP, int d, int pad_row, void* stream);
+/* rows i < min(cap, *count): gather dst[i] = src[idx[i]], or scatter (scatter != 0) dst[idx[i]] = src[i]; bf16 rows of d % 8 == 0
+ * elements; other rows of dst are not written */
+int gget_op_gather_rows(const void* src, const int32_t* idx, const int32_t* count, void* dst, int cap, int d, int scatter, void* stream);
+/* rows i < min(cap, *count): r = pad2c[idx[i]] (pad_row and status[2] = 1 where that is negative; status may be NULL), dst[i] = src[r],
+ * idx[i] = r (rewritten in place).  Without a negative entry status is not written. */
+int gget_op_gather_rows_remap(const void* src, int32_t* idx, const int32_t* count, const int32_t* pad2c, void* dst, int cap, int d,
+                              int pad_row, int32_t* status, void* stream);
+/* w[b] = 1.0f / ((float)tot_b + 1e-7f), tot_b = entries of labels int64 [B,cells] that are not -100 */
+int gget_op_sample_mask_wgt(const int64_t* labels, float* w, int B, int cells, void* stream);
+/* raw-embedding inputs: out bf16 [T,e] row t = bf16_rne(raw f32 row lt), or tok bf16 [e] when every label (first_only: the first label) of
+ * labels int64 row lt [n] is set (!= -100); flag[t] = 1 on the replaced rows, else 0.  lt = rows_map[t] (NULL: t); lt >= n_logical: a zero
+ * row, flag 0.  labels NULL: no row is replaced. */
+int gget_op_raw_blend(const float* raw, const int64_t* labels, int n, int first_only, const void* tok, void* out, int32_t* flag, int T,
+                      int e, const int32_t* rows_map, int n_logical, void* stream);
+/* dtok f32 [e] += sum over the rows t < T with flag[t] != 0 of dx bf16 [T,e] (fp32 atomics, one per 256-row block and column) */
+int gget_op_raw_tok_grad(const void* dx, const int32_t* flag, float* dtok, int T, int e, void* stream);
+/* The indexed GEMM of the slot-sorted head, C = op(A) op(B) in bf16 with the plain epilogue, mode GGET_GEMM_NT / GGET_GEMM_NN, rows
+ * m < min(M_cap, *m_dev) (m_dev is required with a_rows / b_tile_off):
+ *   a_rows      row m of the product reads row a_rows[m] of A (repeats allowed);
+ *   b_tile_off  the B operand of row tile t starts b_tile_off[t] ELEMENTS behind B; the tile height is b_tile_rows = 256 when N % 256 == 0,
+ *               else 128 (a b_tile_rows of 256 falls back to 128-row tiles, and b_tile_off is then indexed by 128-row tile);
+ *   c_rows      row m is stored at row c_rows[m] of C; a NEGATIVE entry means the row is NOT STORED.
+ * N % 192 == 0, K % 64 == 0.  With a_rows and b_tile_off both NULL this is the plain single-problem launch with the c_rows scatter
+ * (any mode the plain epilogue supports; m_dev optional). */
+int gget_op_gemm_indexed(int mode, const void* A, const void* B, void* C, int M_cap, int N, int K, int lda, int ldb, int ldc,
+                         const int32_t* m_dev, const int32_t* a_rows, const int32_t* b_tile_off, int b_tile_rows, const int32_t* c_rows,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rank metrics of the multi-label evaluation pass (csrc/metrics.hip; the Python surface is graph-gpt_amd/metrics.py rank_metrics).
  * replaces: MultiLabelClassificationMetrics.compute (src/utils/metrics_utils.py:112-114: torcheval BinaryAUROC over num_labels tasks),
  * `_eval_rocauc` (src/utils/ogb_utils.py:13-29: scikit-learn roc_auc_score column by column on the host - ogbn-proteins :71-79, ogbg-molhiv
