@@ -2778,6 +2778,11 @@ extern "C" int gget_op_unmask_origin(int64_t* x, const int64_t* cand, int B, int
   GGET_REQUIRE(x && cand && B >= 0 && N >= 0, "unmask_origin: bad arguments");
   return k_unmask_origin(x, cand, B, N, p_transfer, seed, mask_token_id, (hipStream_t)stream);
 }
+extern "C" int gget_op_unmask_origin_rows(int64_t* x, const int64_t* cand, int B, int N, const float* p_transfer, uint32_t seed,
+                                          int mask_token_id, void* stream) {
+  GGET_REQUIRE(x && cand && p_transfer && B >= 0 && N >= 0, "unmask_origin_rows: bad arguments");
+  return k_unmask_origin_rows(x, cand, B, N, p_transfer, seed, mask_token_id, (hipStream_t)stream);
+}
 extern "C" int gget_op_token_confidence(const void* logits, int ld, int R, int V, int mode, float* conf, int64_t* tok, void* stream) {
   GGET_REQUIRE(logits && conf && tok, "token_confidence: null argument");
   GGET_REQUIRE(R >= 0 && V >= 2 && ld >= V && mode >= 0 && mode <= 2, "token_confidence: bad arguments (R %d V %d ld %d mode %d)", R, V, ld, mode);

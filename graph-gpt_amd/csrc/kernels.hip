@@ -2584,6 +2584,18 @@ __global__ void __launch_bounds__(kBlock) unmask_origin_kernel(int64_t* __restri
   }
 }
 
+// the same update with one p_transfer per sample (the per-example schedule of sample_per_example, generation_utils.py:379-392: every
+// sample walks its own time grid; a finished sample carries p = 0)
+__global__ void __launch_bounds__(kBlock) unmask_origin_rows_kernel(int64_t* __restrict__ x, const int64_t* __restrict__ cand, int B, int N,
+                                                                    const float* __restrict__ p_transfer, unsigned seed, int mask_id) {
+  const long total = (long)B * N;
+  for (long w = (long)blockIdx.x * kBlock + threadIdx.x; w < total; w += (long)gridDim.x * kBlock) {
+    const unsigned b = (unsigned)(w / N), n = (unsigned)(w % N);
+    const float u = (float)smtp_rng(seed, 34, b, n) * (1.0f / 16777216.0f);
+    if (x[w] == mask_id && u < p_transfer[b]) x[w] = cand[w];
+  }
+}
+
 // first / last non-zero of every row of a [B,S,S] int64 mask: one wave per row (block-diagonal packing masks,
 // reference src/utils/tokenizer_utils.py:349-355).  An all-zero row (padding) gives lo = 0, hi = -1 (attends nothing).
 __global__ void __launch_bounds__(kBlock) ranges_from_mask3d_kernel(const int64_t* __restrict__ mask, int32_t* __restrict__ lo,
@@ -3604,6 +3616,13 @@ int k_token_sample(const void* logits, int ld, int R, int V, int mode, float tem
 int k_unmask_origin(int64_t* x, const int64_t* cand, int B, int N, float p_transfer, unsigned seed, int mask_id, hipStream_t st) {
   if ((long)B * N == 0) return 0;
   hipLaunchKernelGGL(unmask_origin_kernel, dim3(grid_for((long)B * N)), dim3(kBlock), 0, st, x, cand, B, N, p_transfer, seed, mask_id);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
+
+int k_unmask_origin_rows(int64_t* x, const int64_t* cand, int B, int N, const float* p_transfer, unsigned seed, int mask_id, hipStream_t st) {
+  if ((long)B * N == 0) return 0;
+  hipLaunchKernelGGL(unmask_origin_rows_kernel, dim3(grid_for((long)B * N)), dim3(kBlock), 0, st, x, cand, B, N, p_transfer, seed, mask_id);
   GGET_LAUNCH_CHECK();
   return 0;
 }

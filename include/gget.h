@@ -595,6 +595,30 @@ int gget_op_token_sample(const void* logits, int ld, int R, int V, int mode, flo
  * cand[b][n] where it is <mask> and the cell's own uniform draw is below p_transfer. */
 int gget_op_unmask_origin(int64_t* x, const int64_t* cand, int B, int N, float p_transfer, uint32_t seed, int mask_token_id,
                           void* stream);
+/* replaces: the alg = "origin" update of sample_per_example (src/utils/generation_utils.py:379-392) for a whole batch whose samples
+ * each walk their own time grid: as gget_op_unmask_origin with p_transfer[b] (f32 [B], device) read per sample. */
+int gget_op_unmask_origin_rows(int64_t* x, const int64_t* cand, int B, int N, const float* p_transfer, uint32_t seed,
+                               int mask_token_id, void* stream);
+/* replaces: the confidence-ranked update - confidence[~mask] = -inf, torch.topk, gather, where, scatter_ of
+ * _batch_unmask_without_for_loop (src/utils/generation_utils.py:197-236) and the topk / index write of sample_per_example
+ * (:402-433).  x i64 [B,N] in place, conf f32 [B,N], cand i64 [B,N]; p f32 on the device, read at p[b * p_stride] (p_stride 0: one
+ * value for the batch, 1: one per sample); n_revealed i32 [B] or NULL.  One workgroup per sample: n = (int)floorf((float)n_masked * p)
+ * (one fp32 multiply, = torch.floor(n_masked * p).int() and int(num_mask_token * (1 - s / t))), then cand is written into the n masked
+ * cells of largest confidence, ties to the lower cell index (torch.sort(descending=True, stable=True)); -0.0 == +0.0; unmasked cells
+ * are neither ranked nor written; confidences of masked cells must not be NaN.  Any N >= 0 (radix select over the row, no LDS per cell). */
+int gget_op_unmask_ranked(int64_t* x, const float* conf, const int64_t* cand, int B, int N, int mask_token_id, const float* p,
+                          int p_stride, int32_t* n_revealed, void* stream);
+/* replaces: the step rule of _batch_unmask_without_for_loop (src/utils/generation_utils.py:171-184) with its two .item() reads.
+ * p_tab f32 [steps] (device) holds 1 - t[i+1] / t[i], last entry 1; state_i (device word) holds i.  From m = max_b n_masked[b] the
+ * kernel advances i while i < steps until floorf(m * p_tab[i]) >= 1, stores i back, the p of the last rule iteration (0 when none
+ * ran: nothing masked, or i == steps) into p_word (device), and {i, any cell masked} into host_pair: two int32 of PINNED host memory,
+ * valid once the stream has passed the launch. */
+int gget_op_gen_plan(const int64_t* x, int B, int N, int mask_token_id, const float* p_tab, int steps, int32_t* state_i, float* p_word,
+                     int32_t* host_pair, void* stream);
+/* replaces: the counts behind cal_gen_acc_batch / cal_gen_acc_per_sample (src/utils/generation_utils.py:439-463): counts i32 [B,2] =
+ * {sum (gen == labels) & (input_ids == mask), sum (input_ids == mask)} over the N cells of every sample (all i64 [B,N]). */
+int gget_op_gen_acc(const int64_t* gen, const int64_t* labels, const int64_t* input_ids, int B, int N, int mask_token_id,
+                    int32_t* counts, void* stream);
 /* replaces: the collator's SMTP masking (prepare_inputs_for_pretrain_mlm, src/utils/tokenizer_utils.py:259-271 polynomial
  * schedule + _mask_stacked_input_ids_v2 :112-148, mtp (1,0,0)) for a right-padded batch ids [B,S,F] with lengths [B]:
  * per sample t = umr_min + (umr_max - umr_min) U, exactly ceil(len*F*(1 - t^power)) of its cells are masked (id -> 1

@@ -1,8 +1,13 @@
-"""`src.utils.log_eval_dump_utils` of the reference: the evaluation passes (log_eval_dump_utils.py:77-163, :242-304)."""
+"""`src.utils.log_eval_dump_utils` of the reference: the evaluation passes (log_eval_dump_utils.py:77-163, :242-304) and the
+generation evaluation (:308-447)."""
 import importlib as _il
 
 _t = _il.import_module("graph-gpt_amd.training")
+_g = _il.import_module("graph-gpt_amd.generation")
 evaluate = _t.evaluate
 ft_evaluate = _t.ft_evaluate
+evaluate_generation = _g.evaluate_generation
+eval_gen_per_batch = _g.eval_gen_per_batch
+eval_gen_per_sample = _g.eval_gen_per_sample
 
-__all__ = ["evaluate", "ft_evaluate"]
+__all__ = ["evaluate", "ft_evaluate", "evaluate_generation", "eval_gen_per_batch", "eval_gen_per_sample"]
