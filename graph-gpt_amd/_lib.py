@@ -187,8 +187,11 @@ SIGNATURES = {
     "gget_op_link_mrr_workspace": (C.c_size_t, [i32]),
     "gget_op_link_mrr": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "gget_op_cluster_metrics": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "gget_op_infer_append": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]),
+    "gget_op_node_records": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
 }
-CLUSTER_MAX_C = 2048   # include/gget.h GGET_CLUSTER_MAX_C: the classes the LDS tables of gget_op_cluster_metrics hold
+NODE_RECORDS_MAX_POS = 1 << 20   # include/gget.h GGET_NODE_RECORDS_MAX_POS: positions (B * S) one gget_op_node_records call takes
+CLUSTER_MAX_C = 2048  # include/gget.h GGET_CLUSTER_MAX_C: the classes the LDS tables of gget_op_cluster_metrics hold
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 OPT_NORM_FROM_BACKWARD = 1   # gget_set_option

@@ -671,7 +671,21 @@ def get_metrics(metric_type: str, device=None, num_labels: int = 2, on_device: b
     raise NotImplementedError(f"metric_type={metric_type!r} (sequence metrics are outside the hot-path scope)")
 
 
-HITS_DATASETS = {"ogbl-ppa": 100, "ogbl-ddi": 20}           # K of OGB's Hits@K evaluators
+def compare_metrics_res(curr_res, prev_best_res):
+    """reference `compare_metrics_res` (metrics_utils.py:192-208): (is `curr_res` the new best, the result to keep).  The result dicts
+    are compared on ONE key: their only key, or the single key that starts with "ema" (any case); a key that names an MAE or a loss is
+    better when smaller, every other one when larger, and a tie keeps the previous best."""
+    keys = list(curr_res.keys())
+    if len(keys) > 1:
+        keys = [k for k in keys if k.lower().startswith("ema")]
+        assert len(keys) == 1, f"curr_res keys: {list(curr_res.keys())}"
+    key = keys[0]
+    smaller_wins = any(word in key.lower() for word in ("mae", "loss"))
+    better = curr_res[key] < prev_best_res[key] if smaller_wins else curr_res[key] > prev_best_res[key]
+    return (True, curr_res) if better else (False, prev_best_res)
+
+
+HITS_DATASETS = {"ogbl-ppa": 100, "ogbl-ddi": 20}         # K of OGB's Hits@K evaluators
 MRR_DATASETS = {"ogbl-citation2": 1, "ogbl-wikikg2": 2}      # groups of `link_mrr` (wikikg2: head / tail batches)
 
 

@@ -885,6 +885,13 @@ def ft_evaluate(model, loader, *, problem_type: str = "single_label_classificati
     return test_loss, cls_metrics, res, input_dict
 
 
+def _format_eval_res(eval_res, rnd: int = 6):
+    """reference `format_ogb_output_for_csv` (ogb_utils.py:207-213): "key,value" pairs of a result dict, values rounded to 6 places."""
+    if isinstance(eval_res, dict):
+        return ",".join(f"{k},{round(v, rnd)}" for k, v in eval_res.items())
+    return eval_res
+
+
 # ----------------------------------------------------------------------------- pipeline
 class TrainingMode(abc.ABC):
     """Strategy interface of the reference (src/training/mode.py:46-89).  The dataset / tokenizer / sampler halves of
@@ -982,9 +989,14 @@ class TrainingMode(abc.ABC):
                              f"tokens/s/gpu {int(tokens) / dt:.0f}")
                 pipeline.log_lines.append(f"{pipeline.engine.global_steps},{float(loss):.6f},{pipeline.engine.last_lr:.6e}\n")
                 pipeline.model.check_deferred()      # device-side input guards (position ids), read where the loop syncs anyway
+            self.after_step(pipeline)
             if pipeline.max_steps and pipeline.engine.global_steps >= pipeline.max_steps:
                 break
         pipeline.model.check_deferred()
+
+    def after_step(self, pipeline) -> None:
+        """Called by the step loop behind every `train_step` (FinetuneMode: the epoch's end)."""
+        return None
 
 
 class PretrainMode(TrainingMode):
@@ -1027,9 +1039,174 @@ class PretrainMode(TrainingMode):
 
 
 class FinetuneMode(TrainingMode):
+    """Fine-tuning.  Constructed with evaluation loaders (`valid_loader` / `test_loader`, optionally `train_loader_for_eval`) the mode
+    closes every epoch the way the reference's `log_dump_ft_training_stats` does (log_eval_dump_utils.py:648-799, see `end_of_epoch`);
+    without them the run is the plain step loop.  An epoch is `steps_per_epoch` optimizer steps (default: samples_per_gpu //
+    batch_size of a reference-shaped config).  The `training.ft_eval` fields - `epoch_per_eval`, `save_pred`, `save_hidden_states`,
+    `eval_only`, `infer_only` - are read from a reference-shaped config; a keyword given here replaces the config's value.
+    `eval_kwargs` are `ft_evaluate`'s keywords (problem_type, num_labels, task_level, metric_type, dataset_name); what is not given
+    comes from the config (`model.ft_head`, `tokenization.data.dataset`) or the model.  `eval_only` trains nothing: every `epoch_k`
+    checkpoint under the checkpoint path (`training.pretrain_cpt`; `output_dir` of the lean config form) is loaded and evaluated
+    (finetune_mode.py:351-431).  `infer_only` replaces the evaluation by `dump_results` into `infer_writer`, any object with
+    `write(records, indices)` (:433-444; the reference's ODPS writer stays on the host side)."""
+
     model_cls = GraphGPTTaskModel
     skip_keys = True
     finetune = True
+    _FT_EVAL_DEFAULTS = dict(epoch_per_eval=1, save_pred=False, save_hidden_states=False, eval_only=False, infer_only=False)
+
+    def __init__(self, *args, valid_loader=None, test_loader=None, train_loader_for_eval=None, steps_per_epoch: Optional[int] = None,
+                 epoch_per_eval: Optional[int] = None, save_pred: Optional[bool] = None, save_hidden_states: Optional[bool] = None,
+                 eval_only: Optional[bool] = None, infer_only: Optional[bool] = None, infer_writer=None,
+                 eval_kwargs: Optional[Dict[str, Any]] = None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.valid_loader, self.test_loader, self.train_loader_for_eval = valid_loader, test_loader, train_loader_for_eval
+        self.steps_per_epoch, self.infer_writer, self.eval_kwargs = steps_per_epoch, infer_writer, dict(eval_kwargs or {})
+        self.epoch_per_eval, self.save_pred, self.save_hidden_states = epoch_per_eval, save_pred, save_hidden_states
+        self.eval_only, self.infer_only = eval_only, infer_only
+        self.best_res = self.best_epoch = None      # the best validation result so far (the EMA weights' when an EMA is attached)
+        self.epoch_results = []                     # one dict per evaluated epoch: losses, results, the files written
+        self._epochs_closed = 0
+
+    @property
+    def has_eval_loaders(self) -> bool:
+        return self.valid_loader is not None or self.test_loader is not None
+
+    # -- the ft_eval fields: keyword > reference-shaped config > default
+    def _resolve_ft_eval(self, cfg) -> None:
+        from . import conf as CF
+        tc = CF._get(cfg, "training") if cfg is not None and CF.is_reference_config(cfg) else None
+        ft_eval = CF._get(tc, "ft_eval") if tc is not None else None
+        for name, default in self._FT_EVAL_DEFAULTS.items():
+            if getattr(self, name) is None:
+                setattr(self, name, type(default)(CF._get(ft_eval, name, default) if ft_eval is not None else default))
+
+    def update_config(self, pipeline):
+        self._resolve_ft_eval(pipeline.cfg)
+
+    def allow_resume(self) -> bool:
+        return not self.eval_only           # finetune_mode.py: an eval_only run loads the epoch checkpoints itself
+
+    def allow_save_config(self) -> bool:
+        return not self.eval_only           # ... and writes neither a config nor a checkpoint
+
+    def setup_training(self, pipeline):
+        from . import conf as CF
+        self._resolve_ft_eval(pipeline.cfg)
+        if not self.has_eval_loaders:
+            if self.eval_only or self.infer_only:
+                raise ValueError("FinetuneMode(eval_only / infer_only): valid_loader / test_loader are needed")
+            return
+        if (self.eval_only or not self.infer_only) and (self.valid_loader is None or self.test_loader is None):
+            raise ValueError("FinetuneMode: the epoch's end evaluates valid AND test (log_dump_ft_training_stats): give both loaders")
+        if self.infer_only and (self.infer_writer is None or self.test_loader is None):
+            raise ValueError("FinetuneMode(infer_only=True): test_loader and infer_writer (an object with write(records, indices)) are needed")
+        if self.steps_per_epoch is None and pipeline.reference_cfg and self.samples_per_gpu:
+            self.steps_per_epoch = max(1, int(self.samples_per_gpu) // int(CF._get(pipeline.train_cfg, "batch_size")))
+        if not self.eval_only and not self.steps_per_epoch:
+            raise ValueError("FinetuneMode(steps_per_epoch=...): the optimizer steps of one epoch are needed to know where an epoch ends")
+        kw = self.eval_kwargs
+        if pipeline.reference_cfg:
+            head = CF._get(pipeline.model_cfg, "ft_head")
+            for ours, theirs in (("problem_type", "problem_type"), ("num_labels", "num_labels"), ("task_level", "task_type"),
+                                 ("metric_type", "metric_type")):
+                if ours not in kw and head is not None and CF._get(head, theirs) is not None:
+                    kw[ours] = CF._get(head, theirs)
+            if "dataset_name" not in kw and pipeline.data_cfg is not None and CF._get(pipeline.data_cfg, "dataset"):
+                kw["dataset_name"] = CF._get(pipeline.data_cfg, "dataset")
+        kw.setdefault("num_labels", int(pipeline.model.config.num_labels))
+        kw.setdefault("problem_type", pipeline.model.config.problem_type or ("regression" if kw["num_labels"] == 1 else "single_label_classification"))
+
+    # -- the epoch's end
+    def after_step(self, pipeline):
+        if not self.has_eval_loaders or not self.steps_per_epoch:
+            return
+        done = int(pipeline.engine.global_steps) // int(self.steps_per_epoch)
+        if done <= self._epochs_closed or int(pipeline.engine.global_steps) % int(self.steps_per_epoch):
+            return
+        self._epochs_closed = done
+        epoch = done - 1
+        if (epoch + 1) % int(self.epoch_per_eval) == 0:
+            self.end_of_epoch(pipeline, epoch)
+
+    def end_of_epoch(self, pipeline, epoch: int):
+        """reference log_dump_ft_training_stats (log_eval_dump_utils.py:648-799), in its order: (1) the checkpoint `epoch_<k>` (not under
+        eval_only); (2) `ft_evaluate` on train-for-eval, valid and test - with an EMA attached the valid pass once more under
+        `engine.ema_weights()`, and the test pass and the inference pass on the averaged weights; (3) the best validation result so far
+        by `compare_metrics_res` (the EMA result's when there is one; a result dict that names no single key to compare on - several
+        keys, none starting with "ema" - is not ranked, where the reference would stop on an assertion); with an EMA the rank-0 files
+        model_ema.pt / model_ema_best.pt follow it (EMAStats.save_ema_ckp); (4) one line on `pipeline.log_lines`; (5) on rank 0 the
+        prediction triplets as epoch_<k>/{train,valid,test}_results.csv when `save_pred`; (6) `ft_infer_hidden_states` on the test loader
+        and `dump_infer_results`.  With `infer_only` steps 2 to 6 are `dump_results` into `infer_writer`.  Checkpoints of earlier epochs
+        are kept (the reference deletes epoch k - 5)."""
+        from . import inference as INF
+        from . import metrics as M
+        engine, model, out_dir = pipeline.engine, pipeline.model, pipeline.output_dir
+        if not out_dir:
+            raise ValueError("FinetuneMode: the epoch's end writes files; the pipeline needs an output_dir")
+        ep_dir = os.path.join(out_dir, f"epoch_{epoch}")
+        if not self.eval_only:
+            engine.consolidate()            # (a collective of every rank)
+            if pipeline.rank == 0:
+                engine.save_checkpoint(out_dir, tag=f"epoch_{epoch}")
+        if self.infer_only:
+            n = INF.dump_results(model, self.test_loader, pipeline.device, self.infer_writer, pipeline.rank, epoch=epoch)
+            model.train()
+            self.epoch_results.append({"epoch": epoch, "records": n})
+            return
+        e = model._engine
+        use_ema = not self.eval_only and e is not None and e.ema is not None and e.ema_live
+        kw = self.eval_kwargs
+        tr_loss, _, tr_res, tr_triplet = (ft_evaluate(model, self.train_loader_for_eval, eval_name="train", **kw)
+                                          if self.train_loader_for_eval is not None else (0, None, None, None))
+        val_loss, val_metrics, val_res, val_triplet = ft_evaluate(model, self.valid_loader, eval_name="valid", **kw)
+        val_res_ema = None
+        with (engine.ema_weights() if use_ema else contextlib.nullcontext()):
+            if use_ema:
+                _, _, val_res_ema, _ = ft_evaluate(model, self.valid_loader, eval_name="valid", **kw)
+            test_loss, test_metrics, test_res, test_triplet = ft_evaluate(model, self.test_loader, eval_name="test", **kw)
+            idx, logits, hidden = INF.ft_infer_hidden_states(model, self.test_loader, None, "test", save_hidden_states=self.save_hidden_states)
+        model.train()
+        ranked = val_res_ema if use_ema else val_res
+        is_best = False
+        if isinstance(ranked, dict) and (len(ranked) == 1 or sum(k.lower().startswith("ema") for k in ranked) == 1):
+            is_best, self.best_res = (True, ranked) if self.best_res is None else M.compare_metrics_res(ranked, self.best_res)
+            if is_best:
+                self.best_epoch = epoch
+        pipeline.log(f"[epoch {epoch}][global {engine.global_steps}] train_loss: {tr_loss}, valid_loss: {val_loss}, test_loss: {test_loss}, "
+                     f"train: {tr_res}, valid: {val_res}, EMA valid: {val_res_ema}, test: {test_res}")
+        tup = lambda m: ",".join(str(v) for v in m.results_in_tuple())      # noqa: E731
+        pipeline.log_lines.append(f"{epoch},{engine.global_steps},{float(tr_loss)},{float(val_loss)},{float(test_loss)},{tup(val_metrics)},"
+                                  f"{_format_eval_res(val_res)},{tup(test_metrics)},{_format_eval_res(test_res)}\n")
+        files = []
+        if pipeline.rank == 0:
+            os.makedirs(ep_dir, exist_ok=True)
+            if self.save_pred:
+                for name, triplet in (("train", tr_triplet), ("valid", val_triplet), ("test", test_triplet)):
+                    if triplet:
+                        files.append(INF.save_pred_results(triplet, ep_dir, name))
+            if use_ema:
+                engine.save_ema_checkpoint(out_dir, best=bool(is_best))
+        files += INF.dump_infer_results(out_dir, epoch, idx=idx, logits=logits, hidden_states=hidden)
+        self.epoch_results.append({"epoch": epoch, "train_loss": float(tr_loss), "valid_loss": float(val_loss), "test_loss": float(test_loss),
+                                   "train": tr_res, "valid": val_res, "valid_ema": val_res_ema, "test": test_res, "is_best": bool(is_best),
+                                   "files": files, "idx": idx, "logits": logits, "hidden_states": hidden})
+
+    def run_training(self, pipeline):
+        if not self.eval_only:
+            return super().run_training(pipeline)
+        # eval_only (finetune_mode.py:419-431): no step; every epoch_<k> under the checkpoint path is loaded by name and evaluated
+        from . import checkpoint as CK
+        root = pipeline.pretrain_cpt or pipeline.output_dir
+        if not root or not os.path.isdir(root):
+            raise ValueError(f"FinetuneMode(eval_only=True): no checkpoint directory at {root!r}")
+        for epoch in CK._scan_ckps(root):
+            ckp = os.path.join(root, f"epoch_{epoch}")
+            if not os.path.isdir(ckp) or (epoch + 1) % int(self.epoch_per_eval):
+                continue
+            CK.load_from_ckp_with_try(pipeline.model, ckp, skip_keys=False)
+            self.end_of_epoch(pipeline, epoch)
+        pipeline.model.check_deferred()
 
     def prepare_data(self, pipeline):
         """reference finetune_mode.py:181-192: epoch budget -> steps, set_ft_model_config (modules_utils.py:84-92), nested -> flat."""
@@ -1212,9 +1389,9 @@ class TrainingPipeline:
             self.engine.load_checkpoint(self.resume_from)
         self.mode.setup_training(self)
         self.mode.run_training(self)
-        if self.output_dir and getattr(self, "engine", None) is not None:
+        if self.output_dir and self.mode.allow_save_config() and getattr(self, "engine", None) is not None:
             self.engine.consolidate()
-        if self.output_dir and self.rank == 0:
+        if self.output_dir and self.rank == 0 and self.mode.allow_save_config():
             self.engine.save_checkpoint(self.output_dir)
         return self
 

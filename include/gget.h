@@ -1009,6 +1009,43 @@ int gget_op_link_mrr(const float* scores, const int64_t* labels, const int64_t* 
 int gget_op_cluster_metrics(const void* pred_or_logits, int is_logits, const int64_t* labels, const int64_t* raw_node_idx, int B, int S,
                             int C, int64_t* y_pred, int32_t* counts, int64_t* totals, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Prediction passes (csrc/infer.hip; the Python surface is graph-gpt_amd/inference.py).
+ *
+ * gget_op_infer_append
+ * replaces: the per-batch collection of ft_infer_hidden_states (src/utils/log_eval_dump_utils.py:63-67: idx.view((-1, 1)),
+ * res.task_logits.half(), res.task_hidden_states.half() appended to Python lists) and the vstack at its end (:68-73).
+ * One launch appends a batch to three device arenas at row `row0` (the host knows it: B is a shape):
+ *   logits   f32 [B][C]            -> out_logits fp16 [capacity][C], rows row0 .. row0 + B - 1
+ *   hidden   bf16 [B][d] or NULL   -> out_hidden fp16 [capacity][d] (NULL exactly when hidden is), same rows
+ *   idx      i64 [B]               -> out_idx    i64  [capacity], copied as is
+ * f32 -> fp16 rounds to nearest even, as tensor.half() does: overflow to +-inf, fp16 subnormals produced, NaN stays NaN; bf16 -> fp16
+ * widens to f32 (exact) and rounds once.  Nothing outside the B rows is written.  C >= 1, B >= 1, d % 64 == 0 (d = 0 without hidden
+ * states); hidden / out_hidden 16-byte aligned.  row0 + B > capacity, a null pointer, an empty or an unsupported shape: error 2, no
+ * launch.
+ *
+ * gget_op_node_records
+ * replaces: the record building of process_data (src/utils/misc_utils.py:436-468: torch.argmax, torch.where(raw_node_idx != -100)
+ * [0].unique(), three gathers, two .cpu() copies and a np.tile per batch).
+ *   logits        f32 [B][S][C] or NULL   prediction = arg-max over C with torch's rule (the first maximal class; a NaN is maximal)
+ *   pred          i64 [B][S]    or NULL   the predictions themselves; exactly one of logits / pred is given
+ *   raw_node_idx  i64 [B][S]              -100 at every position that is not a node's one counted occurrence
+ *   idx           i64 [B]                 the samples' indices
+ *   records       i64 [cap][3]            every flat position p with raw_node_idx[p] != -100 becomes (idx[p / S], raw_node_idx[p], pred[p]),
+ *                                         in ascending p, appended at the device cursor state[0]
+ *   state         i64 [2]                 [0] the cursor, advanced by the records written; [1] += the records that did not fit in cap
+ *                                         (they are not written).  The caller zeroes both once per pass.
+ * Two launches on `stream` (nodes per chunk of 1024 positions; then a chunk's first record sits at cursor + the nodes of the chunks
+ * before it, with a ballot rank inside the chunk): no atomic decides a record's place, so two calls on the same input give identical
+ * bytes.  Scratch (4 KiB per device and stream) is the library's own.  B, S >= 1, B * S <= GGET_NODE_RECORDS_MAX_POS, C >= 1 with logits;
+ * anything else is error 2 without a launch.
+ * ------------------------------------------------------------------------------------------ */
+#define GGET_NODE_RECORDS_MAX_POS (1 << 20)
+int gget_op_infer_append(const float* logits, const void* hidden, const int64_t* idx, void* out_logits, void* out_hidden, int64_t* out_idx,
+                         int64_t row0, int64_t capacity, int B, int C, int d, void* stream);
+int gget_op_node_records(const float* logits, const int64_t* pred, const int64_t* raw_node_idx, const int64_t* idx, int64_t* records,
+                         int64_t* state, int64_t cap, int B, int S, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
