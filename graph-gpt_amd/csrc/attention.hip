@@ -789,7 +789,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 3 : 2) attn_bwd_dkv_kernel(
       if (tid < 32) {
         const int q = min(q0 + tid, S - 1);
         p_lse = lse[((size_t)b * H + h) * S + q];
-        p_dl = delta[((size_t)b * H + h) * S + q];
+        // (var-len layout: the dQ kernel writes delta for the sample's own rows only; behind them the workspace holds whatever it held,
+        //  and p = 0 times a NaN there is a NaN in dK of every key of the sample)
+        p_dl = q0 + tid < SL ? delta[((size_t)b * H + h) * S + q] : 0.f;
         if (packed) {
           const bool v = q0 + tid < SL;
           p_lo = v ? KR.lo[(size_t)b * S + q] : 0;
@@ -814,7 +816,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 3 : 2) attn_bwd_dkv_kernel(
         if (tid < 32) {
           const int q = min(q0 + tid, S - 1);
           lse_s[tid] = -lse[((size_t)b * H + h) * S + q] * kLog2e;
-          dl_s[tid] = -delta[((size_t)b * H + h) * S + q];
+          dl_s[tid] = q0 + tid < SL ? -delta[((size_t)b * H + h) * S + q] : 0.f;     // (rows behind the sample: see fetch_q)
           if (packed) {
             const bool v = q0 + tid < SL;
             qlo_s[tid] = v ? KR.lo[(size_t)b * S + q] : 0;
@@ -2712,7 +2714,8 @@ __global__ void __launch_bounds__(NWB * 64, 2) attn_bwd_dkv64_kernel(const bf16_
     if (tid < STG) {
       const int q = min(r0 + tid, S - 1);
       p_lse = lse[((size_t)b * H + h) * S + q];          // raw: the scaling waits for commit_vec (no wait for the load here)
-      p_dl = delta[((size_t)b * H + h) * S + q];
+      // (var-len layout: delta is written for the sample's own rows only - p = 0 times a stale NaN behind them is a NaN in dK)
+      p_dl = r0 + tid < SL ? delta[((size_t)b * H + h) * S + q] : 0.f;
       if (PK) {
         const bool v = r0 + tid < SL;
         p_lo = v ? KR.lo[(size_t)b * S + q] : 0;

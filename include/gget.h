@@ -642,7 +642,26 @@ int gget_op_rope(void* qkv, const float* cos_tab, const float* sin_tab, const in
 /* cos_tab/sin_tab ([max_pos][32] fp32, hf LlamaRotaryEmbedding tables) non-NULL: RoPE (hf apply_rotary_pos_emb
  * :138-160) is applied to q,k inside the kernels and undone on dq,dk; qkv / dqkv are the UN-rotated projections.
  * dropout_p > 0: attention dropout on the softmax output (hf eager_attention_forward :210), counter-based mask
- * keyed by (dropout_seed, batch*head, query, key) - see drop_mul() in csrc/attention.hip. */
+ * keyed by (dropout_seed, batch*head, query, key) - see drop_mul() in csrc/attention.hip.
+ *
+ * Numerical contract of gget_op_attn_fwd / _bwd and their _varlen, _ranges and _fused forms (what the per-element bounds of
+ * tests/_attn_out_ref.py count; head_dim 64, scores x = q k / 8):
+ *  - forward: scores, the running maximum, the row sum l and the O accumulator are fp32.  l sums the UNROUNDED, un-dropped p.  P (after the
+ *    keep multiplier m = 0 or 1 / (1 - p); the long-sequence kernels drop in P and apply 1 / (1 - p) with 1 / l at the end) is rounded to
+ *    bf16 once, as the operand of the P V MFMA.  out = bf16(O / l): one rounding.  lse = fp32 natural log of sum_allowed exp(x), before
+ *    dropout; 0 for a query without an allowed key, whose out row is 0.  A query with ONE allowed key and no dropout returns that v row
+ *    bit for bit.  With RoPE on load the rotated q / k are rounded to bf16 before the score MFMA.
+ *  - backward: p = exp(x - lse) is recomputed in fp32 from the lse handed in.  dP = dO V^T is fp32.  delta is the softmax-backward row
+ *    term: rowsum(dO * out) in fp32 from the bf16 out handed in - in the dQ kernels of the two-kernel forms, which leave it in delta_ws
+ *    for the dK / dV kernel, and in the first launch of the fused form - or, where one launch holds a whole row (one key length per row and S <= 32, or
+ *    S <= 64 without RoPE on load: these do not read out or delta_ws), sum_k m p dP from registers.  dS = p (m dP - delta) / 8 is rounded to bf16
+ *    once, as the operand of both dQ = dS K and dK = dS^T Q; P (times m) is rounded to bf16 once, as the operand of dV = P^T dO; the
+ *    accumulators are fp32 and dq, dk, dv are rounded to bf16 once.  The fused form (S >= 256) rounds the dQ partial of every block of 256
+ *    keys to bf16 (its slab of dq_ws) and sums the slabs in fp32.  dq / dk are rotated back in fp32 before their rounding.
+ *  - delta_ws, dq_ws: workspaces, contents irrelevant on entry; rows of delta_ws behind a sample's tokens are not read.
+ *  - pad rows of dqkv.  Padded grid and packed rows: EVERY row is written; the rows without a token (behind key_len[b]; empty key range)
+ *    are exact zeros provided dout is zero there and out / lse are the forward's - the q | k | v weight-gradient GEMM sums over all rows.
+ *    Var-len layout: only the samples' rows are written; rows behind the last sample are the caller's (the engine zeroes them once). */
 int gget_op_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, int B, int S, int H,
                      int causal, const float* cos_tab, const float* sin_tab, const int64_t* position_ids,
                      float dropout_p, uint32_t dropout_seed, void* stream);

@@ -94,11 +94,21 @@ def attn_probs64(q, k, allowed, keep=None):
     return dict(ref=ref, p=p, x=x, A=A, lse=lse, W=(p * A).sum(-1), X=(p * x.abs()).sum(-1), allowed=ok)
 
 
+def attn_sum_const(S):
+    """The "(S + const)" of the sum and the log of the online softmax, in units of u (module docstring)."""
+    return S + 4 * math.ceil(S / 32) + 3 * math.log(S) + 1
+
+
+def attn_exp_err(r, S):
+    """E of the module docstring: the absolute error of the exponent x - lse, [B,H,S,S]."""
+    lse, x = r["lse"][..., None], r["x"]
+    const = attn_sum_const(S) + 3
+    return U * (16 * r["A"] + 16 * r["W"][..., None] + const + r["X"][..., None] + 5 * lse.abs() + x.abs() + (x - lse).abs())
+
+
 def attn_bound(r, S, m_max=1.0):
     """The per-element bound of the module docstring from attn_probs64's result."""
-    lse, x = r["lse"][..., None], r["x"]
-    const = S + 4 * math.ceil(S / 32) + 3 * math.log(S) + 1 + 3
-    E = U * (16 * r["A"] + 16 * r["W"][..., None] + const + r["X"][..., None] + 5 * lse.abs() + x.abs() + (x - lse).abs())
+    E = attn_exp_err(r, S)
     ref = r["ref"]
     return (2.0 ** -8 * ref + 1.01 * ref * torch.expm1(E) + TINY * max(1.0, m_max)).masked_fill(~r["allowed"], 0.0)
 
