@@ -2862,6 +2862,21 @@ extern "C" int gget_op_attn_oproj_bwd(const void* dxn, const void* x_mid, const 
   *taken = t;
   return rc;
 }
+extern "C" int gget_op_attn_oproj_bwd_list(const void* dxn, const void* x_mid, const void* norm_w, const float* rstd, const void* dres,
+                                           void* dx_mid, float* dw_accum, int copies, uint64_t copy_stride, const void* wot_packed,
+                                           const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, void* dqkv, int B,
+                                           int S, int H, int causal, const float* cos_tab, const float* sin_tab, const int64_t* position_ids,
+                                           float dropout_p, uint32_t dropout_seed, int t_rows, void* stream, int32_t* taken, void* dattn_long,
+                                           const int32_t* long_list) {
+  GGET_REQUIRE(dxn && x_mid && norm_w && rstd && dres && dx_mid && dw_accum && wot_packed && qkv && lse && dqkv && taken, "null argument");
+  GGET_REQUIRE(!long_list || row_base, "attn_oproj_bwd_list: the list of long samples belongs to the var-len layout");
+  int t = 0;
+  const int rc = k_attn_oproj_bwd(dxn, x_mid, norm_w, rstd, dres, dx_mid, dw_accum, copies, copy_stride, wot_packed, qkv, lse, key_len, row_base,
+                                  dqkv, B, S, H, causal, cos_tab, sin_tab, position_ids, dropout_p, dropout_seed, t_rows, (hipStream_t)stream, &t,
+                                  dattn_long, long_list);
+  *taken = t;
+  return rc;
+}
 extern "C" int gget_op_attn_fwd_ranges(const void* qkv, const int32_t* key_lo, const int32_t* key_hi, void* out, float* lse, int B,
                                        int S, int H, int causal, float dropout_p, uint32_t dropout_seed, void* stream) {
   GGET_REQUIRE(key_lo && key_hi, "attn_fwd_ranges: null ranges");
@@ -2910,6 +2925,14 @@ extern "C" int gget_op_attn_bwd_varlen(const void* qkv, const void* out, const v
   GGET_REQUIRE(qkv && dout && key_len && row_base && dqkv, "attn_bwd_varlen: null argument");
   return k_attn_bwd(qkv, out, dout, lse, key_len, dqkv, delta_ws, B, S, H, causal, cos_tab, sin_tab, position_ids, qk_rotated, dropout_p,
                     dropout_seed, (hipStream_t)stream, nullptr, nullptr, row_base);
+}
+extern "C" int gget_op_attn_bwd_varlen_list(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len,
+                                            const int32_t* row_base, void* dqkv, float* delta_ws, int B, int S, int H, int causal,
+                                            const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int qk_rotated,
+                                            float dropout_p, uint32_t dropout_seed, void* stream, const int32_t* long_list) {
+  GGET_REQUIRE(qkv && dout && key_len && row_base && dqkv, "attn_bwd_varlen_list: null argument");
+  return k_attn_bwd(qkv, out, dout, lse, key_len, dqkv, delta_ws, B, S, H, causal, cos_tab, sin_tab, position_ids, qk_rotated, dropout_p,
+                    dropout_seed, (hipStream_t)stream, nullptr, nullptr, row_base, nullptr, 0, long_list);
 }
 extern "C" int gget_op_attn_bwd_fused(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len,
                                       const int32_t* key_lo, const int32_t* key_hi, void* dqkv, float* delta_ws, void* dq_ws, int B, int S,

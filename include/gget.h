@@ -721,6 +721,19 @@ int gget_op_attn_oproj_bwd(const void* dxn, const void* x_mid, const void* norm_
                            const int32_t* key_len, const int32_t* row_base, void* dqkv, int B, int S, int H, int causal, const float* cos_tab,
                            const float* sin_tab, const int64_t* position_ids, float dropout_p, uint32_t dropout_seed, int t_rows,
                            void* stream, int32_t* taken, void* dattn_long);
+/* gget_op_attn_bwd_varlen and gget_op_attn_oproj_bwd in the engine's launch form for 32 < S <= 64: long_list (int32 [3 B + 1], may be NULL)
+ * is what gget_op_varlen_plan wrote - [0] the number n of 33 .. 64-row samples, [1 ..] their indices, [1 + B ..] their first rows,
+ * [1 + 2 B ..] their row counts.  attn_bwd_long_kernel then runs at most 32 block slots per head that walk the list with the grid's stride
+ * instead of one block per sample.  NULL: exactly the entries above.  Same results, bit for bit. */
+int gget_op_attn_bwd_varlen_list(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len,
+                                 const int32_t* row_base, void* dqkv, float* delta_ws, int B, int S, int H, int causal, const float* cos_tab,
+                                 const float* sin_tab, const int64_t* position_ids, int qk_rotated, float dropout_p, uint32_t dropout_seed,
+                                 void* stream, const int32_t* long_list);
+int gget_op_attn_oproj_bwd_list(const void* dxn, const void* x_mid, const void* norm_w, const float* rstd, const void* dres, void* dx_mid,
+                                float* dw_accum, int copies, uint64_t copy_stride, const void* wot_packed, const void* qkv, const float* lse,
+                                const int32_t* key_len, const int32_t* row_base, void* dqkv, int B, int S, int H, int causal,
+                                const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
+                                uint32_t dropout_seed, int t_rows, void* stream, int32_t* taken, void* dattn_long, const int32_t* long_list);
 /* attention with a per-token inclusive key range [key_lo, key_hi] (int32 [B,S]; packed rows) instead of one length per
  * batch row; gget_op_ranges_from_mask3d derives the ranges from a block-diagonal int64 [B,S,S] mask. */
 int gget_op_attn_fwd_ranges(const void* qkv, const int32_t* key_lo, const int32_t* key_hi, void* out, float* lse, int B, int S,

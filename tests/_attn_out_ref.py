@@ -52,6 +52,11 @@ on the 32-row shape, and the kernels reach 0.88 of the bounds here.)
       dK :  the same with Q for K and the transposed dS.
       dq / dk rotated back (unrope_acc :333, attn_dq_finish_kernel :2920): the bound before the output rounding goes through the rotation,
             |c| b_lo + |s| b_up, plus 4 u (|lo c| + |up s|) for the fp32 rotation; the output rounding comes last.
+      e_dO: where the entry under test forms dO itself (attn_oproj_bwd_kernel rounds its fp32 dattn = dx_mid Wo to bf16, :1898-1903, and
+            dattn never reaches memory) the statement forms dO = bf16(float64 product) and round_flips marks the elements whose exact
+            value lies within the fp32 accumulation error of a rounding boundary: each may differ by one bf16 spacing, e_dO.  It
+            propagates linearly: err dP += e_dO |V|^T, the dV bound += 1.01 (m p)^T e_dO, err delta from out += sum_j e_dO_j |out_j|;
+            delta from P and dS carry it through err dP.  Zero (the default) where dO is an input.
 Where kernel classes differ in a count the larger is used (32-key stages; 5 u |lse| inside E for the forward, which has no conversion).
 Nothing here is fitted to the kernel: every constant is a count of roundings of the contract above.
 
@@ -188,16 +193,20 @@ def delta_from_out(S, packed, rope):
     return not ((S <= 32 or (S <= 64 and rope != "load")) and not packed)
 
 
-def _rotate_round(t, c, s):
-    """bf16(rotation of t) from float64, and per element how far the kernel's value may lie from it: 0, or - where the exact value is
-    within the fp32 rotation's error 4 u (|a c| + |b s|) (two products, one sum) of a rounding boundary - one bf16 spacing."""
-    r = rotate(t, c, s)
+def round_flips(r, eps):
+    """bf16(r) of the float64 r, and per element how far a kernel's bf16 value may lie from it when the kernel rounds an fp32 value within
+    eps of r: 0, or - where r is within eps of a rounding boundary - one bf16 spacing."""
     rb = r.float().to(torch.bfloat16).double()
-    eps = 4 * U * rotate_abs(t.abs(), c, s)
     sp = torch.exp2(torch.floor(torch.log2(rb.abs().clamp_min(TINY))) - 7)
     dist = (r - rb).abs()
     near = torch.minimum((dist - sp / 2).abs(), (dist - sp / 4).abs()) <= eps         # (sp / 4: the boundary below a power of two)
     return rb, torch.where(near, sp, torch.zeros_like(sp))
+
+
+def _rotate_round(t, c, s):
+    """bf16(rotation of t) from float64, and per element how far the kernel's value may lie from it: 0, or - where the exact value is
+    within the fp32 rotation's error 4 u (|a c| + |b s|) (two products, one sum) of a rounding boundary - one bf16 spacing."""
+    return round_flips(rotate(t, c, s), 4 * U * rotate_abs(t.abs(), c, s))
 
 
 def operands64(pr, flips=False):
@@ -264,9 +273,10 @@ def forward_check(pr, out, lse, f=None, zero_rows=False):
 
 
 # ------------------------------------------------------------------------------------------------------------------ backward
-def backward64(pr, lse, out, from_out, slabs=0):
+def backward64(pr, lse, out, from_out, slabs=0, dO=None, e_dO=None):
     """Float64 statement and bounds of dq, dk, dv [B,H,S,64] from the handed lse (fp32 [B,H,S]) and out (bf16 [B*S, d]).  from_out: delta =
-    rowsum(dO o out), else sum_k p m dP.  slabs > 0: the fused form's per-slab bf16 rounding of dQ."""
+    rowsum(dO o out), else sum_k p m dP.  slabs > 0: the fused form's per-slab bf16 rounding of dQ.  dO ([B*S, d], any float type): the
+    output gradient in place of pr.dout; e_dO [B,H,S,64]: how far the kernel's own dO may lie from it (module docstring)."""
     B, S, Hn = pr.B, pr.S, pr.Hn
     q, k, v, fq, fk = operands64(pr, flips=True)
     ok = pr.allowed[:, None].expand(B, Hn, S, S)
@@ -276,17 +286,21 @@ def backward64(pr, lse, out, from_out, slabs=0):
     p = torch.exp((x - lse).masked_fill(~ok, float("-inf")))
     m = pr.keep.double() if pr.keep is not None else torch.ones_like(p)
     pm = p * m
-    dO = heads(pr.dout, B, S, Hn).double()
+    dO = heads(pr.dout if dO is None else dO, B, S, Hn).double()
     Eb = U * (16 * A + 2 * lse.abs() + x.abs() + (x - lse).abs() + 3)
     if pr.rope == "load":
         Eb = Eb + flip_scores(q, k, fq, fk)
     eE = torch.expm1(Eb).masked_fill(~ok, 0.0)
     dP = dO @ v.transpose(2, 3)
     e_dP = 128 * U * (dO.abs() @ v.abs().transpose(2, 3))
+    if e_dO is not None:
+        e_dP = e_dP + e_dO @ v.abs().transpose(2, 3)
     if from_out:
         o = heads(out, B, S, Hn).double()
         delta = (dO * o).sum(-1, keepdim=True)
         e_dl = 128 * U * (dO * o).abs().sum(-1, keepdim=True)
+        if e_dO is not None:
+            e_dl = e_dl + (e_dO * o.abs()).sum(-1, keepdim=True)
     else:
         delta = (pm * dP).sum(-1, keepdim=True)
         e_dl = (pm * e_dP + eE * pm * dP.abs() + 2 * S * U * pm * dP.abs()).sum(-1, keepdim=True)
@@ -298,6 +312,8 @@ def backward64(pr, lse, out, from_out, slabs=0):
     inner = dict(dv=(1.01 * (BF + eE + 2 * U) * pm + acc * pm).transpose(2, 3) @ dO.abs(),
                  dq=e_dS @ k.abs() / 8 + acc * aq + dS.abs() @ fk / 8,
                  dk=e_dS.transpose(2, 3) @ q.abs() / 8 + acc * ak + dS.abs().transpose(2, 3) @ fq / 8)
+    if e_dO is not None:
+        inner["dv"] = inner["dv"] + 1.01 * pm.transpose(2, 3) @ e_dO
     if slabs:      # every 256-key partial of dQ is rounded to bf16: 2^-8 of the partial (its own error included), then summed in fp32
         part = sum((dS[..., 256 * i:256 * (i + 1)] @ k[:, :, 256 * i:256 * (i + 1)] / 8).abs() for i in range(slabs))
         inner["dq"] = inner["dq"] + 1.01 * BF * (part + inner["dq"]) + slabs * U * aq
@@ -402,8 +418,9 @@ def forward_fp32(pr, fault=None):
     return rows2d(o).to(torch.bfloat16), lse.masked_fill(~pr.real_h, 0.0)
 
 
-def backward_fp32(pr, lse, out, from_out, slabs=0, fault=None):
-    """The same of the backward (P o m and dS to bf16, outputs to bf16, per-slab dQ to bf16 for the fused form): dqkv bf16 [B*S, 3 d]."""
+def backward_fp32(pr, lse, out, from_out, slabs=0, fault=None, dO=None):
+    """The same of the backward (P o m and dS to bf16, outputs to bf16, per-slab dQ to bf16 for the fused form): dqkv bf16 [B*S, 3 d].
+    dO ([B*S, d]): the output gradient in place of pr.dout."""
     B, S, Hn = pr.B, pr.S, pr.Hn
     q, k, v = _operands32(pr)
     ok = pr.allowed[:, None].expand(B, Hn, S, S)
@@ -412,7 +429,7 @@ def backward_fp32(pr, lse, out, from_out, slabs=0, fault=None):
     p = torch.exp((x - lse).masked_fill(~ok, float("-inf")))
     m = pr.keep if pr.keep is not None else torch.ones_like(p)
     pm = p * m
-    dO = heads(pr.dout, B, S, Hn).float()
+    dO = heads(pr.dout if dO is None else dO, B, S, Hn).float()
     dP = dO @ v.transpose(2, 3)
     if fault == "delta_before_dropout":
         delta = (p * dP).sum(-1, keepdim=True)

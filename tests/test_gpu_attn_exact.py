@@ -18,7 +18,9 @@ p in {0, 0.1} without the full product) and the kernels they reach:
           gget_op_attn_fwd_varlen          S 40 (40, 33, 1) | 64 (64, 32, 31) | 64 (47, 1, 33)     attn_fwd_rows64_kernel
                                            S 24 | 72 | 160 | 320 | 520                             the kernels above through row_base
           gget_op_attn_fwd_ranges          S 40 | 64 | 160 | 320                                   PK = true of attn_fwd_kernel<1 / 2 / 4>, attn_fwd64_kernel
-          gget_op_attn_oproj_fwd           S <= 32, H 2 | 4 | 8 | 12 (attn_out and lse only)       attn_oproj_fwd_kernel<H> (*taken asserted)
+          gget_op_attn_oproj_fwd           S <= 32, H 2 | 4 | 8 | 12 (attn_out and lse here; x_mid,  attn_oproj_fwd_kernel<H> (*taken asserted)
+                                           xn, rstd and the fused backward gget_op_attn_oproj_bwd:
+                                           tests/test_gpu_layer_exact.py)
  backward, gget_op_attn_bwd                S 8 | 32                                                attn_bwd_small_kernel
                                            S 40 | 64                                               attn_bwd_long_kernel
                                            S 40 | 160 with RoPE on load                            attn_bwd_dq_kernel / attn_bwd_dkv_kernel <1> | <4>
