@@ -4,4 +4,4 @@ Import with ``importlib.import_module("graph-gpt_amd")`` (the directory name is 
 contract and is not a Python identifier) or through the drop-in surface ``src.models`` /
 ``src.training`` at the repo root.
 """
-from .spec import ModelSpec, spec_from_size, KIND_PRETRAIN, KIND_TASK, MODEL_SIZES  # noqa: F401
+from .spec import ModelSpec, spec_from_size, KIND_PRETRAIN, KIND_PRETRAIN_CL, KIND_TASK, MODEL_SIZES  # noqa: F401

@@ -192,7 +192,16 @@ SIGNATURES = {
     "gget_op_cluster_metrics": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "gget_op_infer_append": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]),
     "gget_op_node_records": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "gget_op_cl_embed_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "gget_op_cl_loss_fwd": (i32, [vp, i32, i32, f32, vp, vp, vp]),
+    "gget_op_cl_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp]),
+    "gget_cl_logits": (i32, [vp, C.POINTER(vp)]),
+    "gget_cl_embeddings": (i32, [vp, C.POINTER(vp)]),
+    "gget_cl_loss": (i32, [vp, vp, vp]),
+    "gget_cl_set_gathered": (i32, [vp, vp, i32, vp, vp]),
+    "gget_cl_set_backward_scales": (i32, [vp, f32, f32]),
 }
+CL_MAX_N, CL_MAX_D = 2048, 1024   # include/gget.h "Contrastive pre-training head": 2 <= N <= 2048 (even), d % 64 == 0, d <= 1024
 NODE_RECORDS_MAX_POS = 1 << 20   # include/gget.h GGET_NODE_RECORDS_MAX_POS: positions (B * S) one gget_op_node_records call takes
 CLUSTER_MAX_C = 2048  # include/gget.h GGET_CLUSTER_MAX_C: the classes the LDS tables of gget_op_cluster_metrics hold
 

@@ -118,6 +118,28 @@ def _set(obj, name, value):
         setattr(obj, name, value)
 
 
+def sync_config(cfg) -> None:
+    """base_configs.py:246-247 - the rule of the reference's sync_config that reaches the hot path: `task_type == "pretrain-cl"`
+    switches the contrastive head on (`pt_head.use_discriminative`; the model class then builds the contrastive engine kind).  Its
+    other two lines (ft_head.task_type, the max_length default) feed the tokenizer / dataset half, which stays on the host side."""
+    model_cfg, train_cfg = _get(cfg, "model"), _get(cfg, "training")
+    if model_cfg is None or train_cfg is None:
+        return
+    if _get(train_cfg, "task_type") == "pretrain-cl":
+        pt_head = _get(model_cfg, "pt_head")
+        if pt_head is not None:
+            _set(pt_head, "use_discriminative", True)
+        else:
+            _set(model_cfg, "use_discriminative", True)       # (a flat GraphGPTConfig keyword dict)
+
+
+def eval_loader_drop_last(train_cfg) -> bool:
+    """src/utils/loader_utils.py:658 - the evaluation loader of a pretrain-cl run drops its last, possibly odd-sized batch (the
+    contrastive loss pairs samples 2m and 2m + 1), except when it only infers.  The loaders themselves stay on the host side; this is
+    the `drop_last` to build them with."""
+    return _get(train_cfg, "task_type") == "pretrain-cl" and not _get(train_cfg, "do_infer", False)
+
+
 def update_num_steps(sched_cfg, tokens_per_sample, batch_size, world_size) -> None:
     """base_configs.py:52-58 - optimizer steps of a token-budgeted run, rounded UP; the global batch is world * batch_size."""
     per_step = tokens_per_sample * batch_size * world_size

@@ -61,6 +61,10 @@ struct ParamRec {
   uint64_t off32;   // element offset in the fp32 scratch
 };
 
+// the contrastive kind is the pre-train model with one more head: whatever is said of the pre-train kind holds for it
+inline bool is_pretrain(const gget_config_t& c) { return c.kind == GGET_KIND_PRETRAIN || c.kind == GGET_KIND_PRETRAIN_CL; }
+inline bool has_cl(const gget_config_t& c) { return c.kind == GGET_KIND_PRETRAIN_CL; }
+
 struct LayerOff {
   uint64_t ln1, wqkv, wo, lam1, ln2, wgu, wdown, lam2;
   uint64_t ln1_32, lam1_32, ln2_32, lam2_32;
@@ -74,6 +78,7 @@ struct Plan {
   std::vector<LayerOff> layers;
   uint64_t emb = 0, emb32 = 0, gate = 0, gate32 = 0, normf = 0, normf32 = 0;
   uint64_t raw_ln = 0, raw_ln32 = 0, raw_tok = 0, raw_tok32 = 0, raw_proj = 0;   // raw-embedding inputs (embed_dim > 0)
+  uint64_t cl = 0, cl32 = 0;   // cl_proj.weight (contrastive kind) and its fp32 accumulator
   uint64_t ntp = 0, lm = 0, lm32 = 0, score = 0, score32 = 0, sbias = 0, sbias32 = 0;
   bool has_gate = false, has_ntp = false, has_ls = false;
   // MLP score head (config.head_mlp_layers > 0): n_lin = layers + 1 Linears of widths head_dim[0] = d, ..., head_dim[n_lin] = num_labels
@@ -112,12 +117,12 @@ Plan make_plan(const gget_config_t& c) {
   pl.has_gate = c.gated_agg != 0;
   pl.has_ls = c.layer_scale_init > 0.f;
   pl.has_res = pl.has_ls || c.path_pdrop > 0.f || c.mlp_pdrop > 0.f;   // (mlp_dropout sits between down_proj and the residual add)
-  pl.has_ntp = c.kind == GGET_KIND_PRETRAIN && c.next_n_token > 1;
+  pl.has_ntp = is_pretrain(c) && c.next_n_token > 1;
   add_param(pl, "model.embed_tokens.weight", V, d, -1, true, &pl.emb, &pl.emb32);
   if (pl.has_gate) add_param(pl, "stacked_feat_agg.weight", F, d, -1, true, &pl.gate, &pl.gate32);
   if (c.embed_dim > 0) {   // modeling_pretrain.py:69-84 / modeling_finetune.py:76-85
     add_param(pl, "embed_layernorm.weight", c.embed_dim, 0, -1, true, &pl.raw_ln, &pl.raw_ln32);
-    if (c.kind == GGET_KIND_PRETRAIN) add_param(pl, "emb_mask_token", c.embed_dim, 0, -1, true, &pl.raw_tok, &pl.raw_tok32);
+    if (is_pretrain(c)) add_param(pl, "emb_mask_token", c.embed_dim, 0, -1, true, &pl.raw_tok, &pl.raw_tok32);
     add_param(pl, "embed_proj.weight", d, c.embed_dim, -1, false, &pl.raw_proj, nullptr);
   }
   pl.layers.resize(L);
@@ -137,7 +142,7 @@ Plan make_plan(const gget_config_t& c) {
     if (pl.has_ls) add_param(pl, p + "lambda_2", d, 0, i, true, &lo.lam2, &lo.lam2_32);
   }
   add_param(pl, "model.norm.weight", d, 0, (int)L, true, &pl.normf, &pl.normf32);
-  if (c.kind == GGET_KIND_PRETRAIN) {
+  if (is_pretrain(c)) {
     if (pl.has_ntp) add_param(pl, "n_token_proj.weight", (int64_t)c.next_n_token * d, d, (int)L, false, &pl.ntp, nullptr);
     add_param(pl, "lm_head.weight", V, d, (int)L, false, &pl.lm, nullptr);
     // zero rows behind lm_head up to round_up(V, 64): its dgrad GEMM then runs over K = Vp without a K tail (the pad
@@ -146,6 +151,8 @@ Plan make_plan(const gget_config_t& c) {
     pl.lm_pad_off = pl.n_params;
     pl.lm_pad_count = (uint64_t)(Vp - V) * d;
     pl.n_params += align_up(pl.lm_pad_count, 128);
+    if (has_cl(c))   // modeling_pretrain.py:106-107: last, as the reference registers it and as ModelSpec.param_table lists it
+      add_param(pl, "cl_proj.weight", d, d, (int)L, true, &pl.cl, &pl.cl32);
   } else {
     if (c.head_mlp_layers > 0) {   // `MLP` head (src/utils/modules_utils.py:8-34): state-dict keys score.mlp_modules.<i>.weight / .bias
       pl.n_lin = c.head_mlp_layers + 1;
@@ -179,6 +186,9 @@ struct LayerWs {
   uint64_t rstd1, xn1, qkv, lse, attn, araw, xmid, rstd2, xn2, gu, h, mraw;
 };
 
+constexpr int kClRowsMax = 2048;   // rows of the contrastive loss problem (contrastive.hip kClMaxN)
+constexpr float kClRatio = 0.5f;   // ratio_dis beside the generative head (modeling_pretrain.py:99-100)
+
 struct Ws {
   uint64_t key_len, pool_row, cos_tab, sin_tab, key_lo, key_hi;
   std::vector<uint64_t> xres;  // L+1 residual-stream snapshots
@@ -194,6 +204,7 @@ struct Ws {
   uint64_t ss_tok, ss_cell, ss_l, ss_pos, ss_tile, ss_state, ss_total;
   // task head
   uint64_t tlogits, tdlogits, pooled_h, auc_lists;
+  uint64_t cl_z = 0, cl_e = 0, cl_dz = 0, cl_rn = 0, cl_stat = 0, cl_loss = 0;   // contrastive head (make_ws)
   uint64_t raw_x, raw_xn, raw_rstd, raw_dxn, raw_dx, raw_flag;   // raw-embedding inputs: blended bf16 [T,e], normalised [T,e], 1/rms [T], their gradients, mask flags [T]
   uint64_t rr_cos, rr_sin, rr_ids;   // rope_range: per-token angle tables [T][32] fp32 and the identity position list [T] int64
   uint64_t tok_stat;   // token-level head: loss sum, labelled rows, 1 / rows
@@ -291,7 +302,15 @@ Ws make_ws(const gget_config_t& c, const Plan& pl) {
   w.emb_sort = b.take(k_embed_bwd_ws_elems(T * (uint64_t)c.stacked_feat, (uint64_t)c.vocab_size) * 4);
   w.emb_cnt = k_embed_dense_ok(c.vocab_size, pl.has_gate) ? b.take(T * align_up(c.vocab_size, 64) * 2) : 0;   // bf16 [T][Vp] count matrix
   w.emb_slab = k_embed_dense_ok(c.vocab_size, pl.has_gate) ? b.take((uint64_t)kEmbDenseSplit * c.vocab_size * d * 4) : 0;
-  if (c.kind == GGET_KIND_PRETRAIN) {
+  if (has_cl(c)) {   // contrastive head: logits, embeddings, 1 / norm and dz of the batch's rows; row statistics of up to kClRowsMax gathered rows
+    w.cl_z = b.take(Bm * d * 4);
+    w.cl_e = b.take(Bm * d * 4);
+    w.cl_dz = b.take(Bm * d * 4);
+    w.cl_rn = b.take(Bm * 4);
+    w.cl_stat = b.take(3 * (uint64_t)kClRowsMax * 4);
+    w.cl_loss = b.take(256);
+  }
+  if (is_pretrain(c)) {
     const uint64_t n = c.next_n_token, Vp = align_up(c.vocab_size, 64);
     w.cnt = b.take(T * 4);
     w.hc_tot = b.take(k_head_compact_ws_bytes((int)T));
@@ -353,10 +372,11 @@ int check_cfg(const gget_config_t* c) {
   GGET_REQUIRE(c->intermediate_size > 0 && c->intermediate_size % 64 == 0, "intermediate_size must be a multiple of 64");
   GGET_REQUIRE(c->hidden_size <= 2048, "hidden_size > 2048 not supported by the norm kernels");
   GGET_REQUIRE(c->vocab_size > 1 && c->num_layers >= 1 && c->stacked_feat >= 1, "bad vocab/layers/stacked_feat");
-  GGET_REQUIRE(c->kind == GGET_KIND_PRETRAIN || c->kind == GGET_KIND_TASK, "bad kind");
+  GGET_REQUIRE(is_pretrain(*c) || c->kind == GGET_KIND_TASK, "bad kind");
   GGET_REQUIRE(c->max_tokens > 0 && c->max_batch > 0 && c->max_position > 0, "bad capacities");
-  if (c->kind == GGET_KIND_PRETRAIN) GGET_REQUIRE(c->next_n_token >= 1, "next_n_token must be >= 1");
+  if (is_pretrain(*c)) GGET_REQUIRE(c->next_n_token >= 1, "next_n_token must be >= 1");
   else GGET_REQUIRE(c->num_labels >= 1, "num_labels must be >= 1");
+  if (has_cl(*c)) GGET_REQUIRE(c->hidden_size <= 1024, "the contrastive head holds hidden_size <= 1024");
   GGET_REQUIRE(c->embed_dim >= 0 && c->embed_dim % 64 == 0 && c->embed_dim <= 2048, "embed_dim must be 0 or a multiple of 64 up to 2048");
   GGET_REQUIRE(c->head_mlp_layers >= 0 && c->head_mlp_layers <= 4, "the MLP score head holds at most 4 hidden layers");
   for (int i = 0; i < c->head_mlp_layers; ++i) GGET_REQUIRE(c->head_mlp[i] > 0, "bad MLP head width");
@@ -524,7 +544,15 @@ struct gget_engine {
   hipEvent_t count_event = nullptr;
   unsigned auc_seed = 0;
   bool fwd_valid = false;
-  float attn_drop_p = 0.f;        // attention dropout of the NEXT forward (training mode); 0 = off
+  // contrastive head (GGET_KIND_PRETRAIN_CL): the embedding matrix the loss of the last forward was taken over - the batch's own rows in
+  // the workspace, or the caller's gathered matrix with the positions of the local rows (gget_cl_set_gathered) - and the upstream scales of
+  // the NEXT backward (gget_cl_set_backward_scales; consumed by gget_backward_begin)
+  const float* cl_E = nullptr;
+  const int32_t* cl_map = nullptr;
+  int cl_N = 0;
+  bool cl_valid = false;
+  float cl_gen_scale = 1.f, cl_scale = 1.f;
+  float attn_drop_p = 0.f;       // attention dropout of the NEXT forward (training mode); 0 = off
   float path_drop_p = 0.f;        // stochastic-depth rate of the last layer (layer l: p*l/(L-1))
   unsigned attn_drop_seed = 0;
   float embed_drop_p = 0.f;       // embed_dropout / mlp dropouts of the NEXT forward (training mode); 0 = off
@@ -1512,9 +1540,9 @@ int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, 
   if (mask_is_3d) {
     GGET_REQUIRE(mask != nullptr && c.kind == GGET_KIND_PRETRAIN, "a 3-D (packed) attention mask needs the pre-train model and a mask");
     if (int e = k_ranges_from_mask3d(mask, h->wsp<int32_t>(h->ws.key_lo), h->wsp<int32_t>(h->ws.key_hi), B, S, st)) return e;
-  } else if (int e = k_lengths(mask, c.kind == GGET_KIND_TASK ? ids : nullptr, ldF, c.pad_token_id,
+  } else if (int e = k_lengths(mask, c.kind != GGET_KIND_PRETRAIN ? ids : nullptr, ldF, c.pad_token_id,
                                h->wsp<int32_t>(h->ws.key_len),
-                               c.kind == GGET_KIND_TASK ? h->wsp<int32_t>(h->ws.pool_row) : nullptr, B, S, st)) {
+                               c.kind != GGET_KIND_PRETRAIN ? h->wsp<int32_t>(h->ws.pool_row) : nullptr, B, S, st)) {
     return e;
   }
   if (allow_varlen && varlen_enabled() && (tc_hint > 0 || tc_hint == GGET_TOKENS_AUTO) && !mask_is_3d && mask != nullptr) {
@@ -1580,7 +1608,7 @@ int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, 
     // (h->pos_cur: the caller's positions, or with rope_range the identity list into the per-token angle tables - a compact row then
     //  reads the table row of its logical token)
     if (int e = k_varlen_plan(ids, ldF, c.stacked_feat, h->pos_cur, h->wsp<int32_t>(w.key_len),
-                              c.kind == GGET_KIND_TASK ? h->wsp<int32_t>(w.pool_row) : nullptr, h->wsp<int32_t>(w.vl_cu),
+                              c.kind != GGET_KIND_PRETRAIN ? h->wsp<int32_t>(w.pool_row) : nullptr, h->wsp<int32_t>(w.vl_cu),
                               h->wsp<int64_t>(w.vl_ids), h->wsp<int64_t>(w.vl_pos), h->wsp<int32_t>(w.vl_rowb), h->wsp<int32_t>(w.vl_pad2c),
                               h->wsp<int32_t>(w.vl_c2p), h->wsp<int32_t>(w.vl_status), B, S, h->tc, h->T, c.pad_token_id, st,
                               h->wsp<int32_t>(w.vl_long)))
@@ -1601,7 +1629,7 @@ int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, 
     GGET_REQUIRE(h->raw_next != nullptr, "this model was built with embed_dim > 0: hand the raw embeddings over with gget_set_raw_embeds");
     const Ws& w = h->ws;
     const int e_ = c.embed_dim;
-    const bool blend = c.kind == GGET_KIND_PRETRAIN && labels != nullptr;
+    const bool blend = is_pretrain(c) && labels != nullptr;
     if (int e = k_raw_blend(h->raw_next, blend ? labels : nullptr, c.next_n_token, h->raw_first_label_only,
                             blend ? h->P + h->plan.raw_tok : nullptr, h->wsp<bf16_t>(w.raw_x), h->wsp<int32_t>(w.raw_flag), h->T, e_, st,
                             h->varlen ? h->wsp<int32_t>(w.vl_c2p) : nullptr, B * S))     // (var-len: raw rows / labels through the logical row)
@@ -1631,7 +1659,10 @@ static int forward_pretrain_impl(gget_handle_t h, const int64_t* input_ids_dev, 
   const long tc_hint = h->tc_next;   // the token count belongs to THIS call whatever happens below (a failing forward must not leave it
   h->tc_next = -1;                   // to the next batch)
   GGET_REQUIRE(input_ids_dev, "null argument");
-  GGET_REQUIRE(h->cfg.kind == GGET_KIND_PRETRAIN, "handle was not created as a pre-train model");
+  GGET_REQUIRE(is_pretrain(h->cfg), "handle was not created as a pre-train model");
+  GGET_REQUIRE(!(has_cl(h->cfg) && mask_is_3d), "the contrastive (pretrain-cl) model takes no packed [B,S,S] mask: the reference masks on the host and never packs");
+  GGET_REQUIRE(!has_cl(h->cfg) || (B % 2 == 0 && B >= 2 && B <= kClRowsMax),
+               "the contrastive (pretrain-cl) model pairs samples 2m and 2m + 1: B = %d must be even, 2 <= B <= %d", B, kClRowsMax);
   hipStream_t st = (hipStream_t)stream;
   const gget_config_t& c = h->cfg;
   CallScope scope(h);
@@ -1716,7 +1747,64 @@ static int forward_pretrain_impl(gget_handle_t h, const int64_t* input_ids_dev, 
     if (h->varlen && h->tc_from_caller && loss_dev)
       if (int e = k_poison_loss(h->wsp<int32_t>(w.vl_status), loss_dev, st)) return e;
   }
+  h->cl_valid = false;
+  if (has_cl(c)) {
+    // contrastive head (modeling_pretrain.py:238-250, modeling_helpers.py:201-227): cl_proj on the pooled row of the final-norm output,
+    // L2 normalisation, InfoNCE over the batch's own rows with ratio_dis = 0.5 (labels or not); pool_row indexes the rows of either
+    // token layout.  A multi-rank caller replaces the loss through gget_cl_set_gathered.
+    if (int e = k_cl_embed_fwd(h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.pool_row), h->P + h->plan.cl, h->wsp<float>(w.cl_z),
+                               h->wsp<float>(w.cl_e), h->wsp<float>(w.cl_rn), B, d, st))
+      return e;
+    if (int e = k_cl_loss_fwd(h->wsp<float>(w.cl_e), B, d, kClRatio, h->wsp<float>(w.cl_stat), h->wsp<float>(w.cl_loss), st)) return e;
+    h->cl_E = h->wsp<float>(w.cl_e);
+    h->cl_map = nullptr;
+    h->cl_N = B;
+    h->cl_valid = true;
+  }
   h->fwd_valid = true;
+  return 0;
+}
+
+extern "C" int gget_cl_logits(gget_handle_t h, const float** z_dev) {
+  GGET_REQUIRE(h && z_dev, "null argument");
+  GGET_REQUIRE(has_cl(h->cfg) && h->fwd_valid && h->cl_valid, "cl_logits: needs a forward of a contrastive (GGET_KIND_PRETRAIN_CL) handle");
+  *z_dev = h->wsp<float>(h->ws.cl_z);
+  return 0;
+}
+
+extern "C" int gget_cl_embeddings(gget_handle_t h, const float** e_dev) {
+  GGET_REQUIRE(h && e_dev, "null argument");
+  GGET_REQUIRE(has_cl(h->cfg) && h->fwd_valid && h->cl_valid, "cl_embeddings: needs a forward of a contrastive (GGET_KIND_PRETRAIN_CL) handle");
+  *e_dev = h->wsp<float>(h->ws.cl_e);
+  return 0;
+}
+
+extern "C" int gget_cl_loss(gget_handle_t h, float* loss_dev, void* stream) {
+  GGET_REQUIRE(h && loss_dev, "null argument");
+  GGET_REQUIRE(has_cl(h->cfg) && h->fwd_valid && h->cl_valid, "cl_loss: needs a forward of a contrastive (GGET_KIND_PRETRAIN_CL) handle");
+  GGET_HIP_CHECK(hipMemcpyAsync(loss_dev, h->wsp<float>(h->ws.cl_loss), 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int gget_cl_set_gathered(gget_handle_t h, const float* E_dev, int N, const int32_t* row_map_dev, void* stream) {
+  GGET_REQUIRE(h && E_dev && row_map_dev, "null argument");
+  GGET_REQUIRE(has_cl(h->cfg) && h->fwd_valid && h->cl_valid, "cl_set_gathered: needs a forward of a contrastive (GGET_KIND_PRETRAIN_CL) handle");
+  GGET_REQUIRE(N >= h->B, "cl_set_gathered: N = %d rows cannot hold the batch's %d", N, h->B);
+  if (int e = k_cl_loss_fwd(E_dev, N, h->cfg.hidden_size, kClRatio, h->wsp<float>(h->ws.cl_stat), h->wsp<float>(h->ws.cl_loss), (hipStream_t)stream))
+    return e;
+  h->cl_E = E_dev;
+  h->cl_map = row_map_dev;
+  h->cl_N = N;
+  return 0;
+}
+
+extern "C" int gget_cl_set_backward_scales(gget_handle_t h, float generative, float contrastive) {
+  GGET_REQUIRE(h != nullptr, "null handle");
+  GGET_REQUIRE(has_cl(h->cfg), "cl_set_backward_scales: the handle is no contrastive (GGET_KIND_PRETRAIN_CL) model");
+  GGET_REQUIRE(generative == 0.f || generative == 1.f, "cl_set_backward_scales: the generative scale is 0 or 1 (no loss scaling on the bf16 path)");
+  GGET_REQUIRE(contrastive == contrastive, "cl_set_backward_scales: NaN");
+  h->cl_gen_scale = generative;
+  h->cl_scale = contrastive;
   return 0;
 }
 
@@ -2044,7 +2132,11 @@ static bool embed_dense_path(int T, int d, int V, bool gated, const ElemDropArg&
 
 extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stream) {
   GGET_REQUIRE(h, "null handle");
-  GGET_REQUIRE(h->fwd_valid && h->have_labels, "backward needs a preceding forward with labels");
+  // contrastive kind: the upstream scales of the two losses (gget_cl_set_backward_scales), consumed here
+  const bool gen_on = !has_cl(h->cfg) || h->cl_gen_scale != 0.f;
+  const float cl_scale = has_cl(h->cfg) ? h->cl_scale : 0.f;
+  h->cl_gen_scale = h->cl_scale = 1.f;
+  GGET_REQUIRE(h->fwd_valid && (h->have_labels || !gen_on), "backward needs a preceding forward with labels");
   GGET_REQUIRE(loss_scale == 1.0f, "loss scaling is not used on the bf16 path (pass 1.0)");
   h->sq_layers = 0;
   CallScope scope(h);
@@ -2064,7 +2156,7 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
     // q|k|v gradient rows are written by nobody and must read as zeros in the weight gradients (K = T) and the dgrad below them
     zr.add(h->wsp<bf16_t>(w.dqkv) + (size_t)h->tc * 3 * d, (size_t)(h->T - h->tc) * 3 * d * 2);
   int T = h->TP;   // the head works in the padded token index space (capacities only: the counts are on the device)
-  if (c.kind == GGET_KIND_PRETRAIN) {
+  if (is_pretrain(c) && gen_on) {
     // ... the scatter target of the lm_head dgrad and the split-K slabs of its weight gradient (both only ever written by the launches below)
     if (h->plan.has_ntp && head_scatter_fused())
       zr.add(h->wsp<bf16_t>(w.dP), (size_t)(h->varlen ? h->T : T) * c.next_n_token * d * 2);
@@ -2078,7 +2170,11 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
     h->emb_cnt_cleared = true;
   }
   if (int e = k_zero_ranges(zr, st)) return e;
-  if (c.kind == GGET_KIND_PRETRAIN) {
+  if (is_pretrain(c) && !gen_on) {
+    // generative scale 0: the head's launches are skipped; its weight gradients are written straight into the bf16 array, so clear them
+    GGET_HIP_CHECK(hipMemsetAsync(h->G + h->plan.lm, 0, (size_t)c.vocab_size * d * 2, st));
+    if (h->plan.has_ntp) GGET_HIP_CHECK(hipMemsetAsync(h->G + h->plan.ntp, 0, (size_t)c.next_n_token * d * d * 2, st));
+  } else if (is_pretrain(c)) {
     const int n = c.next_n_token, V = c.vocab_size, Vp = (int)align_up(V, 64);
     int32_t* counts = h->wsp<int32_t>(w.counts);
     bf16_t* dlog = h->wsp<bf16_t>(w.dlogits);
@@ -2165,6 +2261,15 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
     if (int e = k_score_bwd(h->wsp<float>(w.tdlogits), h->wsp<bf16_t>(w.hidden), h->wsp<int32_t>(w.pool_row),
                             h->P + h->plan.score, s32 + h->plan.score32, c.score_bias ? s32 + h->plan.sbias32 : nullptr, dhid,
                             h->B, c.num_labels, d, st))
+      return e;
+  }
+  if (has_cl(c) && cl_scale != 0.f) {
+    // contrastive head: its gradient is ADDED onto the pooled rows of the final-norm output's gradient, which the generative head above
+    // has only scattered into (a pooled row that carries a label holds a gradient already); dW lands in cl_proj's fp32 accumulator
+    GGET_REQUIRE(h->cl_valid, "backward: the contrastive forward of this handle is missing");
+    if (int e = k_cl_bwd(h->cl_E, h->wsp<float>(w.cl_stat), h->cl_map, h->wsp<float>(w.cl_rn), h->wsp<bf16_t>(w.hidden),
+                         h->wsp<int32_t>(w.pool_row), h->P + h->plan.cl, cl_scale * kClRatio, h->wsp<float>(w.cl_dz), s32 + h->plan.cl32, dhid,
+                         h->cl_N, h->B, d, st))
       return e;
   }
   bf16_t* dx = h->wsp<bf16_t>(w.dxa);
@@ -2255,7 +2360,7 @@ extern "C" int gget_backward_end(gget_handle_t h, void* stream) {
     if (int e = k_rmsnorm_bwd(h->wsp<bf16_t>(w.raw_dxn), h->wsp<bf16_t>(w.raw_x), h->P + h->plan.raw_ln, h->wsp<float>(w.raw_rstd), nullptr,
                               h->wsp<bf16_t>(w.raw_dx), s32 + h->plan.raw_ln32, T, e_, st, kAccumCopies, align_up((uint64_t)e_, 128)))
       return e;
-    if (c.kind == GGET_KIND_PRETRAIN)
+    if (is_pretrain(c))
       if (int e = k_raw_tok_grad(h->wsp<bf16_t>(w.raw_dx), h->wsp<int32_t>(w.raw_flag), s32 + h->plan.raw_tok32, T, e_, st)) return e;
   }
   if (h->stack_long)   // d(e * ratio) / de = ratio
@@ -2574,7 +2679,7 @@ extern "C" int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, f
 
 extern "C" int gget_head_counts(gget_handle_t h, int32_t counts[2], void* stream) {
   GGET_REQUIRE(h && counts, "null argument");
-  GGET_REQUIRE(h->cfg.kind == GGET_KIND_PRETRAIN, "head counts exist only for the pre-train head");
+  GGET_REQUIRE(is_pretrain(h->cfg), "head counts exist only for the pre-train head");
   GGET_HIP_CHECK(hipMemcpyAsync(counts, h->wsp<int32_t>(h->ws.counts), 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
   GGET_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
@@ -2582,7 +2687,7 @@ extern "C" int gget_head_counts(gget_handle_t h, int32_t counts[2], void* stream
 
 extern "C" int gget_head_logits(gget_handle_t h, const void** logits_dev, int32_t* ld) {
   GGET_REQUIRE(h && logits_dev && ld, "null argument");
-  GGET_REQUIRE(h->cfg.kind == GGET_KIND_PRETRAIN, "head logits exist only for the pre-train head");
+  GGET_REQUIRE(is_pretrain(h->cfg), "head logits exist only for the pre-train head");
   *logits_dev = h->wsp<bf16_t>(h->ws.logits);
   *ld = (int32_t)align_up(h->cfg.vocab_size, 64);
   return 0;

@@ -113,6 +113,14 @@ int k_tok_intra_bwd(const float* dl, const float* stat, const void* hidden, cons
 int k_intra_plan(const int64_t* cls_idx, const int32_t* key_len, const int32_t* cu, int32_t* row_start, int64_t* cls_safe, int32_t* flag,
                  int B, int S, int C, hipStream_t st);
 int k_pool_rows(const void* hidden, const int32_t* pool_row, void* out, int B, int d, hipStream_t st);
+// contrastive pre-training head (contrastive.hip): z = W h[pool_row] (fp32), e = z / max(|z|, 1e-12), rnorm = 1 / max(|z|, 1e-12); the InfoNCE
+// loss over E [N,d] (stat [3][N]: row max, log-sum-exp, row term; loss = ratio / N sum of the terms); and the backward of B local rows
+// (row_map: their positions in E, NULL = identity): dz [B,d], dw [d,d] += dz^T h, dhidden[pool_row[b]] += dz_b W.  d % 64 == 0, d <= 1024,
+// 2 <= N <= 2048, N even.
+int k_cl_embed_fwd(const void* hidden, const int32_t* pool_row, const void* w, float* z, float* e, float* rnorm, int B, int d, hipStream_t st);
+int k_cl_loss_fwd(const float* E, int N, int d, float ratio, float* stat, float* loss, hipStream_t st);
+int k_cl_bwd(const float* E, const float* stat, const int32_t* row_map, const float* rnorm, const void* hidden, const int32_t* pool_row,
+             const void* w, float scale, float* dz, float* dw, void* dhidden, int N, int B, int d, hipStream_t st);
 int k_head_linear_fwd(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din, int Dout,
                       int layer, ElemDropArg E, hipStream_t st);
 int k_head_linear_bwd(const float* dy, const void* x, const void* a, const void* w, float* dw, float* dbias, float* dx, int B,

@@ -50,6 +50,27 @@ def all_reduce_bucket(flat: torch.Tensor, bucket, group=None, async_op: bool = T
     return h
 
 
+def gather_cl_embeddings(e_local: torch.Tensor, group=None):
+    """The embedding matrix of the contrastive loss over all ranks, as the reference builds it for world > 1 (src/utils/loss_utils.py
+    :119-124 and cos_sim :149-152): the even rows (`left`) and the odd rows (`right`) of every rank's [B,d] embeddings are all-gathered
+    separately, concatenated in rank order, and interleaved again - row 2m of the result is gathered-left[m], row 2m + 1 gathered-right[m].
+    With m = r B/2 + m' that puts sample b of rank r at row r B + b.  Returns (E [world B, d], int32 [B] positions of the local rows);
+    every rank must hold the same even B.  No gradient flows through the gather: the engine's backward differentiates the loss for the
+    local rows only, which is what GatherLayer.backward hands back (loss_utils.py:99-104)."""
+    B, d = e_local.shape
+    assert B % 2 == 0, f"pretrain-cl needs an even batch, got {B}"
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    halves = []
+    for part in (e_local[0::2].contiguous(), e_local[1::2].contiguous()):
+        out = [torch.empty_like(part) for _ in range(world)]
+        dist.all_gather(out, part, group=group)
+        halves.append(torch.cat(out, dim=0))                       # [world B/2, d]
+    E = torch.stack(halves, dim=1).reshape(world * B, d)           # hstack([left, right]).reshape(-1, d)
+    m = rank * (B // 2) + torch.arange(B // 2, device=e_local.device)
+    pos = torch.stack([2 * m, 2 * m + 1], dim=1).reshape(-1).to(torch.int32)
+    return E, pos
+
+
 def _host_staged(flat: torch.Tensor, group) -> bool:
     # gloo's reduce-scatter / all-gather are fed host tensors: a device arena is staged through host memory (NCCL takes device tensors)
     return flat.is_cuda and dist.get_backend(group) == "gloo"

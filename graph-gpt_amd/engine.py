@@ -333,7 +333,41 @@ class Engine:
         #  had to copy out with a kernel before the next step overwrote it)
         self._loss = torch.empty(1, dtype=torch.float32, device=dev)
         L.check(fn(self.h, _ptr(ids), _ptr(att), _ptr(lab), _ptr(wgt), _ptr(pos), B, S, _ptr(self._loss), _stream()))
+        self._cl_keep = None
         return self._loss[0] if lab is not None else None
+
+    # ------------------------------------------------------------------ contrastive head (KIND_PRETRAIN_CL)
+    def _cl_view(self, getter, B: int) -> torch.Tensor:
+        p = C.c_void_p()
+        L.check(getter(self.h, C.byref(p)))
+        off = p.value - self.workspace.data_ptr()
+        return self.workspace[off: off + B * self.spec.hidden_size * 4].view(torch.float32).view(B, self.spec.hidden_size)
+
+    def cl_logits(self, B: int) -> torch.Tensor:
+        """fp32 [B,d] contrastive logits z = cl_proj(h at the pooled row) of the last forward (gget_cl_logits; a copy)."""
+        return self._cl_view(self.lib.gget_cl_logits, B).clone()
+
+    def cl_embeddings(self, B: int) -> torch.Tensor:
+        """fp32 [B,d] L2-normalised embeddings of the last forward (gget_cl_embeddings; a view of the workspace)."""
+        return self._cl_view(self.lib.gget_cl_embeddings, B)
+
+    def cl_set_gathered(self, E: torch.Tensor, row_map: torch.Tensor):
+        """Hand the embeddings of all ranks [N,d] and the positions of this rank's rows in them to the handle (gget_cl_set_gathered): the
+        contrastive loss and its backward then run over the N rows.  Both tensors are kept alive until the next forward."""
+        E = E.to(device=self.device, dtype=torch.float32).contiguous()
+        row_map = row_map.to(device=self.device, dtype=torch.int32).contiguous()
+        self._cl_keep = (E, row_map)
+        L.check(self.lib.gget_cl_set_gathered(self.h, _ptr(E), int(E.shape[0]), _ptr(row_map), _stream()))
+
+    def cl_loss(self) -> torch.Tensor:
+        """The contrastive loss (ratio_dis applied) of the last forward, or of the gathered matrix set since (gget_cl_loss): a device scalar."""
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        L.check(self.lib.gget_cl_loss(self.h, _ptr(out), _stream()))
+        return out[0]
+
+    def cl_set_backward_scales(self, generative: float = 1.0, contrastive: float = 1.0):
+        """Upstream gradients of head1_loss / head2_loss for the NEXT backward (gget_cl_set_backward_scales); generative is 0 or 1."""
+        L.check(self.lib.gget_cl_set_backward_scales(self.h, float(generative), float(contrastive)))
 
     def forward_task(self, input_ids, attention_mask, position_ids=None, task_labels=None, sample_wgt=None,
                      problem: int = L.PROBLEM_SINGLE_LABEL, num_tokens=None):

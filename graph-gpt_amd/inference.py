@@ -139,6 +139,31 @@ def ft_infer_hidden_states(model, loader, cfg=None, eval_name: str = "test", *, 
     return arenas.idx[:n].view(-1, 1), arenas.logits[:n].view(n, *tail), (arenas.hidden[:n] if save else None)
 
 
+@torch.no_grad()
+def pt_infer_hidden_states(model, loader, cfg=None):
+    """reference log_eval_dump_utils.pt_infer_hidden_states (:166-194): the embeddings of a contrastively pre-trained model - eval mode,
+    one forward per batch without labels (position_ids passed, as there), and (idx i64 [N, 1], head2_logits fp16 [N, d], None) on the
+    model's device in loader order; head2_logits is the un-normalised cl_proj output.  Every batch must hold an even number of samples
+    (the model pairs them; build the loader with conf.eval_loader_drop_last)."""
+    model.eval()
+    device = model.device
+    ls_idx, ls_logits = [], []
+    for data in loader:
+        res = model(input_ids=data["input_ids"].to(device), attention_mask=data["attention_mask"].to(device),
+                    inputs_raw_embeds=data["embed"].to(device) if "embed" in data else None,
+                    position_ids=data["position_ids"].to(device) if "position_ids" in data else None, **_layout_kw(model, data))
+        if res.head2_logits is None:
+            raise ValueError("pt_infer_hidden_states: the model has no contrastive head (head2_logits is None); build it with "
+                             "use_discriminative=True / task_type 'pretrain-cl'")
+        ls_idx.append(torch.as_tensor(data["idx"]).to(device=res.head2_logits.device, dtype=torch.int64).view(-1, 1))
+        ls_logits.append(res.head2_logits.half())
+    if hasattr(model, "check_deferred"):
+        model.check_deferred()
+    if not ls_idx:
+        raise ValueError("pt_infer_hidden_states: the loader yielded no batch")
+    return torch.vstack(ls_idx), torch.vstack(ls_logits), None
+
+
 # ----------------------------------------------------------------------------- node-level records
 def append_node_records(out: torch.Tensor, raw_node_idx: torch.Tensor, idx: torch.Tensor, records: torch.Tensor, state: torch.Tensor):
     """`gget_op_node_records` on device tensors: `out` is the model's output, f32 logits [B, S, C] or the predictions [B, S] (any

@@ -25,7 +25,7 @@ from torch import nn
 
 from . import _lib as L
 from .engine import Engine
-from .spec import KIND_PRETRAIN, KIND_TASK, ModelSpec
+from .spec import KIND_PRETRAIN, KIND_PRETRAIN_CL, KIND_TASK, ModelSpec
 from .weights import make_state_dict
 
 
@@ -95,13 +95,19 @@ class GraphGPTConfig:
         need(int(self.pretraining_tp or 1) == 1, "pretraining_tp > 1 (sliced projections)")
         need(self.embed_dim % 64 == 0 and 0 <= self.embed_dim <= 2048, f"embed_dim={self.embed_dim}: raw-embedding width must be a multiple of 64 (<= 2048)")
         need(self.stack_method in ("short", "long", None), f"stack_method={self.stack_method!r}")
-        need(not self.use_discriminative and self.use_generative, "contrastive (pretrain-cl) head")
+        if kind == KIND_PRETRAIN_CL:    # the pre-train plan + cl_proj (modeling_pretrain.py:96-115); every other kind has no cl_proj
+            need(self.use_discriminative, "KIND_PRETRAIN_CL needs use_discriminative=True")
+            need(self.use_generative, "the contrastive head alone (use_generative=False; no reference launch script runs it)")
+            need(self.hidden_size <= L.CL_MAX_D, f"contrastive head with hidden_size > {L.CL_MAX_D}")
+            need(not self.smtp_inside, "smtp_inside with the contrastive head (the reference's pretrain-cl masks on the host)")
+        else:
+            need(not self.use_discriminative and self.use_generative, "contrastive (pretrain-cl) head")
         need(len(self.mlp) <= 4, "an MLP score head with more than 4 hidden layers")
         need(self.pooling_method == "last", "pooling other than 'last'")
         return ModelSpec(kind=kind, vocab_size=self.vocab_size, hidden_size=self.hidden_size,
                          intermediate_size=self.intermediate_size, num_layers=self.num_hidden_layers,
                          num_heads=self.num_attention_heads, head_dim=64, stacked_feat=self.stacked_feat,
-                         next_n_token=self.next_n_token if kind == KIND_PRETRAIN else 1,
+                         next_n_token=self.next_n_token if kind in (KIND_PRETRAIN, KIND_PRETRAIN_CL) else 1,
                          gated_agg=self.stacked_feat_agg_method == "gated", causal=bool(self.causal_attention),
                          rms_eps=self.rms_norm_eps, rope_theta=self.rope_theta, max_position=self.max_position_embeddings,
                          layer_scale_init=float(self.layer_scale_init_value), num_labels=self.num_labels,
@@ -166,6 +172,26 @@ class _PretrainOutput(DoubleHeadsModelOutput):
         if name == "head1_logits":
             return object.__getattribute__(self, "_lazy").get()
         return object.__getattribute__(self, name)
+
+
+class _TwoLossFn(torch.autograd.Function):
+    """head1_loss (generative) and head2_loss (contrastive) of the pretrain-cl model as ONE autograd node with two outputs: whichever
+    combination of the two is backpropagated - their sum in the reference's step (training_utils.py:33-44) - the HIP backward runs
+    once, with the two upstream gradients as its scales (Engine.cl_set_backward_scales)."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, gen_loss, cl_loss):
+        ctx.model = model
+        ctx.has_gen = gen_loss is not None
+        gen = gen_loss.detach() if ctx.has_gen else anchor.new_zeros(())
+        if not ctx.has_gen:
+            ctx.mark_non_differentiable(gen)
+        return gen, cl_loss.detach()
+
+    @staticmethod
+    def backward(ctx, g_gen, g_cl):
+        ctx.model._autograd_backward_cl(g_gen if ctx.has_gen else None, g_cl)
+        return None, None, None, None
 
 
 class _LossFn(torch.autograd.Function):
@@ -396,7 +422,7 @@ class _GgetModel(nn.Module):
         else:
             e.set_dropout(0.0, 0.0, 0)
         e.set_dropout_ex(pe, pm, ph)
-        if self.kind == KIND_PRETRAIN:
+        if self.kind in (KIND_PRETRAIN, KIND_PRETRAIN_CL):
             e.set_focal_gamma(float(getattr(self.config, "focal_gamma", 0.0) or 0.0))
         return e
 
@@ -420,6 +446,22 @@ class _GgetModel(nn.Module):
                     continue
                 p.grad = (e.view(name, "grad").to(torch.float32) * scale).view(p.shape)
         self._dirty = True  # an external optimizer will now touch the master weights
+
+    def _autograd_backward_cl(self, g_gen, g_cl):
+        """The backward behind _TwoLossFn: g_gen / g_cl are the upstream gradients of head1_loss / head2_loss (None or zeros = that loss
+        is not part of what is backpropagated).  The generative head has no loss scaling on the bf16 path, so its gradient is taken at
+        scale 1 and the common factor (1 for a plain `.backward()`) multiplies the materialised gradients, as _autograd_backward does;
+        the contrastive scale is handed to the engine relative to it."""
+        given = [g.detach().to(torch.float32).reshape(()) for g in (g_gen, g_cl) if g is not None]
+        vals = torch.stack(given).tolist() if given else []      # (one read-back for both scales)
+        gg = 0.0 if g_gen is None else vals[0]
+        gc = 0.0 if g_cl is None else vals[-1]
+        if gg != 0.0:
+            self._engine.cl_set_backward_scales(1.0, gc / gg)
+            self._autograd_backward(torch.tensor(gg))
+        else:
+            self._engine.cl_set_backward_scales(0.0, 1.0 if gc != 0.0 else 0.0)
+            self._autograd_backward(torch.tensor(gc))
 
     def _check_positions(self, position_ids, S):
         """The RoPE table is precomputed for max_position_embeddings rows (the reference evaluates the rotary embedding on the
@@ -542,6 +584,21 @@ class _GgetModel(nn.Module):
 class GraphGPTPretrainBase(_GgetModel):
     kind = KIND_PRETRAIN
 
+    def __init__(self, config: GraphGPTConfig, seed: int = 0):
+        # task_type = "pretrain-cl" (use_discriminative, src/conf/base_configs.py:246-247): the contrastive engine kind - the pre-train
+        # plan plus cl_proj and the InfoNCE head (modeling_pretrain.py:96-115)
+        if getattr(config, "use_discriminative", False):
+            self.kind = KIND_PRETRAIN_CL
+        super().__init__(config, seed=seed)
+        self.use_generative, self.use_discriminative = bool(config.use_generative), bool(config.use_discriminative)
+        self.ratio_dis = 0.5 if (self.use_generative and self.use_discriminative) else 1
+        try:                                    # modeling_pretrain.py:108-111
+            self.world_size = torch.distributed.get_world_size()
+        except Exception:
+            self.world_size = 1
+        if self.use_discriminative:
+            print(f"WORLD-SIZE for CL loss gathering and calculation: {self.world_size}")
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 inputs_raw_embeds=None, labels=None, label_mask=None, sample_wgt=None, use_cache=None,
                 output_attentions=None, output_hidden_states=None, return_dict=None, cache_position=None, num_tokens=None):
@@ -569,6 +626,12 @@ class GraphGPTPretrainBase(_GgetModel):
         if attention_mask is None:
             attention_mask = torch.ones(B, S, dtype=torch.int64)
         assert attention_mask.dim() in (2, 3), "attention_mask is [B,S] (right padding) or [B,S,S] (packed, block-diagonal)"
+        cl = self.kind == KIND_PRETRAIN_CL
+        if cl:
+            if B % 2 != 0:
+                raise ValueError(f"pretrain-cl pairs samples 2m and 2m + 1 (the two views of one graph): the batch size {B} must be even")
+            if attention_mask.dim() == 3:
+                raise NotImplementedError("pretrain-cl with a packed [B,S,S] mask (the reference's pretrain-cl never packs)")
         if attention_mask.dim() == 3:
             assert not self.spec.causal, "the reference only builds the 3-D mask for bi-directional attention (modeling_pretrain.py:197-198)"
         self._check_positions(position_ids, S)
@@ -577,11 +640,31 @@ class GraphGPTPretrainBase(_GgetModel):
         if inputs_raw_embeds is not None:
             e.set_raw_embeds(inputs_raw_embeds, first_label_only=bool(getattr(self.config, "smtp_inside", False)))
         loss = e.forward_pretrain(input_ids, attention_mask, labels, sample_wgt, position_ids, num_tokens=n_real)
-        out = _PretrainOutput(self._wrap_loss(loss), _LazyLogits(self))
+        if cl:
+            out = self._cl_output(e, loss, B)
+        else:
+            out = _PretrainOutput(self._wrap_loss(loss), _LazyLogits(self))
         if want_hs:
             out.hidden_states = self._collect_hidden_states(B, S)       # modeling_pretrain.py:264 (outputs.hidden_states)
         if self._want_attentions(output_attentions):
             out.attentions = self._collect_attentions(B, S)             # modeling_pretrain.py:265 (outputs.attentions)
+        return out
+
+
+    def _cl_output(self, e, gen_loss, B):
+        """head2_* of the pretrain-cl model (modeling_pretrain.py:238-262): the un-normalised cl_proj output and ratio_dis * InfoNCE.
+        With more than one rank the embeddings of all ranks are gathered first (loss_utils.py:119-124) and the loss runs over them."""
+        from . import dp
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            E, pos = dp.gather_cl_embeddings(e.cl_embeddings(B))
+            e.cl_set_gathered(E, pos)
+        cl_loss = e.cl_loss()
+        if torch.is_grad_enabled():
+            gen, cl_loss = _TwoLossFn.apply(self._anchor, self, gen_loss, cl_loss)
+            gen_loss = gen if gen_loss is not None else None
+        out = _PretrainOutput(gen_loss, _LazyLogits(self))
+        out.head2_loss, out.head2_logits = cl_loss, e.cl_logits(B)
         return out
 
 

@@ -14,6 +14,7 @@ from typing import Dict, List, Tuple
 
 KIND_PRETRAIN = 0   # GraphGPTPretrainBase: SMTP/NTP head (n_token_proj + lm_head + CE)
 KIND_TASK = 1       # GraphGPTTaskModel: `score` head on the pooled ("last") row
+KIND_PRETRAIN_CL = 2  # GraphGPTPretrainBase with use_discriminative (task_type "pretrain-cl"): the pre-train plan + cl_proj and the InfoNCE head
 
 
 @dataclasses.dataclass
@@ -44,6 +45,11 @@ class ModelSpec:
     rope_range: float = 0.0         # > 0: position ids passed to a forward are rescaled to [0, rope_range) per row (utils_graphgpt.py:574-581)
     embed_dim: int = 0              # > 0: raw-embedding inputs [B,S,embed_dim] (embed_layernorm, emb_mask_token (pre-train), embed_proj)
 
+    @property
+    def is_pretrain(self) -> bool:
+        """Both pre-train kinds carry the SMTP/NTP head; the contrastive one adds cl_proj."""
+        return self.kind in (KIND_PRETRAIN, KIND_PRETRAIN_CL)
+
     def __post_init__(self):
         assert self.hidden_size == self.num_heads * self.head_dim, "no GQA / odd head dims on this path"
         assert self.head_dim == 64, "reference fixes head_dim = 64 (src/utils/modules_utils.py:37-42)"
@@ -57,7 +63,7 @@ class ModelSpec:
             t["stacked_feat_agg.weight"] = (F, d)
         if self.embed_dim > 0:    # modeling_pretrain.py:69-84 / modeling_finetune.py:76-85
             t["embed_layernorm.weight"] = (self.embed_dim,)
-            if self.kind == KIND_PRETRAIN:
+            if self.is_pretrain:
                 t["emb_mask_token"] = (1, 1, self.embed_dim)
             t["embed_proj.weight"] = (d, self.embed_dim)
         for i in range(self.num_layers):
@@ -76,10 +82,12 @@ class ModelSpec:
             if self.layer_scale_init > 0:
                 t[p + "lambda_2"] = (d,)
         t["model.norm.weight"] = (d,)
-        if self.kind == KIND_PRETRAIN:
+        if self.is_pretrain:
             if self.next_n_token > 1:
                 t["n_token_proj.weight"] = (self.next_n_token * d, d)
             t["lm_head.weight"] = (V, d)
+            if self.kind == KIND_PRETRAIN_CL:   # modeling_pretrain.py:106-107 (last, as the reference registers it)
+                t["cl_proj.weight"] = (d, d)
         elif len(self.head_mlp) > 0:
             dims = [d] + [int(x) for x in self.head_mlp] + [self.num_labels]
             for i in range(len(dims) - 1):

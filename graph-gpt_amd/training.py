@@ -1295,6 +1295,7 @@ class TrainingPipeline:
     def _extract_config(self):
         from . import conf as CF
         g = CF._get
+        CF.sync_config(self.cfg)      # (task_type "pretrain-cl" -> pt_head.use_discriminative, base_configs.py:246-247)
         self.token_cfg, self.model_cfg, self.train_cfg = g(self.cfg, "tokenization"), g(self.cfg, "model"), g(self.cfg, "training")
         self.data_cfg = g(self.token_cfg, "data") if self.token_cfg is not None else None
         self.sched_cfg, self.optim_cfg = g(self.train_cfg, "schedule"), g(self.train_cfg, "optimizer")

@@ -31,6 +31,7 @@ extern "C" {
 
 #define GGET_KIND_PRETRAIN 0 /* GraphGPTPretrainBase (src/models/graphgpt/modeling_pretrain.py:57) */
 #define GGET_KIND_TASK 1     /* GraphGPTTaskModel    (src/models/graphgpt/modeling_finetune.py:64) */
+#define GGET_KIND_PRETRAIN_CL 2 /* GraphGPTPretrainBase with use_generative and use_discriminative (task_type "pretrain-cl", modeling_pretrain.py:96-115): the pre-train parameter plan plus cl_proj.weight [d,d]; everything said of GGET_KIND_PRETRAIN holds for it, see "Contrastive pre-training head" below */
 
 #define GGET_PROBLEM_SINGLE_LABEL 0 /* CrossEntropy on pooled logits (modeling_finetune.py:209-214) */
 #define GGET_PROBLEM_REGRESSION_L1 1 /* L1Loss  (modeling_finetune.py:183-197) */
@@ -1077,6 +1078,54 @@ int gget_op_infer_append(const float* logits, const void* hidden, const int64_t*
                          int64_t row0, int64_t capacity, int B, int C, int d, void* stream);
 int gget_op_node_records(const float* logits, const int64_t* pred, const int64_t* raw_node_idx, const int64_t* idx, int64_t* records,
                          int64_t* state, int64_t cap, int B, int S, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Contrastive pre-training head (GGET_KIND_PRETRAIN_CL; task_type = "pretrain-cl").  replaces: `cl_proj` and the discriminative branch of
+ * GraphGPTPretrainBase (src/models/graphgpt/modeling_pretrain.py:96-115, :238-257), _get_cl_logits_loss (modeling_helpers.py:201-227) and
+ * _dist_infonce / cos_sim / GatherLayer (src/utils/loss_utils.py:89-167).
+ *   r_b = (entries of input_ids[b,:,0] that differ from pad_token_id) - 1, h_b = the final-norm output at row r_b (bf16)
+ *   z_b = cl_proj(h_b), fp32 accumulation, kept in fp32: the contrastive logits (head2_logits)       e_b = z_b / max(|z_b|, 1e-12)
+ *   samples 2m and 2m + 1 are the two views of one graph: p(i) = i ^ 1; E [N,d] = the embeddings of all ranks (N = B for one rank)
+ *   scores[i][j] = 20 <E[i], E[p(j)]>, scores[i][p(i)] = the most negative float (the self-similarity is masked)
+ *   loss = ratio / 2 (CE(scores, arange(N)) + CE(scores^T, arange(N))), ratio = 0.5 beside the generative head (ratio_dis)
+ * Shapes: d % 64 == 0, d <= 1024, 2 <= N <= 2048, N even; anything else is error 2 ("unsupported") without a launch.
+ * The N x N scores are never stored and never rounded to bf16; every sum has a fixed order (no atomics: two calls give the same bits).
+ * ------------------------------------------------------------------------------------------ */
+/* replaces: hidden_states[bz_idx, sequence_lengths], cl_proj and F.normalize (modeling_helpers.py:213-218).  hidden bf16 [rows,d],
+ * pool_row int32 [B] (rows of `hidden`), w bf16 [d,d]; z, e f32 [B,d]; rnorm f32 [B] = 1 / max(|z_b|, 1e-12).  B = 0: nothing to do. */
+int gget_op_cl_embed_fwd(const void* hidden, const int32_t* pool_row, const void* w, float* z, float* e, float* rnorm, int B, int d,
+                         void* stream);
+/* replaces: _dist_infonce after the gather (loss_utils.py:127-137; cos_sim :140-167).  E f32 [N,d], rows in the order of cos_sim's
+ * `left_new`.  stat f32 [3][N]: max_{k != i} 20 <E_i, E_k>, its log-sum-exp over k != i, and the row's loss term lse_i - 20 <E_i, E_p(i)>;
+ * loss[0] = ratio / N * sum of the terms (the transposed cross-entropy sums the same N terms: the term of column i is the term of row p(i)). */
+int gget_op_cl_loss_fwd(const float* E, int N, int d, float ratio, float* stat, float* loss, void* stream);
+/* replaces: autograd through the above for the caller's own B rows (GatherLayer.backward, loss_utils.py:99-104, keeps the local slice).
+ * row_map int32 [B]: the position of local row b in E (NULL: b itself, N = B); stat of gget_op_cl_loss_fwd on the same E; rnorm, hidden,
+ * pool_row, w of gget_op_cl_embed_fwd; scale = upstream gradient * ratio.
+ *   dE_b = 20 scale / N sum_{k != i} (P[i][k] + P[k][i] - 2 [k == p(i)]) E_k, i = row_map[b], P[i][k] = exp(20 <E_i, E_k> - lse_i)
+ *          (row i as the query of its own term and as a key of every other row's)
+ *   dz f32 [B,d] = (dE_b - e_b <e_b, dE_b>) rnorm_b (overwritten);  dw f32 [d,d] += dz^T h;
+ *   dhidden bf16 [rows,d]: row pool_row[b] += dz_b w (bf16 read, fp32 sum, one rounding; other rows untouched). */
+int gget_op_cl_bwd(const float* E, const float* stat, const int32_t* row_map, const float* rnorm, const void* hidden, const int32_t* pool_row,
+                   const void* w, float scale, float* dz, float* dw, void* dhidden, int N, int B, int d, void* stream);
+/* Engine calls of a GGET_KIND_PRETRAIN_CL handle.  gget_forward_pretrain runs the generative head as for GGET_KIND_PRETRAIN and then the
+ * contrastive forward on the batch's own rows (B even, B <= 2048; labels may be NULL: the contrastive loss needs none); a packed [B,S,S]
+ * mask is refused (the reference's pretrain-cl masks on the host and never packs).
+ * replaces: `head2_logits` / `head2_loss` of the model output (modeling_pretrain.py:250-262): z f32 [B,d] and e f32 [B,d] of the last
+ * forward (pointers into the workspace), and the loss scalar copied to loss_dev f32[1] on `stream`. */
+int gget_cl_logits(gget_handle_t h, const float** z_dev);
+int gget_cl_embeddings(gget_handle_t h, const float** e_dev);
+int gget_cl_loss(gget_handle_t h, float* loss_dev, void* stream);
+/* replaces: the two GatherLayer.apply + torch.cat of _dist_infonce for world > 1 (loss_utils.py:119-124).  After a forward, hands the
+ * gathered matrix E_dev f32 [N,d] (caller-owned, alive until the backward has run) and row_map_dev int32 [B] (the positions of this
+ * rank's rows in it) to the handle: the loss and the row statistics are recomputed over the N rows at once, gget_cl_loss then returns
+ * that loss and the backward differentiates it for the local rows.  Holds until the next forward. */
+int gget_cl_set_gathered(gget_handle_t h, const float* E_dev, int N, const int32_t* row_map_dev, void* stream);
+/* replaces: the upstream gradients of `head1_loss` and `head2_loss` (autograd; src/utils/training_utils.py:44,66 backpropagates their
+ * sum): the scales the NEXT gget_backward_begin / gget_backward applies to the generative and the contrastive loss, consumed by it
+ * (default 1, 1).  generative = 1 or 0 (0: the generative head's backward is skipped, its weight gradients are zero; required when the
+ * forward had no labels); contrastive: any float, 0 skips the contrastive backward (cl_proj's gradient is then exactly zero). */
+int gget_cl_set_backward_scales(gget_handle_t h, float generative, float contrastive);
 
 #ifdef __cplusplus
 }
