@@ -150,6 +150,16 @@ SIGNATURES = {
     "gget_op_ls_rmsnorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "gget_op_accum_layout": (i32, [i32, C.POINTER(i32), C.POINTER(u64)]),
     "gget_op_rmsnorm_bwd_ls": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    # masks on: (elem_p, elem_seed, elem_rows) and, for the residual kernels, (path_rate, path_seed, path_S, path_row_b) before the stream
+    "gget_op_ls_rmsnorm_fwd_drop": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, C.c_uint32, vp, f32, C.c_uint32, i32, vp, vp]),
+    "gget_op_rmsnorm_bwd_ls_drop": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint32, vp, f32, C.c_uint32, i32, vp, vp]),
+    "gget_op_ls_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, C.c_uint32, vp, f32, C.c_uint32, i32, vp, vp]),
+    "gget_op_ls_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint32, vp, f32, C.c_uint32, i32, vp, vp]),
+    "gget_op_elem_dropout": (i32, [vp, i64, i32, C.c_uint32, f32, C.c_uint32, vp, vp]),
+    "gget_op_embed_fwd_drop": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint32, vp, vp]),
+    "gget_op_embed_bwd_drop": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, C.c_uint32, vp, vp]),
+    "gget_op_head_linear_fwd_drop": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint32, vp, vp]),
+    "gget_op_head_linear_bwd_drop": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint32, vp, vp]),
     "gget_op_rope_table": (i32, [vp, vp, i32, f32, vp]),
     "gget_op_rope_range_table": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp]),
     "gget_op_clamp_positions": (i32, [vp, vp, vp, i64, i32, vp]),

@@ -1001,6 +1001,13 @@ __global__ void __launch_bounds__(256) ls_fwd_kernel(const bf16_t* __restrict__ 
     *reinterpret_cast<uint4*>(out + w * 8) = pack8(r);
   }
 }
+int ls_fwd(const bf16_t* res, const bf16_t* y, const bf16_t* lam, bf16_t* out, int T, int d, PathDrop D, ElemDropArg E, hipStream_t st) {
+  if (T == 0) return 0;
+  const int g = (int)std::min<long>(4096, ((long)T * (d / 8) + 255) / 256);
+  hipLaunchKernelGGL(ls_fwd_kernel, dim3(g), dim3(256), 0, st, res, y, lam, out, (long)T, d, D, E);
+  GGET_LAUNCH_CHECK();
+  return 0;
+}
 // ls_fwd_kernel and the RMSNorm that always follows it (rmsnorm_fwd_kernel, kernels.hip) in one pass over the rows: the residual stream
 // is written (out) and normalised (xn, rstd) without being read back - same arithmetic and rounding points as the two kernels.
 // A wave owns a row at a time; NCH = 16-byte chunks per lane.
@@ -1129,6 +1136,18 @@ __global__ void __launch_bounds__(256) ls_bwd_kernel(const bf16_t* __restrict__ 
       unsafeAtomicAdd(dst + j, sum);
     }
   }
+}
+// d/8 <= 256 chunks per row (d <= 2048 is checked at create), 512 blocks; dlam: kAccumCopies replicas of align_up(d, 128) floats, or nullptr
+int ls_bwd(const bf16_t* dy, const bf16_t* y, const bf16_t* lam, bf16_t* dsc, float* dlam, int T, int d, PathDrop D, ElemDropArg E,
+           hipStream_t st) {
+  if (T == 0) return 0;
+  const int ls_rl = 256 / (d / 8);
+  dim3 lsgrid((unsigned)std::min(512, (T + ls_rl - 1) / ls_rl));
+  const size_t ls_lds_bytes = (size_t)ls_rl * d * sizeof(float);
+  hipLaunchKernelGGL(ls_bwd_kernel, lsgrid, dim3(256), ls_lds_bytes, st, dy, y, lam, dsc, dlam, T, d, D, kAccumCopies,
+                     align_up((uint64_t)d, 128), E);
+  GGET_LAUNCH_CHECK();
+  return 0;
 }
 
 // RMSNorm backward (rmsnorm_bwd_kernel, kernels.hip) and the LayerScale / DropPath backward that consumes its result (ls_bwd_kernel) in
@@ -1433,7 +1452,6 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
     const bf16_t* lam1 = h->plan.has_ls ? h->P + lo.lam1 : nullptr;
     const bf16_t* lam2 = h->plan.has_ls ? h->P + lo.lam2 : nullptr;
     const PathDrop pd1 = h->path_drop(i, 0), pd2 = h->path_drop(i, 1);
-    const int g = (int)std::min<long>(4096, ((long)T * (d / 8) + 255) / 256);
     if (int e = gemm_nt(attn, h->P + lo.wo, araw, nullptr, T, d, d, d, d, d, nullptr, st)) return e;
     // the residual kernels also produce what the RMSNorm behind them would: the residual stream is written and normalised in one pass
     // (the second one normalises for the NEXT layer, or with the final norm)
@@ -1443,7 +1461,7 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
                                  ElemDropArg{0, 1.f, 0}, st))
         return e;
     } else {
-      hipLaunchKernelGGL(ls_fwd_kernel, dim3(g), dim3(256), 0, st, x_in, araw, lam1, xmid, (long)T, d, pd1, ElemDropArg{0, 1.f, 0});
+      if (int e = ls_fwd(x_in, araw, lam1, xmid, T, d, pd1, ElemDropArg{0, 1.f, 0}, st)) return e;
       if (int e = k_rmsnorm_fwd(xmid, h->P + lo.ln2, xn2, h->wsp<float>(lw.rstd2), T, d, c.rms_eps, st)) return e;
     }
     if (int e = gateup_geglu(xn2, h->P + lo.wgu, gu, hh, T, d, ff, st)) return e;
@@ -1457,9 +1475,7 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
       float* nrs = last ? h->wsp<float>(h->ws.rstd_f) : h->wsp<float>(h->ws.lw[i + 1].rstd1);
       return ls_rmsnorm_fwd(xmid, mraw, lam2, x_out, nw, nxn, nrs, T, d, c.rms_eps, pd2, md, st);
     }
-    hipLaunchKernelGGL(ls_fwd_kernel, dim3(g), dim3(256), 0, st, xmid, mraw, lam2, x_out, (long)T, d, pd2, md);
-    GGET_LAUNCH_CHECK();
-    return 0;
+    return ls_fwd(xmid, mraw, lam2, x_out, T, d, pd2, md, st);
   }
   if (int e = gemm_nt(attn, h->P + lo.wo, xmid, x_in, T, d, d, d, d, d, nullptr, st)) return e;
   if (int e = k_rmsnorm_fwd(xmid, h->P + lo.ln2, xn2, h->wsp<float>(lw.rstd2), T, d, c.rms_eps, st)) return e;
@@ -1938,19 +1954,15 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
   bf16_t* dh = h->wsp<bf16_t>(w.dh);
   const bf16_t* dy_down = dx_out;  // gradient of the down_proj output
   const bf16_t* dy_o = nullptr;    // gradient of the o_proj output
-  // LayerScale / DropPath backward: d/8 <= 256 chunks per row (d <= 2048 is checked at create), 512 blocks
-  const int ls_rl = 256 / (d / 8);
-  dim3 lsgrid((unsigned)std::min(512, (T + ls_rl - 1) / ls_rl));
-  const size_t ls_lds_bytes = (size_t)ls_rl * d * sizeof(float);
   const bool fuse_ls = h->plan.has_res && ls_norm_fused();
   if (h->plan.has_res) {
     // x_out = xmid + keep_b * lam2 * mraw  =>  d mraw = keep_b * lam2 * dx_out, dlam2 += sum keep_b * dx_out * mraw
     // (already done by the RMSNorm backward that produced dx_out when the two are fused - see the end of this function)
     bf16_t* dsc = h->wsp<bf16_t>(w.dscaled);
-    if (!h->ls2_done)
-      hipLaunchKernelGGL(ls_bwd_kernel, lsgrid, dim3(256), ls_lds_bytes, st, dx_out, h->wsp<bf16_t>(lw.mraw),
-                         h->plan.has_ls ? h->P + lo.lam2 : nullptr, dsc, h->plan.has_ls ? s32 + lo.lam2_32 : nullptr, T, d,
-                         h->path_drop(i, 1), kAccumCopies, align_up((uint64_t)d, 128), h->mlp_drop(i));
+    if (!h->ls2_done)   // (LayerScale / DropPath backward of the MLP branch)
+      if (int e = ls_bwd(dx_out, h->wsp<bf16_t>(lw.mraw), h->plan.has_ls ? h->P + lo.lam2 : nullptr, dsc,
+                         h->plan.has_ls ? s32 + lo.lam2_32 : nullptr, T, d, h->path_drop(i, 1), h->mlp_drop(i), st))
+        return e;
     h->ls2_done = false;
     dy_down = dsc;   // stays alive for the grouped wgrad at the end of the layer (the o_proj branch has its own buffer)
   }
@@ -1996,9 +2008,9 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
     dy_o = h->wsp<bf16_t>(w.dscaled2);
   } else if (h->plan.has_res) {
     bf16_t* dsc = h->wsp<bf16_t>(w.dscaled2);
-    hipLaunchKernelGGL(ls_bwd_kernel, lsgrid, dim3(256), ls_lds_bytes, st, dx_mid, h->wsp<bf16_t>(lw.araw),
-                       h->plan.has_ls ? h->P + lo.lam1 : nullptr, dsc, h->plan.has_ls ? s32 + lo.lam1_32 : nullptr, T, d,
-                       h->path_drop(i, 0), kAccumCopies, align_up((uint64_t)d, 128), ElemDropArg{0, 1.f, 0});
+    if (int e = ls_bwd(dx_mid, h->wsp<bf16_t>(lw.araw), h->plan.has_ls ? h->P + lo.lam1 : nullptr, dsc,
+                       h->plan.has_ls ? s32 + lo.lam1_32 : nullptr, T, d, h->path_drop(i, 0), ElemDropArg{0, 1.f, 0}, st))
+      return e;
     dy_o = dsc;
   }
   // attention: dattn = dy_o W_o ; (dq,dk,dv) ; inverse RoPE ; dxn1 = dqkv W_qkv
@@ -2908,12 +2920,20 @@ extern "C" int gget_op_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                                    float* dw_accum, int T, int d, void* stream) {
   return k_rmsnorm_bwd(dy, x, w, rstd, dres, dx, dw_accum, T, d, (hipStream_t)stream);
 }
+// (the _drop entries: embedding dropout from (elem_p, elem_seed, elem_rows) through gget_engine::elem_drop; the plain ones call them with it off)
+extern "C" int gget_op_embed_fwd_drop(const int64_t* ids, const void* emb, const void* gate, void* out, int T, int F, int ldF, int d,
+                                      float elem_p, uint32_t elem_seed, const int32_t* elem_rows, void* stream) {
+  GGET_REQUIRE(elem_p < 1.f, "embed_fwd: bad mask arguments");
+  return k_embed_fwd(ids, emb, gate, out, T, F, ldF, d, (hipStream_t)stream, gget_engine::elem_drop(elem_p, elem_seed, elem_rows));
+}
 extern "C" int gget_op_embed_fwd(const int64_t* ids, const void* emb, const void* gate, void* out, int T, int F, int ldF, int d,
                                  void* stream) {
-  return k_embed_fwd(ids, emb, gate, out, T, F, ldF, d, (hipStream_t)stream);
+  return gget_op_embed_fwd_drop(ids, emb, gate, out, T, F, ldF, d, 0.f, 0u, nullptr, stream);
 }
-extern "C" int gget_op_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb_accum,
-                                 float* dgate_accum, int T, int F, int ldF, int d, int V, int pad_id, void* stream) {
+extern "C" int gget_op_embed_bwd_drop(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb_accum,
+                                      float* dgate_accum, int T, int F, int ldF, int d, int V, int pad_id, float elem_p, uint32_t elem_seed,
+                                      const int32_t* elem_rows, void* stream) {
+  GGET_REQUIRE(elem_p < 1.f, "embed_bwd: bad mask arguments");
   // (before the workspaces are sized from them; the launchers check again)
   GGET_REQUIRE(ids && dx && demb_accum && (!gate || (emb && dgate_accum)), "embed_bwd: null argument");
   GGET_REQUIRE(T >= 0 && F >= 1 && ldF >= F && d > 0 && d % 8 == 0 && V >= 1, "embed_bwd: bad shape T %d F %d ldF %d d %d V %d", T, F, ldF, d, V);
@@ -2924,11 +2944,15 @@ extern "C" int gget_op_embed_bwd(const int64_t* ids, const void* dx, const void*
     GGET_HIP_CHECK(hipMalloc(&cnt, (size_t)T * align_up((uint64_t)V, 64) * 2 + (size_t)kEmbDenseSplit * V * d * 4));
   void* slab = cnt ? static_cast<unsigned char*>(cnt) + (size_t)T * align_up((uint64_t)V, 64) * 2 : nullptr;
   const int rc = embed_bwd(ids, dx, emb, gate, demb_accum, dgate_accum, T, F, ldF, d, V, pad_id, ws, cnt, slab, (hipStream_t)stream,
-                           ElemDropArg{0, 1.f, 0});
+                           gget_engine::elem_drop(elem_p, elem_seed, elem_rows));
   (void)hipStreamSynchronize((hipStream_t)stream);
   (void)hipFree(ws);
   if (cnt) (void)hipFree(cnt);
   return rc;
+}
+extern "C" int gget_op_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb_accum,
+                                 float* dgate_accum, int T, int F, int ldF, int d, int V, int pad_id, void* stream) {
+  return gget_op_embed_bwd_drop(ids, dx, emb, gate, demb_accum, dgate_accum, T, F, ldF, d, V, pad_id, 0.f, 0u, nullptr, stream);
 }
 extern "C" int gget_op_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B, int S,
                             int H, int inverse, void* stream) {
@@ -3098,13 +3122,48 @@ extern "C" int gget_op_rmsnorm_dw(const void* dy, const void* x, const float* rs
   GGET_REQUIRE(dy && x && rstd && dw_accum && T >= 0 && copies >= 1 && copy_stride >= (uint64_t)d, "rmsnorm_dw: bad arguments");
   return k_rmsnorm_dw(dy, x, rstd, dw_accum, T, d, (hipStream_t)stream, copies, copy_stride);
 }
-extern "C" int gget_op_ls_rmsnorm_fwd(const void* res, const void* y, const void* lam, void* out, const void* w, void* xn, float* rstd, int T,
-                                      int d, float eps, void* stream) {
+// test-only entries of the dropout / DropPath / LayerScale family (tests/test_gpu_drop.py): every argument of the launcher, no arithmetic
+// here.  The masks: (elem_p, elem_seed, elem_rows) becomes the ElemDropArg through gget_engine::elem_drop - the engine's threshold rule -
+// and (path_rate, path_seed, path_S, path_row_b) is the PathDropArg as it stands.  The entries without masks call these with everything off.
+static PathDropArg path_arg(float rate, uint32_t seed, int S, const int32_t* row_b) { return PathDropArg{rate, seed, S, row_b}; }
+extern "C" int gget_op_ls_rmsnorm_fwd_drop(const void* res, const void* y, const void* lam, void* out, const void* w, void* xn, float* rstd,
+                                           int T, int d, float eps, float elem_p, uint32_t elem_seed, const int32_t* elem_rows,
+                                           float path_rate, uint32_t path_seed, int path_S, const int32_t* path_row_b, void* stream) {
   GGET_REQUIRE(res && y && out && w && xn && rstd && T >= 0, "ls_rmsnorm_fwd: null argument");
   GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "ls_rmsnorm_fwd: d=%d unsupported", d);
+  GGET_REQUIRE(elem_p < 1.f && path_rate < 1.f && (path_rate <= 0.f || path_row_b || path_S >= 1), "ls_rmsnorm_fwd: bad mask arguments");
   if (T == 0) return 0;
   return ls_rmsnorm_fwd((const bf16_t*)res, (const bf16_t*)y, (const bf16_t*)lam, (bf16_t*)out, (const bf16_t*)w, (bf16_t*)xn, rstd, T, d, eps,
-                        PathDropArg{0.f, 0u, 1, nullptr}, ElemDropArg{0, 1.f, 0}, (hipStream_t)stream);
+                        path_arg(path_rate, path_seed, path_S, path_row_b), gget_engine::elem_drop(elem_p, elem_seed, elem_rows),
+                        (hipStream_t)stream);
+}
+extern "C" int gget_op_ls_rmsnorm_fwd(const void* res, const void* y, const void* lam, void* out, const void* w, void* xn, float* rstd, int T,
+                                      int d, float eps, void* stream) {
+  return gget_op_ls_rmsnorm_fwd_drop(res, y, lam, out, w, xn, rstd, T, d, eps, 0.f, 0u, nullptr, 0.f, 0u, 1, nullptr, stream);
+}
+extern "C" int gget_op_ls_fwd(const void* res, const void* y, const void* lam, void* out, int T, int d, float elem_p, uint32_t elem_seed,
+                              const int32_t* elem_rows, float path_rate, uint32_t path_seed, int path_S, const int32_t* path_row_b,
+                              void* stream) {
+  GGET_REQUIRE(res && y && out && T >= 0, "ls_fwd: null argument");
+  GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "ls_fwd: d=%d unsupported", d);
+  GGET_REQUIRE(elem_p < 1.f && path_rate < 1.f && (path_rate <= 0.f || path_row_b || path_S >= 1), "ls_fwd: bad mask arguments");
+  return ls_fwd((const bf16_t*)res, (const bf16_t*)y, (const bf16_t*)lam, (bf16_t*)out, T, d, path_arg(path_rate, path_seed, path_S, path_row_b),
+                gget_engine::elem_drop(elem_p, elem_seed, elem_rows), (hipStream_t)stream);
+}
+/* dlam_accum: the kAccumCopies replicas of gget_op_accum_layout, or NULL */
+extern "C" int gget_op_ls_bwd(const void* dy, const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d, float elem_p,
+                              uint32_t elem_seed, const int32_t* elem_rows, float path_rate, uint32_t path_seed, int path_S,
+                              const int32_t* path_row_b, void* stream) {
+  GGET_REQUIRE(dy && y && dsc && T >= 0, "ls_bwd: null argument");
+  GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "ls_bwd: d=%d unsupported", d);
+  GGET_REQUIRE(elem_p < 1.f && path_rate < 1.f && (path_rate <= 0.f || path_row_b || path_S >= 1), "ls_bwd: bad mask arguments");
+  return ls_bwd((const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)lam, (bf16_t*)dsc, dlam_accum, T, d,
+                path_arg(path_rate, path_seed, path_S, path_row_b), gget_engine::elem_drop(elem_p, elem_seed, elem_rows), (hipStream_t)stream);
+}
+extern "C" int gget_op_elem_dropout(void* x, int64_t T, int n, uint32_t stream_id, float elem_p, uint32_t elem_seed, const int32_t* elem_rows,
+                                    void* stream) {
+  GGET_REQUIRE(x && T >= 0 && n > 0 && elem_p < 1.f, "elem_dropout: bad arguments");
+  return k_elem_dropout(x, (long)T, n, stream_id, gget_engine::elem_drop(elem_p, elem_seed, elem_rows), (hipStream_t)stream);
 }
 extern "C" int gget_op_accum_layout(int d, int* copies, uint64_t* copy_stride) {
   GGET_REQUIRE(copies && copy_stride && d > 0, "accum_layout: bad arguments");
@@ -3112,14 +3171,22 @@ extern "C" int gget_op_accum_layout(int d, int* copies, uint64_t* copy_stride) {
   *copy_stride = align_up((uint64_t)d, 128);
   return 0;
 }
+extern "C" int gget_op_rmsnorm_bwd_ls_drop(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
+                                           float* dw_accum, const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d,
+                                           float elem_p, uint32_t elem_seed, const int32_t* elem_rows, float path_rate, uint32_t path_seed,
+                                           int path_S, const int32_t* path_row_b, void* stream) {
+  GGET_REQUIRE(dy && x && w && rstd && dx && dw_accum && y && dsc && T >= 0, "rmsnorm_bwd_ls: null argument");
+  GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "rmsnorm_bwd_ls: d=%d unsupported", d);
+  GGET_REQUIRE(elem_p < 1.f && path_rate < 1.f && (path_rate <= 0.f || path_row_b || path_S >= 1), "rmsnorm_bwd_ls: bad mask arguments");
+  return rmsnorm_bwd_ls((const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, dw_accum, (const bf16_t*)y,
+                        (const bf16_t*)lam, (bf16_t*)dsc, dlam_accum, T, d, path_arg(path_rate, path_seed, path_S, path_row_b),
+                        gget_engine::elem_drop(elem_p, elem_seed, elem_rows), (hipStream_t)stream);
+}
 extern "C" int gget_op_rmsnorm_bwd_ls(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
                                       float* dw_accum, const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d,
                                       void* stream) {
-  GGET_REQUIRE(dy && x && w && rstd && dx && dw_accum && y && dsc && T >= 0, "rmsnorm_bwd_ls: null argument");
-  GGET_REQUIRE(d > 0 && d % 8 == 0 && d <= 2048, "rmsnorm_bwd_ls: d=%d unsupported", d);
-  return rmsnorm_bwd_ls((const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, dw_accum, (const bf16_t*)y,
-                        (const bf16_t*)lam, (bf16_t*)dsc, dlam_accum, T, d, PathDropArg{0.f, 0u, 1, nullptr}, ElemDropArg{0, 1.f, 0},
-                        (hipStream_t)stream);
+  return gget_op_rmsnorm_bwd_ls_drop(dy, x, w, rstd, dres, dx, dw_accum, y, lam, dsc, dlam_accum, T, d, 0.f, 0u, nullptr, 0.f, 0u, 1, nullptr,
+                                     stream);
 }
 extern "C" int gget_op_ce_full(const void* logits, int ld, const int32_t* labels, const int32_t* sel_tok, const float* sample_wgt, int S,
                                const int32_t* n_rows_dev, int n_rows_cap, int V, float* loss_sum, void* dlogits, float scale_base,
@@ -3187,16 +3254,28 @@ extern "C" int gget_op_scatter_rows_f32(const float* src, const int32_t* pool_ro
   GGET_REQUIRE(src && pool_row && dhidden && B > 0 && d > 0, "scatter_rows_f32: null argument or empty shape");
   return k_scatter_rows_f32(src, pool_row, dhidden, B, d, (hipStream_t)stream);
 }
-// (head dropout off - the ElemDropArg of evaluation mode; the masks are tested through the whole model)
+// (the _drop entries: head dropout from (elem_p, elem_seed, elem_rows) through gget_engine::elem_drop - the head kernels key the mask by the
+//  pooled row b and never read elem_rows; the plain entries are evaluation mode: they call the _drop ones with the dropout off)
+extern "C" int gget_op_head_linear_fwd_drop(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din,
+                                            int Dout, int layer, float elem_p, uint32_t elem_seed, const int32_t* elem_rows, void* stream) {
+  GGET_REQUIRE(x && a && w && y && B > 0 && Din > 0 && Dout > 0, "head_linear_fwd: null argument or empty shape");
+  GGET_REQUIRE(elem_p < 1.f, "head_linear_fwd: bad mask arguments");
+  return k_head_linear_fwd(x, a, w, bias, y, y32, B, Din, Dout, layer, gget_engine::elem_drop(elem_p, elem_seed, elem_rows), (hipStream_t)stream);
+}
 extern "C" int gget_op_head_linear_fwd(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din,
                                        int Dout, int layer, void* stream) {
-  GGET_REQUIRE(x && a && w && y && B > 0 && Din > 0 && Dout > 0, "head_linear_fwd: null argument or empty shape");
-  return k_head_linear_fwd(x, a, w, bias, y, y32, B, Din, Dout, layer, gget_engine::elem_drop(0.f, 0), (hipStream_t)stream);
+  return gget_op_head_linear_fwd_drop(x, a, w, bias, y, y32, B, Din, Dout, layer, 0.f, 0u, nullptr, stream);
+}
+extern "C" int gget_op_head_linear_bwd_drop(const float* dy, const void* x, const void* a, const void* w, float* dw, float* dbias, float* dx,
+                                            int B, int Din, int Dout, int layer, float elem_p, uint32_t elem_seed, const int32_t* elem_rows,
+                                            void* stream) {
+  GGET_REQUIRE(dy && x && a && w && dw && dx && B > 0 && Din > 0 && Dout > 0, "head_linear_bwd: null argument or empty shape");
+  GGET_REQUIRE(elem_p < 1.f, "head_linear_bwd: bad mask arguments");
+  return k_head_linear_bwd(dy, x, a, w, dw, dbias, dx, B, Din, Dout, layer, gget_engine::elem_drop(elem_p, elem_seed, elem_rows), (hipStream_t)stream);
 }
 extern "C" int gget_op_head_linear_bwd(const float* dy, const void* x, const void* a, const void* w, float* dw, float* dbias, float* dx,
                                        int B, int Din, int Dout, int layer, void* stream) {
-  GGET_REQUIRE(dy && x && a && w && dw && dx && B > 0 && Din > 0 && Dout > 0, "head_linear_bwd: null argument or empty shape");
-  return k_head_linear_bwd(dy, x, a, w, dw, dbias, dx, B, Din, Dout, layer, gget_engine::elem_drop(0.f, 0), (hipStream_t)stream);
+  return gget_op_head_linear_bwd_drop(dy, x, a, w, dw, dbias, dx, B, Din, Dout, layer, 0.f, 0u, nullptr, stream);
 }
 // batch layout and SMTP-head index kernels: the launchers of csrc/kernels.h as they are (tests/test_gpu_plan.py)
 extern "C" int gget_op_lengths(const int64_t* mask, const int64_t* ids, int ldF, int pad_id, int32_t* key_len, int32_t* pool_row, int B,

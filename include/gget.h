@@ -801,6 +801,42 @@ int gget_op_accum_layout(int d, int* copies, uint64_t* copy_stride);
  * gradient is the sum of the replicas. */
 int gget_op_rmsnorm_bwd_ls(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, float* dw_accum,
                            const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d, void* stream);
+/* The dropout / DropPath / LayerScale family with its masks on (tests/test_gpu_drop.py).  The mask arguments are the same everywhere:
+ *  - elem_p, elem_seed, elem_rows: element dropout.  Element (a, b) of stream s is dropped when the 24-bit hash of (elem_seed, s, a, b) is
+ *    BELOW (unsigned)(elem_p * 2^24); a kept one is multiplied by 1 / (1 - elem_p).  a = elem_rows[t] (int32 [T], the logical row of compact
+ *    row t) or t when elem_rows is NULL; elem_p <= 0: off.
+ *  - path_rate, path_seed, path_S, path_row_b: DropPath per SAMPLE path_row_b[t] (int32 [T]) or t / path_S when path_row_b is NULL: the
+ *    sample's rows are multiplied by 0 when hash24(path_seed, sample) * 2^-24 < path_rate, else by 1 / (1 - path_rate); path_rate <= 0: off.
+ * gget_op_ls_rmsnorm_fwd_drop: out = bf16(res + keep * bf16(lam * bf16(y * em))) (stream 50, b = the column), then the norm of out.
+ * gget_op_rmsnorm_bwd_ls_drop: dx, dw as gget_op_rmsnorm_bwd_ls; dsc = bf16(lam * keep * dx * em), dlam += sum_t keep * dx * bf16(y * em).
+ * gget_op_ls_fwd / gget_op_ls_bwd: the same residual add / its backward as kernels of their own (dy of ls_bwd = the dx above); dlam_accum
+ *   has the layout of gget_op_accum_layout or is NULL.
+ * gget_op_elem_dropout: x bf16 [T][n] (n % 8 == 0) in place, x = bf16(x * em(stream_id, row, column)); elem_p <= 0 leaves x untouched.
+ * gget_op_embed_*_drop: stream 48, a = row * F + f, b = the channel, on the gathered rows before the gate; with a mask the backward is always
+ *   the sorted scatter-add.  gget_op_head_linear_*_drop: stream 51 + layer, (a, b) = (b, j) of the activation a; elem_rows is not read. */
+int gget_op_ls_rmsnorm_fwd_drop(const void* res, const void* y, const void* lam, void* out, const void* w, void* xn, float* rstd, int T,
+                                int d, float eps, float elem_p, uint32_t elem_seed, const int32_t* elem_rows, float path_rate,
+                                uint32_t path_seed, int path_S, const int32_t* path_row_b, void* stream);
+int gget_op_rmsnorm_bwd_ls_drop(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, float* dw_accum,
+                                const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d, float elem_p, uint32_t elem_seed,
+                                const int32_t* elem_rows, float path_rate, uint32_t path_seed, int path_S, const int32_t* path_row_b,
+                                void* stream);
+int gget_op_ls_fwd(const void* res, const void* y, const void* lam, void* out, int T, int d, float elem_p, uint32_t elem_seed,
+                   const int32_t* elem_rows, float path_rate, uint32_t path_seed, int path_S, const int32_t* path_row_b, void* stream);
+int gget_op_ls_bwd(const void* dy, const void* y, const void* lam, void* dsc, float* dlam_accum, int T, int d, float elem_p,
+                   uint32_t elem_seed, const int32_t* elem_rows, float path_rate, uint32_t path_seed, int path_S, const int32_t* path_row_b,
+                   void* stream);
+int gget_op_elem_dropout(void* x, int64_t T, int n, uint32_t stream_id, float elem_p, uint32_t elem_seed, const int32_t* elem_rows,
+                         void* stream);
+int gget_op_embed_fwd_drop(const int64_t* ids, const void* emb, const void* gate, void* out, int T, int F, int ldF, int d, float elem_p,
+                           uint32_t elem_seed, const int32_t* elem_rows, void* stream);
+int gget_op_embed_bwd_drop(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb_accum, float* dgate_accum,
+                           int T, int F, int ldF, int d, int V, int pad_id, float elem_p, uint32_t elem_seed, const int32_t* elem_rows,
+                           void* stream);
+int gget_op_head_linear_fwd_drop(const void* x, void* a, const void* w, const void* bias, void* y, float* y32, int B, int Din, int Dout,
+                                 int layer, float elem_p, uint32_t elem_seed, const int32_t* elem_rows, void* stream);
+int gget_op_head_linear_bwd_drop(const float* dy, const void* x, const void* a, const void* w, float* dw, float* dbias, float* dx, int B,
+                                 int Din, int Dout, int layer, float elem_p, uint32_t elem_seed, const int32_t* elem_rows, void* stream);
 /* gget_op_ce_fwd_bwd with every argument of the launcher: row weight sample_wgt[sel_tok[row] / S] (f32, both NULL = 1) times the focal
  * weight (1 - p_label)^focal_gamma (0 = off); n = min(n_rows_cap, *n_rows_dev) rows (n_rows_dev NULL: n_rows_cap); loss_sum[0] = the
  * weighted sum of the row losses; dlogits bf16 [n_rows_cap, ld] (may be NULL) = (softmax - onehot) * weight * (mean_over_rows ? 1 / n :

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _drop_ref import model_path_keep as _path_keep  # the Python twin of path_keep() in csrc/engine.hip (tests/_drop_ref.py)
 from _util import ADAM, BASE_CASES, CLIP, FT_CASES, PT_CASES, ft_problem, load_case, loss_tolerance, record_error, rel_l2, tb
 from oracle import gget_oracle as O
 
@@ -270,23 +271,6 @@ def test_staged_backward_equals_monolithic():
     for off, cnt in e.buckets:
         cover[off: off + cnt] += 1
     assert int(cover.min()) == 1 and int(cover.max()) == 1
-
-
-def _path_keep(seed, layer, which, B, rate):
-    """Python twin of path_keep() in csrc/engine.hip."""
-    if rate <= 0:
-        return torch.ones(B)
-    M32 = 0xFFFFFFFF
-    s = (seed ^ ((0xD6E8FEB8 * (layer * 2 + which + 1)) & M32)) & M32
-    out = []
-    for b in range(B):
-        x = (s + b * 0x85EBCA77) & M32
-        x ^= x >> 16; x = (x * 0x7FEB352D) & M32
-        x ^= x >> 15; x = (x * 0x846CA68B) & M32
-        x ^= x >> 16
-        u = np.float32(x >> 8) * np.float32(1.0 / 16777216.0)
-        out.append(0.0 if u < np.float32(rate) else float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate))))
-    return torch.tensor(out)
 
 
 @pytest.mark.parametrize("layer_scale", [0.0, 1.0])
