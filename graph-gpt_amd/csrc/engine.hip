@@ -2888,7 +2888,13 @@ extern "C" int gget_op_smtp2d(const int64_t* ids_in, int ld_in, const int64_t* n
 extern "C" int gget_op_token_sample(const void* logits, int ld, int R, int V, int mode, float temperature, float top_p, int top_k,
                                    float alg_temp, uint32_t seed, float* conf, int64_t* tok, void* stream) {
   GGET_REQUIRE(logits && conf && tok && R >= 0 && V >= 1 && ld >= V && mode >= 0 && mode <= 2, "token_sample: bad arguments");
-  return k_token_sample(logits, ld, R, V, mode, temperature, top_p, top_k, alg_temp, seed, conf, tok, (hipStream_t)stream);
+  return k_token_sample(logits, ld, R, V, mode, temperature, top_p, top_k, alg_temp, seed, conf, tok, nullptr, 0, (hipStream_t)stream);
+}
+extern "C" int gget_op_token_sample_probs(const void* logits, int ld, int R, int V, int mode, float temperature, float top_p, int top_k,
+                                         float alg_temp, uint32_t seed, float* conf, int64_t* tok, float* probs, int ld_p, void* stream) {
+  GGET_REQUIRE(logits && conf && tok && R >= 0 && V >= 1 && ld >= V && mode >= 0 && mode <= 2, "token_sample_probs: bad arguments");
+  GGET_REQUIRE(!probs || ld_p >= V, "token_sample_probs: ld_p %d below V %d", ld_p, V);
+  return k_token_sample(logits, ld, R, V, mode, temperature, top_p, top_k, alg_temp, seed, conf, tok, probs, ld_p, (hipStream_t)stream);
 }
 extern "C" int gget_op_unmask_origin(int64_t* x, const int64_t* cand, int B, int N, float p_transfer, uint32_t seed, int mask_token_id,
                                      void* stream) {

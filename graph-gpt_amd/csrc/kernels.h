@@ -235,7 +235,7 @@ int k_smtp2d(const int64_t* ids_in, int ld_in, const int64_t* node_idx, int ld_n
              int B, int S, int F, float rate, float power, float replace_rate, int vocab, int global_mask, unsigned seed,
              hipStream_t st);
 int k_token_sample(const void* logits, int ld, int R, int V, int mode, float temperature, float top_p, int top_k, float alg_temp,
-                   unsigned seed, float* conf, int64_t* tok, hipStream_t st);
+                   unsigned seed, float* conf, int64_t* tok, float* probs, int ld_p, hipStream_t st);   // probs (fp32 [R, ld_p >= V], may be null): the final distribution of every row
 int k_unmask_origin(int64_t* x, const int64_t* cand, int B, int N, float p_transfer, unsigned seed, int mask_id, hipStream_t st);
 int k_unmask_origin_rows(int64_t* x, const int64_t* cand, int B, int N, const float* p_transfer, unsigned seed, int mask_id, hipStream_t st);
 int k_token_confidence(const void* logits, int ld, int R, int V, int mode, float* conf, int64_t* tok, hipStream_t st);

@@ -2463,7 +2463,7 @@ __global__ void __launch_bounds__(kBlock) token_confidence_kernel(const bf16_t* 
 __global__ void __launch_bounds__(kBlock) token_sample_kernel(const bf16_t* __restrict__ logits, int ld, int R, int V, int mode,
                                                               float temperature, float top_p, int top_k, float alg_temp,
                                                               unsigned seed, float* __restrict__ conf, int64_t* __restrict__ tok,
-                                                              int waves_per_block) {
+                                                              int waves_per_block, float* __restrict__ probs, int ld_p) {
   extern __shared__ float ts_lds[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (wv >= waves_per_block) return;
@@ -2513,6 +2513,9 @@ __global__ void __launch_bounds__(kBlock) token_sample_kernel(const bf16_t* __re
       __builtin_amdgcn_wave_barrier();
     }
     softmax_to_p();
+    if (probs) {   // test-only view of the distribution the candidate is drawn from (gget_op_token_sample_probs)
+      for (int c = lane; c < V; c += 64) probs[(size_t)row * ld_p + c] = p[c];
+    }
     // candidate
     int x0;
     float cf;
@@ -2557,7 +2560,7 @@ __global__ void __launch_bounds__(kBlock) token_sample_kernel(const bf16_t* __re
       x0 = i1;
       cf = m1;
     }
-    if (mode == 1) cf = m1 - m2;
+    if (mode == 1) cf = m1 - fmaxf(m2, 0.f);   // V = 1 has no second token: m2 is still its initial -1 there, the margin is p1
     if (mode == 2) {
       float ent = 0.f;
       for (int c = lane; c < V; c += 64) { const float v = p[c]; ent += v * __logf(v + 1e-10f); }
@@ -3601,14 +3604,14 @@ int k_token_confidence(const void* logits, int ld, int R, int V, int mode, float
 }
 
 int k_token_sample(const void* logits, int ld, int R, int V, int mode, float temperature, float top_p, int top_k, float alg_temp,
-                   unsigned seed, float* conf, int64_t* tok, hipStream_t st) {
+                   unsigned seed, float* conf, int64_t* tok, float* probs, int ld_p, hipStream_t st) {
   if (R == 0) return 0;
   GGET_REQUIRE(V >= 1 && V <= 8192, "token_sample: vocabulary %d out of range (1..8192: the row is filtered in LDS)", V);
   GGET_REQUIRE(temperature >= 0.f && alg_temp >= 0.f && top_k >= 0, "token_sample: negative temperature / alg_temp / top_k");
   const int waves = V <= 1024 ? kBlock / 64 : 1;
   const size_t lds = (size_t)waves * 2 * V * sizeof(float);
   hipLaunchKernelGGL(token_sample_kernel, dim3(grid_for(R, waves, 8192)), dim3(kBlock), lds, st, (const bf16_t*)logits, ld, R, V,
-                     mode, temperature, top_p, top_k, alg_temp, seed, conf, tok, waves);
+                     mode, temperature, top_p, top_k, alg_temp, seed, conf, tok, waves, probs, ld_p);
   GGET_LAUNCH_CHECK();
   return 0;
 }

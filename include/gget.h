@@ -592,6 +592,11 @@ int gget_op_token_confidence(const void* logits, int ld, int R, int V, int mode,
  * of (seed, stream, row) (graph-gpt_amd/generation.py holds the Python twin); V <= 8192. */
 int gget_op_token_sample(const void* logits, int ld, int R, int V, int mode, float temperature, float top_p, int top_k,
                          float alg_temp, uint32_t seed, float* conf, int64_t* tok, void* stream);
+/* test-only: gget_op_token_sample that also shows the distribution the candidate is drawn from - probs f32 [R, ld_p], ld_p >= V, takes
+ * every row's probabilities after the filters (a filtered token: +0); columns [V, ld_p) are not written.  probs NULL: nothing is written
+ * and conf / tok are gget_op_token_sample's. */
+int gget_op_token_sample_probs(const void* logits, int ld, int R, int V, int mode, float temperature, float top_p, int top_k,
+                               float alg_temp, uint32_t seed, float* conf, int64_t* tok, float* probs, int ld_p, void* stream);
 /* replaces: the alg = "origin" update of _batch_unmask_without_for_loop (src/utils/generation_utils.py:150-162): x[b][n] takes
  * cand[b][n] where it is <mask> and the cell's own uniform draw is below p_transfer. */
 int gget_op_unmask_origin(int64_t* x, const int64_t* cand, int B, int N, float p_transfer, uint32_t seed, int mask_token_id,
