@@ -4,6 +4,8 @@
 #include "../../include/gget.h"
 #include "common.h"
 
+inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
 // Small fp32 accumulators (norm weights, LayerScale, ...) exist in kAccumCopies copies, `stride` elements apart: a block
 // adds into copy blockIdx % copies (an atomic add of 512 blocks into ONE 768-float vector serialises in L2: that was
 // the whole cost of the RMSNorm backward), and the bf16 conversion sums the copies.
@@ -17,6 +19,11 @@ struct GgetSegment {
   uint64_t stride; // elements between copies
 };
 
+// the threshold rule of the element dropouts (common.h ElemDropArg): probability p -> 24-bit threshold and the kept elements' scale
+inline ElemDropArg elem_drop(float p, unsigned seed, const int32_t* rows = nullptr) {
+  if (p <= 0.f) return ElemDropArg{0, 1.f, 0, nullptr};
+  return ElemDropArg{(unsigned)(p * 16777216.0f), 1.0f / (1.0f - p), seed, rows};
+}
 int k_embed_fwd(const int64_t* ids, const void* emb, const void* gate, void* out, int T, int F, int ldF, int d,
                 hipStream_t st, ElemDropArg E = ElemDropArg{0, 1.f, 0});
 int k_elem_dropout(void* x, long T, int n, unsigned stream, ElemDropArg E, hipStream_t st);
@@ -40,6 +47,11 @@ inline size_t k_embed_bwd_ws_elems(size_t ncell, size_t V) { return 3 * V + 1 + 
 int k_embed_count(const int64_t* ids, void* cnt, int T, int F, int ldF, int ldc, int pad_id, hipStream_t st);
 inline bool k_embed_dense_ok(int V, bool gated) { return !gated && ((V + 63) / 64) * 64 <= 1024; }
 constexpr int kEmbDenseSplit = 8;   // K slices (fp32 slabs of V*d each) of that GEMM
+// the embedding backward in whichever form applies (engine.hip; its operator entry is in ops.hip): cnt_ws / slab_ws = the count matrix and
+// the kEmbDenseSplit slabs of the dense form, or NULL
+int embed_bwd(const int64_t* ids, const void* dx, const void* emb, const void* gate, float* demb, float* dgate, int T, int F,
+              int ldF, int d, int V, int pad_id, int32_t* sort_ws, void* cnt_ws, void* slab_ws, hipStream_t st, ElemDropArg E,
+              bool cnt_cleared = false);
 int k_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int T, int d, float eps, hipStream_t st);
 // dw_accum: fp32 [copies][copy_stride] accumulators (see GgetSegment); copies = 1 for a plain vector
 // reproducible mode: the scratch of the block-ordered weight-gradient sums (grown on demand; its users run in stream order)
@@ -53,6 +65,30 @@ int k_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rst
 // frozen prefix (gget_set_frozen).  Same accumulate-copies layout, same reproducible mode (menu().deterministic).
 int k_rmsnorm_dw(const void* dy, const void* x, const float* rstd, float* dw_accum, int T, int d, hipStream_t st, int copies = 1,
                  uint64_t copy_stride = 0);
+// Residual add as its own kernel (residual.hip): out = res + keep_b * (lam * y)
+//   lam  : LayerScale vector (utils_graphgpt.py:153-166) or nullptr (= 1)
+//   keep_b: DropPath / stochastic depth per SAMPLE (utils_graphgpt.py:64-66 = transformers BeitDropPath): 0 with
+//           probability `rate`, else 1/(1-rate); counter-based so backward regenerates it.
+struct PathDropArg { float rate; unsigned seed; int S; const int32_t* row_b; };   // row_b: sample index of every row (var-len token layout) or NULL (row / S)
+typedef PathDropArg PathDrop;
+#ifdef __HIPCC__
+__device__ __forceinline__ float path_keep(const PathDrop& D, long t) {
+  if (D.rate <= 0.f) return 1.f;
+  unsigned x = D.seed + (unsigned)(D.row_b ? D.row_b[t] : t / D.S) * 0x85EBCA77u;
+  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+  return (float)(x >> 8) * (1.0f / 16777216.0f) < D.rate ? 0.f : 1.0f / (1.0f - D.rate);
+}
+#endif
+// ... alone, fused with the RMSNorm behind it, its backward, and the RMSNorm backward fused with the backward of the branch behind it
+// (dlam / dlam_accum: kAccumCopies replicas of align_up(d, 128) floats, or nullptr)
+int k_ls_fwd(const bf16_t* res, const bf16_t* y, const bf16_t* lam, bf16_t* out, int T, int d, PathDrop D, ElemDropArg E, hipStream_t st);
+int k_ls_rmsnorm_fwd(const bf16_t* res, const bf16_t* y, const bf16_t* lam, bf16_t* out, const bf16_t* w, bf16_t* xn, float* rstd, int T,
+                     int d, float eps, PathDrop D, ElemDropArg E, hipStream_t st);
+int k_ls_bwd(const bf16_t* dy, const bf16_t* y, const bf16_t* lam, bf16_t* dsc, float* dlam, int T, int d, PathDrop D, ElemDropArg E,
+             hipStream_t st);
+int k_rmsnorm_bwd_ls(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* rstd, const bf16_t* dres, bf16_t* dx, float* dw_accum,
+                     const bf16_t* y, const bf16_t* lam, bf16_t* dsc, float* dlam_accum, int T, int d, PathDrop D, ElemDropArg E,
+                     hipStream_t st);
 int k_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H,
            int inverse, hipStream_t st);
 int k_rope_table(float* cos_tab, float* sin_tab, int max_pos, float theta, hipStream_t st);
@@ -61,6 +97,11 @@ int k_rope_range_table(const int64_t* pos, float* cos_t, float* sin_t, int64_t* 
                        hipStream_t st);
 int k_geglu_fwd(const void* gu, void* h, int T, int ff, hipStream_t st);
 int k_geglu_bwd(const void* gu, const void* dh, void* dgu, int T, int ff, hipStream_t st);
+// the gated-GELU MLP's two launches with the activation fused into the GEMM where the shape allows (engine.hip; operator entries in ops.hip)
+bool geglu_fusable(int d, int ff);
+int gateup_geglu(const bf16_t* x, const bf16_t* wgu, bf16_t* gu, bf16_t* hh, int T, int d, int ff, hipStream_t st);
+int down_dgrad_geglu(const bf16_t* dy, const bf16_t* wdown, const bf16_t* gu, bf16_t* dgu, bf16_t* dh_scratch, int T, int d, int ff,
+                     hipStream_t st);
 int k_lengths(const int64_t* mask, const int64_t* ids, int ldF, int pad_id, int32_t* key_len, int32_t* pool_row, int B,
               int S, hipStream_t st);
 // Var-len (padding-free) token layout of a right-padded batch: cu[b] = first compact row of sample b (exclusive scan of key_len, cu[B] =
@@ -142,7 +183,7 @@ inline size_t k_grad_sqnorm_ws_bytes() { return (16 + 1024) * sizeof(float); }
 struct GgetSqChunk { uint64_t off; uint64_t cnt; };
 int k_grad_sqnorm_chunks(const void* g, const GgetSqChunk* chunks_dev, int nchunks, const float* extra, int nextra, float* ws, hipStream_t st,
                          bool grad_f32 = false);
-// its chunk pass alone, the sharded step's (ZeRO-2, engine.hip gget_shard_*): per-chunk sums into out[slot[c]] (slot == nullptr: out[c]),
+// its chunk pass alone, the sharded step's (ZeRO-2, optimizer.hip gget_shard_*): per-chunk sums into out[slot[c]] (slot == nullptr: out[c]),
 // any number of chunks, no finishing pass - that is the one-block sum of the gathered partials in global chunk order (ws[0])
 int k_grad_sqnorm_partials(const void* g, const GgetSqChunk* chunks_dev, const int32_t* slot_dev, int nchunks, float* out, hipStream_t st,
                            bool grad_f32 = false);

@@ -3,7 +3,7 @@
 // kMenuRows is the one description of the knobs (INTEGRATION.md "Kernel-selection knobs" mirrors it row for row).  The process menu is
 // read from the environment once, when the library loads (menu.hip); gget_debug_set / gget_debug_get write and read it by key
 // afterwards.  A handle that carries a data-parallel menu (gget_set_dp_menu) overlays its fields on the process menu for the length of
-// each of its calls (engine.hip CallScope); menu() returns what the current call plans with.  The defaults are the measured best.
+// each of its calls (engine.h CallScope); menu() returns what the current call plans with.  The defaults are the measured best.
 #pragma once
 
 struct LaunchMenu {
@@ -31,7 +31,7 @@ struct LaunchMenu {
   int attn_stg128;          // S >= 512: dK / dV kernel with 128-row stages (0: 64)
   int attn_oproj;           // S <= 32: attention + o projection + residual + RMSNorm per sample (environment switch)
   int attn_oproj_off;       // ... the same form switched off at run time
-  // engine (engine.hip)
+  // engine (engine.hip; ls_norm_bwd_wide is read in residual.hip, occupy_fat in ops.hip)
   int head_sorted;          // SMTP head: the labelled cells sorted by slot
   int head_dense;           // SMTP head: dense projection of every selected row through all slots
   int head_tile;            // 0: 256-row slot tiles when d % 256 == 0, else 128; 128 / 256: forced

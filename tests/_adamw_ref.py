@@ -33,8 +33,8 @@ KBLOCK = 256                # csrc/kernels.hip kBlock
 SQNORM_BLOCKS = 1024        # kSqnormBlocks
 SLOTS_BLOCK = 1024          # kSlotsBlock
 SHARD_CHUNK = 4096          # include/gget.h GGET_SHARD_CHUNK
-SQ_TILES_PER_LAYER = 256    # csrc/engine.hip kSqTilesPerLayer
-WG_TILE = 192 * 192         # elements of one weight-gradient tile (csrc/engine.hip wg_tiles), summed by a block of 512 threads
+SQ_TILES_PER_LAYER = 256    # csrc/optimizer.hip kSqTilesPerLayer
+WG_TILE = 192 * 192         # elements of one weight-gradient tile (csrc/optimizer.hip wg_tiles), summed by a block of 512 threads
 WG_THREADS = 512
 _SLICE = 1 << 24            # elements per slice of a check (bounds the float64 temporaries)
 
@@ -107,7 +107,7 @@ def chain_chunks(n, layers):
     values over 512 threads: 72 serial additions, 6, 8 (waves).  The final block adds at most ceil(1024 / 256) chunk partials and
     layers x 256 / 256 tile partials per thread, then the 8-level tree.  The tile sums square the value AFTER its bf16 rounding
     (csrc/gemm.hip sq_add: bf2f(f2bf(v))) - the stored gradient, so no extra term."""
-    chunk = max(32768, _cdiv((n + 899) // 900, 128) * 128)      # (engine.hip cuts `other` <= n elements, the non-matrix share: an upper bound)
+    chunk = max(32768, _cdiv((n + 899) // 900, 128) * 128)      # (optimizer.hip cuts `other` <= n elements, the non-matrix share: an upper bound)
     in_block = max(8 * _cdiv(chunk // 8, KBLOCK) + 6 + KBLOCK // 64, WG_TILE // WG_THREADS + 6 + WG_THREADS // 64)
     return in_block + _cdiv(1024, KBLOCK) + _cdiv(layers * SQ_TILES_PER_LAYER, KBLOCK) + 8
 

@@ -60,9 +60,9 @@ on the 32-row shape, and the kernels reach 0.88 of the bounds here.)
 Where kernel classes differ in a count the larger is used (32-key stages; 5 u |lse| inside E for the forward, which has no conversion).
 Nothing here is fitted to the kernel: every constant is a count of roundings of the contract above.
 
-Pad rows.  The q | k | v weight-gradient GEMM of csrc/engine.hip (:1964, K = T rows) reads EVERY row of dqkv: on the padded grid the rows
+Pad rows.  The q | k | v weight-gradient GEMM of csrc/engine.hip (layer_backward, K = T rows) reads EVERY row of dqkv: on the padded grid the rows
 behind a sample's tokens (and packed padding rows) must be exact zeros - they are, given dout = 0 there and out / lse as the forward wrote
-them -; on the var-len layout the rows behind the last sample are zeroed once per step (:2063-2065) and no attention launch may write them.
+them -; on the var-len layout the rows behind the last sample are zeroed once per step (gget_backward_begin) and no attention launch may write them.
 """
 import math
 

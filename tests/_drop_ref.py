@@ -1,4 +1,4 @@
-"""The dropout / DropPath / LayerScale family - the counter hashes elem_drop_mul (csrc/common.h) and path_keep (csrc/engine.hip) and every
+"""The dropout / DropPath / LayerScale family - the counter hashes elem_drop_mul (csrc/common.h) and path_keep (csrc/kernels.h) and every
 kernel that applies them in the forward and regenerates them from coordinates in the backward: numpy twins of the two hashes, seeded inputs,
 float64 statements of every operation on the bf16 / fp32 inputs the kernel gets, the per-element bounds and the checks that hold an
 implementation to them.  tests/test_gpu_drop.py feeds the checks with the HIP kernels' outputs, tests/test_drop_reference.py with the fp32
@@ -114,7 +114,7 @@ def path_keep(seed, sample, rate):
 
 
 def model_path_keep(seed, layer, which, B, rate):
-    """Python twin of path_keep() in csrc/engine.hip behind the engine's seed derivation per (layer, branch): the multiplier of each of the B
+    """Python twin of path_keep() in csrc/kernels.h behind the engine's seed derivation per (layer, branch): the multiplier of each of the B
     samples (what tests/test_gpu_model.py feeds the oracle)."""
     if rate <= 0:
         return torch.ones(B)

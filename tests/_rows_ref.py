@@ -1,5 +1,5 @@
 """The two row-reduction kernel families of every pre-training step - RMSNorm (csrc/kernels.hip K4 and the LayerScale-fused forms of
-csrc/engine.hip) and the cross-entropy (K14): seeded inputs, float64 statements of every operation on the bf16 / fp32 inputs the kernel
+csrc/residual.hip) and the cross-entropy (K14): seeded inputs, float64 statements of every operation on the bf16 / fp32 inputs the kernel
 gets, the per-element error bounds and the checks that hold an implementation to them.  tests/test_gpu_rows.py feeds the checks with the
 HIP kernels' outputs, tests/test_rows_reference.py with the fp32 CPU statements below (which must pass) and with planted faults (which
 must not).

@@ -162,17 +162,17 @@ def test_launch_constants_match_the_sources():
     fails here and not silently in the norm bound"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = lambda *p: open(os.path.join(root, *p)).read()
-    kernels, engine, gemm, header = (src("graph-gpt_amd", "csrc", f) for f in ("kernels.hip", "engine.hip", "gemm.hip", "kernels.h"))
+    kernels, optimizer, gemm, header = (src("graph-gpt_amd", "csrc", f) for f in ("kernels.hip", "optimizer.hip", "gemm.hip", "kernels.h"))
     const = lambda text, name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
     assert const(kernels, "kBlock") == R.KBLOCK
     assert const(kernels, "kSqnormBlocks") == R.SQNORM_BLOCKS
     assert const(kernels, "kSlotsBlock") == R.SLOTS_BLOCK
-    assert const(engine, "kSqTilesPerLayer") == R.SQ_TILES_PER_LAYER
+    assert const(optimizer, "kSqTilesPerLayer") == R.SQ_TILES_PER_LAYER
     assert const(header, "kAdamwItemElems") == 8 * R.KBLOCK
     assert int(re.search(r"#define GGET_SHARD_CHUNK (\d+)", src("include", "gget.h")).group(1)) == R.SHARD_CHUNK
     # the chunk rule of the norm's table, the cap of that table, the tile of the grouped weight-gradient launch and its eight waves
-    assert "std::max<uint64_t>(32768, align_up((other + 899) / 900, 128))" in engine and "chunks.size() <= 1024" in engine
-    assert "/ (192 * 192)" in engine and R.WG_TILE == 192 * 192
+    assert "std::max<uint64_t>(32768, align_up((other + 899) / 900, 128))" in optimizer and "chunks.size() <= 1024" in optimizer
+    assert "/ (192 * 192)" in optimizer and R.WG_TILE == 192 * 192
     assert "for (int w = 0; w < 8; ++w) t += red[w];" in gemm and R.WG_THREADS == 8 * 64
     # the loop shapes the chains count: eight squares per vector, lanes by wave_sum, waves by thread 0, a halving tree
     assert kernels.count("for (int e = 0; e < 8; ++e) s += v[e] * v[e];") == 3

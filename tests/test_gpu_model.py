@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from _drop_ref import model_path_keep as _path_keep  # the Python twin of path_keep() in csrc/engine.hip (tests/_drop_ref.py)
+from _drop_ref import model_path_keep as _path_keep  # the Python twin of path_keep() in csrc/kernels.h (tests/_drop_ref.py)
 from _util import ADAM, BASE_CASES, CLIP, FT_CASES, PT_CASES, ft_problem, load_case, loss_tolerance, record_error, rel_l2, tb
 from oracle import gget_oracle as O
 
@@ -1079,7 +1079,7 @@ def test_c3_training_mode_dropouts_exact_mask():
 @pytest.mark.gpu
 @pytest.mark.parametrize("width", [512, 768, 1024])
 def test_ls_norm_backward_lean_form_matches_the_wide_form(width):
-    """The fused RMSNorm + LayerScale / DropPath backward has two lane mappings (engine.hip: rmsnorm_bwd_ls4_kernel - 8-byte pieces, all
+    """The fused RMSNorm + LayerScale / DropPath backward has two lane mappings (residual.hip: rmsnorm_bwd_ls4_kernel - 8-byte pieces, all
     lanes busy, d = 512 / 768 / 1024 - and the 16-byte-chunk form of every other width): same expressions per element, another fp32 order
     of the row's dot product.  Same batch, same masks (LayerScale, stochastic depth, mlp_dropout, var-len rows): equal loss (the forward
     is not involved), gradients equal up to rounding flips."""
