@@ -194,6 +194,10 @@ SIGNATURES = {
     "gget_op_raw_blend": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp]),
     "gget_op_raw_tok_grad": (i32, [vp, vp, vp, i32, i32, vp]),
     "gget_op_gemm_indexed": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
+    "gget_op_gemm_dyn": (i32, [i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
+    "gget_op_gemm_grouped_slab": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
+    "gget_op_slab_reduce": (i32, [vp, i64, i32, vp, u64, i32, vp]),
+    "gget_op_slab_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),
     "gget_op_rank_metrics_workspace": (C.c_size_t, [i32, i32]),
     "gget_op_rank_metrics": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "gget_op_link_hits_workspace": (C.c_size_t, [i32]),
@@ -261,6 +265,26 @@ def gemm_grouped(lib, mode, problems, stream):
     ptr = lambda k: PA(*[p[k].data_ptr() for p in problems])
     num = lambda k: IA(*[int(p[k]) for p in problems])
     return lib.gget_op_gemm_grouped(mode, n, ptr(0), ptr(1), ptr(2), num(3), num(4), num(5), num(6), num(7), num(8), stream)
+
+
+def gemm_grouped_slab(lib, mode, problems, slab_stride, split_k, stream):
+    """problems as for gemm_grouped, C fp32: one split-K launch into slabs `slab_stride` elements apart (GGET_EPI_SLAB_F32)."""
+    n = len(problems)
+    PA, IA = vp * n, i32 * n
+    ptr = lambda k: PA(*[p[k].data_ptr() for p in problems])
+    num = lambda k: IA(*[int(p[k]) for p in problems])
+    return lib.gget_op_gemm_grouped_slab(mode, n, ptr(0), ptr(1), ptr(2), num(3), num(4), num(5), num(6), num(7), num(8), int(slab_stride),
+                                         int(split_k), stream)
+
+
+SLAB_PLAN_LM_HEAD, SLAB_PLAN_SHED_QKVO, SLAB_PLAN_SHED_O, SLAB_PLAN_QKVO = 0, 1, 2, 3   # include/gget.h GGET_SLAB_PLAN_*
+
+
+def slab_plan(which: int, d: int, V: int, T: int) -> int:
+    """K slices the engine's backward asks for under the current launch menu (gget_op_slab_plan)."""
+    v = i32()
+    check(load().gget_op_slab_plan(int(which), int(d), int(V), int(T), C.byref(v)))
+    return int(v.value)
 PROBLEM_SINGLE_LABEL, PROBLEM_REGRESSION_L1, PROBLEM_REGRESSION_MSE, PROBLEM_MULTI_LABEL, PROBLEM_AUC = 0, 1, 2, 3, 4
 PROBLEM_TOKEN_CE_INTRA = 6   # loss_type = "token_ce_intra": as token_ce, logits = 20 <h^_s, h^_{cls_idx + c}> inside every sample
 PROBLEM_TOKEN_CE = 5   # loss_type = "token_ce": score + cross-entropy on every labelled row, logits [B,S,C]

@@ -325,3 +325,10 @@ struct CallScope {
 extern const int kSqTilesPerLayer;
 long wg_tiles(int d, int ff);
 int upload_sq_chunks(gget_engine* h);
+
+// K slices of the backward's split-K slab launches (engine.hip), each fitted to one round of gget_gemm_num_cu() CUs under the menu of the
+// calling thread: the lm_head weight gradient; q|k|v|o (with_qkv) or o alone when they are shed from the grouped weight-gradient launch;
+// q|k|v + o at a width with d % 192 != 0.  The test-only gget_op_slab_plan (ops.hip) returns exactly these.
+int lm_wgrad_split(int V, int d);
+int shed_wgrad_split(bool with_qkv, int d, int T);
+int qkvo_wgrad_split(int T);

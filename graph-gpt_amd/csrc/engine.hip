@@ -44,6 +44,32 @@ int fit_split(int tiles, int want) {
   return s;
 }
 
+}  // namespace
+
+// The K slices of the engine's split-K slab launches (declared in engine.h: the backward below and the test-only gget_op_slab_plan of
+// ops.hip both call these, so a test runs the engine's numbers).
+// lm_head weight gradient [V, d], K = Lm on the device: 256 x 128 tiles from 160 tile-slices on, 128 x 128 below (gemm.hip launch_shape)
+int lm_wgrad_split(int V, int d) {
+  const int t_big = ((V + 255) / 256) * ((d + 127) / 128), t_small = ((V + 127) / 128) * ((d + 127) / 128);
+  int split = fit_split(t_big, kLmSplit);
+  if (t_big * split < 160) split = fit_split(t_small, kLmSplit);
+  return split;
+}
+// q|k|v|o (with_qkv) or o alone, shed from the grouped weight-gradient launch when a data-parallel run reserves CUs (d % 192 == 0)
+int shed_wgrad_split(bool with_qkv, int d, int T) {
+  const int max_slabs = with_qkv ? kWgSplit : 4 * kWgSplit;
+  const int rows_out = with_qkv ? 4 * d : d;
+  const int t_big = ((rows_out + 255) / 256) * ((d + 127) / 128), t_small = ((rows_out + 127) / 128) * ((d + 127) / 128);
+  int split = fit_split(t_big, max_slabs);
+  if (t_big * split < 160) split = fit_split(t_small, max_slabs);           // (gemm.hip launch_shape: 128 x 128 tiles below 160 tile-slices)
+  while (split > 1 && (T + 63) / 64 < 4 * split) --split;                   // (at least four 64-deep K-tiles per slice)
+  return split;
+}
+// q|k|v + o of a width that is no 192 x 192 grid (d % 192 != 0)
+int qkvo_wgrad_split(int T) { return T >= kWgSplit * 1024 ? kWgSplit : 1; }
+
+namespace {
+
 // the contrastive kind is the pre-train model with one more head: whatever is said of the pre-train kind holds for it
 inline bool is_pretrain(const gget_config_t& c) { return c.kind == GGET_KIND_PRETRAIN || c.kind == GGET_KIND_PRETRAIN_CL; }
 inline bool has_cl(const gget_config_t& c) { return c.kind == GGET_KIND_PRETRAIN_CL; }
@@ -1310,12 +1336,7 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
       float* wg = h->wsp<float>(w.wg32);
       const bool with_qkv = n_grouped == 2;
       const long slab = with_qkv ? (long)4 * d * d : (long)d * d;
-      const int max_slabs = with_qkv ? kWgSplit : 4 * kWgSplit;
-      const int rows_out = with_qkv ? 4 * d : d;
-      const int t_big = ((rows_out + 255) / 256) * ((d + 127) / 128), t_small = ((rows_out + 127) / 128) * ((d + 127) / 128);
-      int split = fit_split(t_big, max_slabs);
-      if (t_big * split < 160) split = fit_split(t_small, max_slabs);           // (gemm.hip launch_shape: 128 x 128 tiles below 160 tile-slices)
-      while (split > 1 && (T + 63) / 64 < 4 * split) --split;                   // (at least four 64-deep K-tiles per slice)
+      const int split = shed_wgrad_split(with_qkv, d, T);
       GemmGroup go;
       memset(&go, 0, sizeof(go));
       if (with_qkv) {
@@ -1349,7 +1370,7 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
     g.count = 2;
     g.p[0] = GemmProblem{dqkv, h->wsp<bf16_t>(lw.xn1), wg, nullptr, 3 * d, d, T, 3 * d, d, d, nullptr, nullptr, 0, 0, slab};
     g.p[1] = GemmProblem{dy_o, h->wsp<bf16_t>(lw.attn), wg + (size_t)3 * d * d, nullptr, d, d, T, d, d, d, nullptr, nullptr, 0, 0, slab};
-    const int split = T >= kWgSplit * 1024 ? kWgSplit : 1;
+    const int split = qkvo_wgrad_split(T);
     if (int e = gget_gemm_launch(GGET_GEMM_TN, GGET_EPI_SLAB_F32, g, split, st)) return e;
     if (int e = k_slab_reduce(wg, slab, split, h->G + lo.wqkv, (size_t)4 * d * d, st)) return e;
   }
@@ -1438,9 +1459,7 @@ extern "C" int gget_backward_begin(gget_handle_t h, float loss_scale, void* stre
       memset(&g, 0, sizeof(g));
       g.count = 1;
       g.p[0] = GemmProblem{dlog, h->wsp<bf16_t>(w.Hl), slabs, nullptr, V, d, T * n, Vp, d, d, nullptr, counts + 1, 0, 0, slab};
-      // (256 x 128 tiles from 160 tile-slices on, 128 x 128 below - gemm.hip launch_shape)
-      int lm_split = fit_split(((V + 255) / 256) * ((d + 127) / 128), kLmSplit);
-      if (((V + 255) / 256) * ((d + 127) / 128) * lm_split < 160) lm_split = fit_split(((V + 127) / 128) * ((d + 127) / 128), kLmSplit);
+      const int lm_split = lm_wgrad_split(V, d);
       if (int e = gget_gemm_launch(GGET_GEMM_TN, GGET_EPI_SLAB_F32, g, lm_split, st)) return e;
       if (int e = k_slab_reduce(slabs, slab, lm_split, h->G + h->plan.lm, (size_t)V * d, st)) return e;
     }

@@ -23,6 +23,11 @@ struct GemmProblem {
   const int64_t* rope_pos;  // [M] or nullptr => position = row % rope_S
   int rope_S, rope_cols;
   int k_pad_zero;           // with k_dev: rows k_dev..round_up(k_dev, 64) of A are zero and those of B finite (whole K-tiles allowed)
+  // Counts of zero (a step without a labelled cell; tests/test_gpu_head_gemm.py):
+  //   *m_dev == 0                   C is untouched (no tile passes the row test);
+  //   EPI_SLAB_F32, *k_dev == 0     no slab is written - the caller clears what it sums (as for every slice past the end of a short K);
+  //   plain epilogues, *k_dev == 0  C is ZEROS in both kernels: gemm_kernel's slice 0 stores its zero accumulators, the persistent kernel
+  //                                 runs K-tile 0 - so with k_pad_zero the contract at count 0 is that K-tile 0 of A is zero (B finite).
   // EPI_GEGLU_FWD (NT, B = [gate rows | up rows] = [2 ff][K]): C = gu [M][2 ff] (pre-activations, kept for the backward),
   //   C2 = h [M][ff] = bf16(gelu(gate)) * up ; N = 2 ff.  EPI_GEGLU_BWD (the dh = dy W_down GEMM, N = ff): the epilogue reads
   //   G = gu [M][2 ff] and writes C = dgu [M][2 ff] = (dh * up * gelu'(gate) | dh * gelu(gate)); dh itself is never stored.

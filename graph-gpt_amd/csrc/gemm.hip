@@ -710,7 +710,9 @@ __global__ void __launch_bounds__(WM * WN * 64, (WM * WN) / 4) gemm_kernel(const
   const int per = (ktiles + gridDim.y - 1) / gridDim.y;
   const int kbeg = blockIdx.y * per * 64;
   const int kend = min(K, kbeg + per * 64);
-  if (kbeg >= kend) return;
+  // an empty slice writes nothing - except slice 0 of a plain epilogue, which owns C: a device-side K of 0 (a step without a labelled
+  // cell) stores the zero accumulators, as the persistent kernel does (gemm.h, k_pad_zero); slabs and atomics are cleared by the caller
+  if (kbeg >= kend && (blockIdx.y > 0 || EPI == GGET_EPI_SLAB_F32 || EPI == GGET_EPI_ATOMIC_F32)) return;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -1,8 +1,9 @@
 // libgget_hip.so - operator-level entry points (gget_op_*, gget_debug_occupy): the launchers of kernels.h / gemm.h behind the C ABI, for
-// tests and tools.  None of them takes a handle: this file does not see the engine object.
+// tests and tools.  None of them takes a handle: of the engine this file uses only the split-K rules that engine.h declares (gget_op_slab_plan).
 #include <string.h>
 
 #include "common.h"
+#include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
 
@@ -81,6 +82,48 @@ extern "C" int gget_op_gemm_grouped(int mode, int count, const void* const* A, c
     p.M = M[i]; p.N = N[i]; p.K = K[i]; p.lda = lda[i]; p.ldb = ldb[i]; p.ldc = ldc[i];
   }
   return gget_gemm_launch(mode, GGET_EPI_NONE, g, 1, (hipStream_t)stream);
+}
+// ---- test-only: the device-sized and split-K slab launches of the SMTP head and the shed weight gradients (include/gget.h) ----
+extern "C" int gget_op_gemm_dyn(int mode, int epilogue, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                                const int32_t* m_dev, const int32_t* k_dev, int k_pad_zero, int split_k, const int32_t* c_rows, void* stream) {
+  GGET_REQUIRE(A && B && C && M >= 0 && N > 0 && K >= 0, "gemm_dyn: bad arguments");
+  GGET_REQUIRE(epilogue == GGET_EPI_NONE || epilogue == GGET_EPI_SLAB_F32, "gemm_dyn: the plain or the fp32 slab epilogue");
+  GGET_REQUIRE(!k_pad_zero || k_dev, "gemm_dyn: k_pad_zero needs k_dev");
+  return gget_gemm_single(mode, epilogue, A, B, C, nullptr, M, N, K, lda, ldb, ldc, m_dev, k_dev, split_k, (hipStream_t)stream, k_pad_zero != 0,
+                          c_rows);
+}
+extern "C" int gget_op_gemm_grouped_slab(int mode, int count, const void* const* A, const void* const* B, void* const* Cs, const int* M,
+                                         const int* N, const int* K, const int* lda, const int* ldb, const int* ldc, int64_t slab_stride,
+                                         int split_k, void* stream) {
+  GGET_REQUIRE(count >= 1 && count <= GGET_MAX_GROUP && A && B && Cs && M && N && K && lda && ldb && ldc && slab_stride > 0 && split_k >= 1,
+               "gemm_grouped_slab: bad arguments");
+  GemmGroup g;
+  memset(&g, 0, sizeof(g));
+  g.count = count;
+  for (int i = 0; i < count; ++i) {
+    GemmProblem& p = g.p[i];
+    p.A = static_cast<const bf16_t*>(A[i]); p.B = static_cast<const bf16_t*>(B[i]); p.C = Cs[i];
+    p.M = M[i]; p.N = N[i]; p.K = K[i]; p.lda = lda[i]; p.ldb = ldb[i]; p.ldc = ldc[i];
+    p.slab_stride = (long)slab_stride;
+  }
+  return gget_gemm_launch(mode, GGET_EPI_SLAB_F32, g, split_k, (hipStream_t)stream);
+}
+extern "C" int gget_op_slab_reduce(const float* slabs, int64_t slab_stride, int nslab, void* dst, uint64_t n, int f32_out, void* stream) {
+  GGET_REQUIRE(slabs && dst && nslab >= 1 && n % 4 == 0 && slab_stride % 4 == 0 && (nslab == 1 || slab_stride >= (int64_t)n),
+               "slab_reduce: bad arguments (n and slab_stride are multiples of 4)");
+  if (n == 0) return 0;
+  return k_slab_reduce(slabs, (long)slab_stride, nslab, dst, (size_t)n, (hipStream_t)stream, f32_out != 0);
+}
+extern "C" int gget_op_slab_plan(int which, int d, int V, int T, int* split) {
+  GGET_REQUIRE(split && d > 0 && V > 0 && T >= 0, "slab_plan: bad arguments");
+  switch (which) {
+    case GGET_SLAB_PLAN_LM_HEAD: *split = lm_wgrad_split(V, d); return 0;
+    case GGET_SLAB_PLAN_SHED_QKVO: *split = shed_wgrad_split(true, d, T); return 0;
+    case GGET_SLAB_PLAN_SHED_O: *split = shed_wgrad_split(false, d, T); return 0;
+    case GGET_SLAB_PLAN_QKVO: *split = qkvo_wgrad_split(T); return 0;
+  }
+  gget_set_error("slab_plan: unknown launch %d", which);
+  return 2;
 }
 extern "C" int gget_op_qkv_rope(const void* x, const void* wqkv, void* qkv, const float* cos_tab, const float* sin_tab,
                                 const int64_t* position_ids, int T, int S, int d, void* stream) {

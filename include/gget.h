@@ -989,6 +989,36 @@ int gget_op_gemm_indexed(int mode, const void* A, const void* B, void* C, int M_
                          const int32_t* m_dev, const int32_t* a_rows, const int32_t* b_tile_off, int b_tile_rows, const int32_t* c_rows,
                          void* stream);
 
+/* ---- test-only entries of the device-sized and split-K slab GEMM launches (the SMTP head, the shed weight gradients): the launcher with
+ * every argument, no arithmetic of their own (tests/test_gpu_head_gemm.py against tests/_headgemm_ref.py) ---- */
+/* One problem through gget_gemm_single, epilogue GGET_EPI_NONE (C bf16 [M][ldc]) or GGET_EPI_SLAB_F32 (C fp32 [split_k][M][ldc]).  M and K are
+ * CAPACITIES: the host sizes the grid for them, the kernel reads the counts.
+ *   m_dev   rows m >= min(M, *m_dev) are neither read nor stored (*m_dev == 0: C is untouched); NULL = M
+ *   k_dev   the reduction runs over K rows [0, min(K, *k_dev)); NULL = K.  *k_dev == 0: the plain epilogue stores ZEROS (both kernels), the slab
+ *           epilogue writes no slab (the caller clears what it sums).
+ *   k_pad_zero (with k_dev) allows the persistent kernel when K % 64 == 0: it reads whole 64-row K-tiles up to round_up(*k_dev, 64), at least
+ *           one, so rows [*k_dev, max(64, round_up(*k_dev, 64))) of A must be zero and those of B finite; without it (or K % 64 != 0) the
+ *           non-persistent kernel zero-fills its K tail and reads nothing at or behind *k_dev
+ *   split_k K slices of a slab launch: ktiles = ceil(K' / 64) over the K' actually reduced, per = ceil(ktiles / split_k), slice s owns K rows
+ *           [64 s per, min(K', 64 (s + 1) per)) and writes slab s; slabs >= ceil(ktiles / per) are NOT written
+ *   c_rows  (plain epilogue) row m is stored at row c_rows[m] of C, a negative entry means the row is not stored; NULL = row m */
+int gget_op_gemm_dyn(int mode, int epilogue, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                     const int32_t* m_dev, const int32_t* k_dev, int k_pad_zero, int split_k, const int32_t* c_rows, void* stream);
+/* up to 4 problems of one mode in ONE split-K launch with GGET_EPI_SLAB_F32 into slabs that share `slab_stride` (fp32 elements between the
+ * slabs of consecutive K slices): problem i's slice s lands at C[i] + s slab_stride, [M[i]][ldc[i]].  How the engine issues the q|k|v and o
+ * weight gradients it sheds from the grouped launch (C = wg and wg + 3 d^2, slab_stride = 4 d^2). */
+int gget_op_gemm_grouped_slab(int mode, int count, const void* const* A, const void* const* B, void* const* C, const int* M, const int* N,
+                              const int* K, const int* lda, const int* ldb, const int* ldc, int64_t slab_stride, int split_k, void* stream);
+/* dst[i] = bf16_rne(slabs[i] + slabs[slab_stride + i] + ... ) for i < n, summed in slab order in fp32 (f32_out = 0: dst bf16, overwritten), or
+ * dst[i] += that sum (f32_out = 1: dst fp32, an accumulator).  n % 4 == 0, slab_stride % 4 == 0; elements at or behind n are untouched. */
+int gget_op_slab_reduce(const float* slabs, int64_t slab_stride, int nslab, void* dst, uint64_t n, int f32_out, void* stream);
+/* the K slices the engine's backward asks for (csrc/engine.h: the same host functions), under the launch menu of the calling thread */
+#define GGET_SLAB_PLAN_LM_HEAD 0   /* lm_head weight gradient [V, d] */
+#define GGET_SLAB_PLAN_SHED_QKVO 1 /* q|k|v + o shed from the grouped weight-gradient launch (d % 192 == 0, CUs reserved), K = T */
+#define GGET_SLAB_PLAN_SHED_O 2    /* o alone shed from it */
+#define GGET_SLAB_PLAN_QKVO 3      /* q|k|v + o at d % 192 != 0 */
+int gget_op_slab_plan(int which, int d, int V, int T, int* split);
+
 /* ------------------------------------------------------------------------------------------
  * Rank metrics of the multi-label evaluation pass (csrc/metrics.hip; the Python surface is graph-gpt_amd/metrics.py rank_metrics).
  * replaces: MultiLabelClassificationMetrics.compute (src/utils/metrics_utils.py:112-114: torcheval BinaryAUROC over num_labels tasks),
