@@ -34,6 +34,11 @@ class GgetParamInfo(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("ndim", i32), ("shape", i64 * 2), ("offset", u64), ("layer", i32)]
 
 
+class GgetGroupItem(C.Structure):
+    """gget_group_item_t: one work item of a grouped optimizer step (gget_group_plan)"""
+    _fields_ = [("off", u64), ("cnt", u64), ("lr_scale", f32), ("wd_scale", f32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/gget.h
 SIGNATURES = {
     "gget_last_error": (cp, []),
@@ -79,6 +84,12 @@ SIGNATURES = {
     "gget_shard_sqnorm_partials": (i32, [vp, vp, vp]),
     "gget_shard_allgather_async": (i32, [vp, i32, vp, vp]),
     "gget_adamw_step_sharded": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp]),
+    "gget_set_param_scales": (i32, [vp, C.POINTER(f32), C.POINTER(f32), i32]),
+    "gget_param_scales": (i32, [vp, C.POINTER(f32), C.POINTER(f32), i32]),
+    "gget_plan_param_count": (i32, [C.POINTER(GgetConfig)]),
+    "gget_plan_param_info": (i32, [C.POINTER(GgetConfig), i32, C.POINTER(GgetParamInfo)]),
+    "gget_group_plan": (i32, [C.POINTER(GgetConfig), C.POINTER(f32), C.POINTER(f32), i32, i32, i32, i32, C.POINTER(GgetGroupItem), i32,
+                              C.POINTER(i32)]),
     "gget_head_counts": (i32, [vp, C.POINTER(i32 * 2), vp]),
     "gget_head_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i32)]),
     "gget_hidden_states": (i32, [vp, C.POINTER(vp)]),

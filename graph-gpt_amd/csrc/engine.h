@@ -97,6 +97,7 @@ inline int bucket_of(int layer, int L) { return layer == L ? 0 : layer < 0 ? L +
 int check_cfg(const gget_config_t* c);
 Plan make_plan(const gget_config_t& c);
 std::vector<std::pair<uint64_t, uint64_t>> bucket_ranges(const gget_config_t& cfg, const Plan& plan);
+void fill_param_info(const ParamRec& p, gget_param_info_t* out);     // (gget_param_info and its handle-free twin gget_plan_param_info)
 
 // ZeRO-2 shard plan of one bucket (include/gget.h gget_shard_plan): `world` equal body slices of slice = floor(cnt / (world C)) C elements,
 // rank r owning [off + r slice, off + (r + 1) slice); the tail [off + world slice, off + cnt) (< world C elements) is all-reduced and updated
@@ -105,13 +106,15 @@ struct ShardBucket { uint64_t off, cnt, slice, tail_off, tail_cnt; };
 
 // The work list of an optimizer step that does not run over the whole arena (a frozen prefix, a rank's shard), one device allocation: the
 // AdamW / EMA work items, the chunks the norm sums and - the sharded form - the slot of each of those chunks in the gathered partial vector
-// (chunk_slot) and of every chunk of the global grid (slot_of)
+// (chunk_slot) and of every chunk of the global grid (slot_of); with parameter groups (gget_set_param_scales) the items are cut at every
+// boundary where a scale changes and `scales` holds {lr_scale, wd_scale} per item - else it is null
 struct OptWork {
   unsigned char* tab = nullptr;
   const GgetSqChunk* items = nullptr;
   const GgetSqChunk* chunks = nullptr;
   const int32_t* chunk_slot = nullptr;
   const int32_t* slot_of = nullptr;
+  const float* scales = nullptr;
   int nitems = 0, nchunks = 0, nglobal = 0;
   int reset() {
     unsigned char* t = tab;
@@ -120,12 +123,13 @@ struct OptWork {
     return 0;
   }
   int upload(const std::vector<GgetSqChunk>& it, const std::vector<GgetSqChunk>& ch, const std::vector<int32_t>& ch_slot = {},
-             const std::vector<int32_t>& global_slot = {}) {
+             const std::vector<int32_t>& global_slot = {}, const std::vector<float>& item_scales = {}) {
     if (int e = reset()) return e;
     const size_t b_it = it.size() * sizeof(GgetSqChunk), b_ch = ch.size() * sizeof(GgetSqChunk);
     const size_t b_cs = ch_slot.size() * sizeof(int32_t), b_gs = global_slot.size() * sizeof(int32_t);
+    const size_t b_sc = item_scales.size() * sizeof(float);     // (2 per item, or none)
     if (b_it + b_ch + b_cs + b_gs == 0) return 0;
-    GGET_HIP_CHECK(hipMalloc(&tab, b_it + b_ch + b_cs + b_gs));
+    GGET_HIP_CHECK(hipMalloc(&tab, b_it + b_ch + b_cs + b_gs + b_sc));
     items = reinterpret_cast<const GgetSqChunk*>(tab);
     chunks = items + it.size();
     chunk_slot = reinterpret_cast<const int32_t*>(chunks + ch.size());
@@ -137,12 +141,28 @@ struct OptWork {
     GGET_HIP_CHECK(put(chunks, ch.data(), b_ch));
     GGET_HIP_CHECK(put(chunk_slot, ch_slot.data(), b_cs));
     GGET_HIP_CHECK(put(slot_of, global_slot.data(), b_gs));
+    if (b_sc) {
+      scales = reinterpret_cast<const float*>(slot_of + global_slot.size());
+      GGET_HIP_CHECK(put(scales, item_scales.data(), b_sc));
+    }
     nitems = (int)it.size();
     nchunks = (int)ch.size();
     nglobal = (int)global_slot.size();
     return 0;
   }
 };
+
+// [offset, count) of the trainable share of the bucket [lo, hi) (gget_engine::bucket_train_range; frozen < 0 = the bucket itself)
+inline std::pair<uint64_t, uint64_t> bucket_train_share(std::pair<uint64_t, uint64_t> bucket, int frozen,
+                                                        const std::vector<std::pair<uint64_t, uint64_t>>& train_ranges) {
+  const uint64_t lo = bucket.first, hi = bucket.second;
+  if (frozen < 0) return {lo, hi - lo};
+  for (const auto& r : train_ranges) {
+    const uint64_t a = std::max(lo, r.first), b = std::min(hi, r.first + r.second);
+    if (a < b) return {a, b - a};
+  }
+  return {lo, 0};
+}
 
 struct gget_engine {
   gget_config_t cfg;
@@ -272,6 +292,12 @@ struct gget_engine {
   int frozen = -1;
   std::vector<std::pair<uint64_t, uint64_t>> train_ranges;   // [offset, count)
   OptWork frozen_work;
+  // parameter groups (gget_set_param_scales): per-parameter scales of lr and weight decay, indexed like plan.params; empty = off (every
+  // launch is then what it was without them).  group_work: the whole arena cut at the scale boundaries, what the replicated step of an
+  // unfrozen model runs over instead of the grid-stride kernel (items and scales only: the norm paths do not change)
+  std::vector<float> lr_scale, wd_scale;
+  bool grouped() const { return !lr_scale.empty(); }
+  OptWork group_work;
   // what a step, or an EMA lerp, runs over: the shard's work list (`sharded`: a plan is active and the caller runs its form), else the
   // trainable ranges', else none - the whole arena
   const OptWork* opt_work(bool sharded) const { return sharded ? &shard_work : frozen >= 0 ? &frozen_work : nullptr; }
@@ -281,15 +307,7 @@ struct gget_engine {
   int first_trainable_layer() const { return frozen < 0 ? 0 : std::min(frozen, cfg.num_layers); }
   // [offset, count) of a bucket's trainable share: the bucket itself, nothing (count 0), or - the embedding bucket - its gate /
   // raw-embedding parameters.  A bucket meets at most one of the ranges, in one piece.
-  std::pair<uint64_t, uint64_t> bucket_train_range(int bucket) const {
-    const uint64_t lo = bucket_range[bucket].first, hi = bucket_range[bucket].second;
-    if (frozen < 0) return {lo, hi - lo};
-    for (const auto& r : train_ranges) {
-      const uint64_t a = std::max(lo, r.first), b = std::min(hi, r.first + r.second);
-      if (a < b) return {a, b - a};
-    }
-    return {lo, 0};
-  }
+  std::pair<uint64_t, uint64_t> bucket_train_range(int bucket) const { return bucket_train_share(bucket_range[bucket], frozen, train_ranges); }
   const int32_t* klo() const { return packed ? wsp<int32_t>(ws.key_lo) : nullptr; }
   const int32_t* khi() const { return packed ? wsp<int32_t>(ws.key_hi) : nullptr; }
 

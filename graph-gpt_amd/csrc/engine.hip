@@ -434,18 +434,14 @@ extern "C" int gget_destroy(gget_handle_t h) {
   if (h) gget_comm_destroy(h);
   if (h) (void)h->shard_work.reset();
   if (h) (void)h->frozen_work.reset();
+  if (h) (void)h->group_work.reset();
   if (h && h->host_word) (void)hipHostFree(h->host_word);
   if (h && h->count_event) (void)hipEventDestroy(h->count_event);
   delete h;
   return 0;
 }
 
-extern "C" int gget_param_count(gget_handle_t h) { return h ? (int)h->plan.params.size() : -1; }
-
-extern "C" int gget_param_info(gget_handle_t h, int index, gget_param_info_t* out) {
-  GGET_REQUIRE(h && out, "null argument");
-  GGET_REQUIRE(index >= 0 && index < (int)h->plan.params.size(), "param index %d out of range", index);
-  const ParamRec& p = h->plan.params[index];
+void fill_param_info(const ParamRec& p, gget_param_info_t* out) {
   memset(out, 0, sizeof(*out));
   snprintf(out->name, sizeof(out->name), "%s", p.name.c_str());
   out->ndim = p.ndim;
@@ -453,6 +449,14 @@ extern "C" int gget_param_info(gget_handle_t h, int index, gget_param_info_t* ou
   out->shape[1] = p.shape[1];
   out->offset = p.off;
   out->layer = p.layer;
+}
+
+extern "C" int gget_param_count(gget_handle_t h) { return h ? (int)h->plan.params.size() : -1; }
+
+extern "C" int gget_param_info(gget_handle_t h, int index, gget_param_info_t* out) {
+  GGET_REQUIRE(h && out, "null argument");
+  GGET_REQUIRE(index >= 0 && index < (int)h->plan.params.size(), "param index %d out of range", index);
+  fill_param_info(h->plan.params[index], out);
   return 0;
 }
 

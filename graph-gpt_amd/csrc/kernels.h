@@ -210,6 +210,10 @@ int k_adamw(const GgetAdamwArgs& a, size_t n, hipStream_t st);
 // ... or over work items of <= kAdamwItemElems elements (offsets / counts multiples of 4, one block each)
 constexpr int kAdamwItemElems = 2048;
 int k_adamw_items(const GgetAdamwArgs& a, const GgetSqChunk* items_dev, int nitems, hipStream_t st);
+// ... or over the same items with per-item scales (parameter groups): scales_dev = [nitems][2] fp32, {lr_scale, wd_scale} of item i; the
+// item runs at lr * lr_scale and wd * wd_scale, one fp32 product each
+struct GgetGroupItems { const GgetSqChunk* items; const float* scales; };
+int k_adamw_group_items(const GgetAdamwArgs& a, const GgetSqChunk* items_dev, const float* scales_dev, int nitems, hipStream_t st);
 // gradient accumulation (reference: DeepSpeed's fp32 accumulation behind gradient_accumulation_steps, conf_utils.py:59-66):
 // acc[i] = (first ? 0 : acc[i]) + float(grad_bf16[i]) over the whole flat array (n a multiple of 8); 6 B per parameter when `first`, else 10
 int k_grad_accumulate(const void* grad, float* acc, size_t n, bool first, hipStream_t st);

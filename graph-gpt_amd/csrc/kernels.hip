@@ -2250,6 +2250,28 @@ __global__ void __launch_bounds__(kBlock) adamw_items_kernel(float* __restrict__
   }
 }
 
+// ... with per-item scales (parameter groups, optimizer.hip gget_set_param_scales): the item's learning rate and weight decay are the
+// step's times its two scales, ONE fp32 product each, and enter adamw_update4 unchanged - with both scales 1.0f the bits are those of
+// adamw_items_kernel.  lr_scale == 0: m and v move, master keeps its bits (w (1 - 0) - 0 U) and so does its bf16 rounding.
+template <typename GT, bool EMA>
+__global__ void __launch_bounds__(kBlock) adamw_group_items_kernel(float* __restrict__ master, float* __restrict__ m_, float* __restrict__ v_,
+                                                                   const GT* __restrict__ grad, bf16_t* __restrict__ param,
+                                                                   GgetGroupItems work, float lr, float beta1, float beta2, float eps, float wd,
+                                                                   float bc1, float bc2_sqrt, float max_norm, float grad_scale,
+                                                                   const float* __restrict__ sqnorm, float* __restrict__ gnorm_out,
+                                                                   int skip_nonfinite, float* __restrict__ ema, float ema_decay) {
+  float coef;
+  const bool go = adamw_coef(grad_scale, max_norm, sqnorm, gnorm_out, skip_nonfinite, coef);
+  if (!EMA && !go) return;
+  const GgetSqChunk it = work.items[blockIdx.x];
+  const float lr_i = lr * work.scales[2 * (size_t)blockIdx.x], wd_i = wd * work.scales[2 * (size_t)blockIdx.x + 1];
+  const size_t v0 = it.off >> 2, nv = it.cnt >> 2;
+  for (size_t i = threadIdx.x; i < nv; i += kBlock) {
+    if (!EMA || go) adamw_update4<EMA>(master, m_, v_, grad, param, v0 + i, coef, lr_i, beta1, beta2, eps, wd_i, bc1, bc2_sqrt, ema, ema_decay);
+    else ema_update4(master, ema, v0 + i, ema_decay);
+  }
+}
+
 // the stand-alone EMA lerp (12 B per parameter: master and ema read, ema written), needed where the reference averages although no AdamW
 // launch runs - the non-boundary micro-steps of a gradient accumulation, seeding (d = 0: ema = master, bit for bit) - in the form of
 // adamw_kernel<2>, and over the work items of a frozen model or a shard plan
@@ -3480,6 +3502,9 @@ struct AdamwGridStride {
 struct AdamwItems {
   template <typename GT, bool EMA> static constexpr auto kernel() { return adamw_items_kernel<GT, EMA>; }
 };
+struct AdamwGroupItems {
+  template <typename GT, bool EMA> static constexpr auto kernel() { return adamw_group_items_kernel<GT, EMA>; }
+};
 template <typename Shape, typename Work>
 int adamw_launch(const GgetAdamwArgs& a, dim3 grid, Work work, hipStream_t st) {
   const float bc1 = 1.0f - powf(a.beta1, (float)a.step);
@@ -3507,6 +3532,11 @@ int k_adamw(const GgetAdamwArgs& a, size_t n, hipStream_t st) {
 int k_adamw_items(const GgetAdamwArgs& a, const GgetSqChunk* items_dev, int nitems, hipStream_t st) {
   if (nitems <= 0) return 0;
   return adamw_launch<AdamwItems>(a, dim3(nitems), items_dev, st);
+}
+
+int k_adamw_group_items(const GgetAdamwArgs& a, const GgetSqChunk* items_dev, const float* scales_dev, int nitems, hipStream_t st) {
+  if (nitems <= 0) return 0;
+  return adamw_launch<AdamwGroupItems>(a, dim3(nitems), GgetGroupItems{items_dev, scales_dev}, st);
 }
 
 int k_grad_accumulate(const void* grad, float* acc, size_t n, bool first, hipStream_t st) {

@@ -2,6 +2,8 @@
 // reference: DeepSpeed zero_optimization.stage 2, examples/ds_config2_pt.json:29-32, engine built at src/training/pretrain_mode.py:281-287)
 // and the plan helpers only the step uses.  The kernels are in kernels.hip.
 #include <algorithm>
+#include <cmath>
+#include <numeric>
 #include <vector>
 
 #include "engine.h"
@@ -51,12 +53,65 @@ static ShardBucket shard_bucket(uint64_t off, uint64_t cnt, int world) {
   return ShardBucket{off, cnt, slice, off + (uint64_t)world * slice, cnt - (uint64_t)world * slice};
 }
 
-// [offset, count) ranges cut into the work items of the item kernels (k_adamw_items, k_ema_lerp_items: one block per item)
-static std::vector<GgetSqChunk> cut_items(const std::vector<std::pair<uint64_t, uint64_t>>& ranges) {
+// Parameter groups (gget_set_param_scales): the arena [0, n_params) as runs of equal {lr_scale, wd_scale}.  A parameter's run reaches to
+// the next parameter's offset - the alignment gap behind it and, behind lm_head.weight, the pad rows ride with it (zeros: any scale keeps
+// them zero) - and neighbours with the same two scales are one run, so a run boundary is a parameter offset (a multiple of 128) where a
+// scale differs.  lr / wd: indexed like plan.params, nullptr = all ones.
+struct ScaleRun { uint64_t off, end; float lr, wd; };
+static std::vector<ScaleRun> scale_runs(const Plan& pl, const float* lr, const float* wd) {
+  std::vector<int> order(pl.params.size());
+  std::iota(order.begin(), order.end(), 0);
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return pl.params[a].off < pl.params[b].off; });
+  std::vector<ScaleRun> runs;
+  for (int i : order) {
+    const float l = lr ? lr[i] : 1.f, w = wd ? wd[i] : 1.f;
+    if (runs.empty()) {
+      runs.push_back(ScaleRun{0, pl.n_params, l, w});
+    } else if (l != runs.back().lr || w != runs.back().wd) {
+      runs.back().end = pl.params[i].off;
+      runs.push_back(ScaleRun{pl.params[i].off, pl.n_params, l, w});
+    }
+  }
+  return runs;
+}
+
+// [offset, count) ranges cut into the work items of the item kernels (k_adamw_items, k_ema_lerp_items: one block per item); with `runs`
+// no item crosses a run boundary and `scales` holds the two scales of every item
+struct WorkItems {
   std::vector<GgetSqChunk> items;
-  for (const auto& r : ranges)
-    for (uint64_t o = 0; o < r.second; o += kAdamwItemElems) items.push_back(GgetSqChunk{r.first + o, std::min<uint64_t>(kAdamwItemElems, r.second - o)});
-  return items;
+  std::vector<float> scales;
+};
+static WorkItems cut_items(const std::vector<std::pair<uint64_t, uint64_t>>& ranges, const std::vector<ScaleRun>* runs = nullptr) {
+  WorkItems w;
+  auto cut = [&](uint64_t lo, uint64_t hi, const ScaleRun* run) {
+    for (uint64_t o = lo; o < hi; o += kAdamwItemElems) {
+      w.items.push_back(GgetSqChunk{o, std::min<uint64_t>(kAdamwItemElems, hi - o)});
+      if (run) w.scales.push_back(run->lr), w.scales.push_back(run->wd);
+    }
+  };
+  for (const auto& r : ranges) {
+    if (!runs) {
+      cut(r.first, r.first + r.second, nullptr);
+      continue;
+    }
+    for (const ScaleRun& run : *runs) {
+      const uint64_t lo = std::max(r.first, run.off), hi = std::min(r.first + r.second, run.end);
+      if (lo < hi) cut(lo, hi, &run);
+    }
+  }
+  return w;
+}
+
+// the element ranges a sharded step updates: the body slice of rank `rank` of every bucket (every rank's when `all_ranks`: the loopback
+// communicator) and every tail
+static std::vector<std::pair<uint64_t, uint64_t>> shard_share(const std::vector<ShardBucket>& plan, int world, int rank, bool all_ranks) {
+  std::vector<std::pair<uint64_t, uint64_t>> share;
+  for (const ShardBucket& b : plan) {
+    for (int r = 0; r < world; ++r)
+      if (all_ranks || r == rank) share.push_back({b.off + (uint64_t)r * b.slice, b.slice});
+    share.push_back({b.tail_off, b.tail_cnt});
+  }
+  return share;
 }
 
 // ================================================================================================
@@ -116,15 +171,20 @@ static std::vector<std::pair<uint64_t, uint64_t>> frozen_train_ranges(const gget
   return r;
 }
 
-extern "C" int gget_set_frozen(gget_handle_t h, int frozen_layers) {
-  GGET_REQUIRE(h != nullptr, "set_frozen: null handle");
-  GGET_REQUIRE(frozen_layers >= -1, "set_frozen: %d frozen layers (-1 = none, k >= 0 = embed_tokens and the first k layers)", frozen_layers);
-  GGET_REQUIRE(h->grad_acc_count == 0, "set_frozen: a gradient-accumulation window is open (%d micro-steps summed); step first", h->grad_acc_count);
+// The work lists of the handle for its frozen prefix (h->frozen), its scale table and its shard plan, built again: what gget_set_frozen
+// and gget_set_param_scales end in, in either call order (gget_shard_init cuts its own from the two others)
+static int rebuild_work(gget_engine* h) {
   if (int e = h->frozen_work.reset()) return e;
+  if (int e = h->group_work.reset()) return e;
   h->train_ranges.clear();
-  h->frozen = frozen_layers;
-  if (frozen_layers >= 0) {
-    h->train_ranges = frozen_train_ranges(h->cfg, h->plan, std::min(frozen_layers, h->cfg.num_layers));
+  std::vector<ScaleRun> runs;
+  if (h->grouped()) runs = scale_runs(h->plan, h->lr_scale.data(), h->wd_scale.data());
+  if (h->grouped() && h->frozen < 0) {      // the replicated step of an unfrozen model: the whole arena as items
+    const WorkItems it = cut_items({{0, h->plan.n_params}}, &runs);
+    if (int e = h->group_work.upload(it.items, {}, {}, {}, it.scales)) return e;
+  }
+  if (h->frozen >= 0) {
+    h->train_ranges = frozen_train_ranges(h->cfg, h->plan, std::min(h->frozen, h->cfg.num_layers));
     uint64_t total = 0;
     for (const auto& r : h->train_ranges) total += r.second;
     // at most 1024 norm chunks (one block and one partial sum each)
@@ -133,10 +193,102 @@ extern "C" int gget_set_frozen(gget_handle_t h, int frozen_layers) {
     for (const auto& r : h->train_ranges)
       for (uint64_t o = 0; o < r.second; o += chunk) chunks.push_back(GgetSqChunk{r.first + o, std::min(chunk, r.second - o)});
     GGET_REQUIRE(chunks.size() <= 1024, "set_frozen: %d norm chunks", (int)chunks.size());
-    if (int e = h->frozen_work.upload(cut_items(h->train_ranges), chunks)) return e;
+    const WorkItems it = cut_items(h->train_ranges, h->grouped() ? &runs : nullptr);
+    if (int e = h->frozen_work.upload(it.items, chunks, {}, {}, it.scales)) return e;
   }
-  // a shard plan cuts the trainable share of every bucket: built again for the new ranges
+  // a shard plan cuts the trainable share of every bucket: built again for the new ranges and scales
   if (h->shard_world > 0) return gget_shard_init(h, h->shard_world, h->shard_rank, nullptr);
+  return 0;
+}
+
+extern "C" int gget_set_frozen(gget_handle_t h, int frozen_layers) {
+  GGET_REQUIRE(h != nullptr, "set_frozen: null handle");
+  GGET_REQUIRE(frozen_layers >= -1, "set_frozen: %d frozen layers (-1 = none, k >= 0 = embed_tokens and the first k layers)", frozen_layers);
+  GGET_REQUIRE(h->grad_acc_count == 0, "set_frozen: a gradient-accumulation window is open (%d micro-steps summed); step first", h->grad_acc_count);
+  h->frozen = frozen_layers;
+  return rebuild_work(h);
+}
+
+// ================================================================================================
+// parameter groups
+// ================================================================================================
+// finite and >= 0 (NaN fails the comparison); nullptr = all ones
+static int check_scales(const char* who, const char* which, const float* s, int n, const Plan& pl) {
+  for (int i = 0; s && i < n; ++i)
+    GGET_REQUIRE(s[i] >= 0.f && std::isfinite(s[i]), "%s: %s[%d] = %g (%s) is not a finite value >= 0", who, which, i, (double)s[i],
+                 pl.params[i].name.c_str());
+  return 0;
+}
+
+extern "C" int gget_set_param_scales(gget_handle_t h, const float* lr_scale, const float* wd_scale, int n) {
+  GGET_REQUIRE(h != nullptr, "set_param_scales: null handle");
+  const int np = (int)h->plan.params.size();
+  const bool off = !lr_scale && !wd_scale && n == 0;
+  GGET_REQUIRE(off || n == np, "set_param_scales: %d scales for %d parameters (NULL, NULL, 0 switches the groups off)", n, np);
+  if (int e = check_scales("set_param_scales", "lr_scale", lr_scale, n, h->plan)) return e;
+  if (int e = check_scales("set_param_scales", "wd_scale", wd_scale, n, h->plan)) return e;
+  h->lr_scale.assign(off ? 0 : np, 1.f);
+  h->wd_scale.assign(off ? 0 : np, 1.f);
+  for (int i = 0; i < n; ++i) {      // (+ 0.0f: a -0.0 is stored as 0.0)
+    if (lr_scale) h->lr_scale[i] = lr_scale[i] + 0.f;
+    if (wd_scale) h->wd_scale[i] = wd_scale[i] + 0.f;
+  }
+  return rebuild_work(h);
+}
+
+extern "C" int gget_param_scales(gget_handle_t h, float* lr_out, float* wd_out, int n) {
+  GGET_REQUIRE(h != nullptr, "param_scales: null handle");
+  const int np = (int)h->plan.params.size();
+  GGET_REQUIRE(n == np, "param_scales: room for %d scales, the model has %d parameters", n, np);
+  for (int i = 0; i < np; ++i) {
+    if (lr_out) lr_out[i] = h->grouped() ? h->lr_scale[i] : 1.f;
+    if (wd_out) wd_out[i] = h->grouped() ? h->wd_scale[i] : 1.f;
+  }
+  return 0;
+}
+
+extern "C" int gget_plan_param_count(const gget_config_t* cfg) {
+  if (check_cfg(cfg)) return -1;
+  return (int)make_plan(*cfg).params.size();
+}
+
+extern "C" int gget_plan_param_info(const gget_config_t* cfg, int index, gget_param_info_t* out) {
+  if (int e = check_cfg(cfg)) return e;
+  GGET_REQUIRE(out != nullptr, "plan_param_info: null argument");
+  const Plan pl = make_plan(*cfg);
+  GGET_REQUIRE(index >= 0 && index < (int)pl.params.size(), "param index %d out of range", index);
+  fill_param_info(pl.params[index], out);
+  return 0;
+}
+
+extern "C" int gget_group_plan(const gget_config_t* cfg, const float* lr_scale, const float* wd_scale, int n, int frozen_layers, int world,
+                               int rank, gget_group_item_t* items_out, int cap, int32_t* n_out) {
+  if (int e = check_cfg(cfg)) return e;
+  const Plan pl = make_plan(*cfg);
+  const int np = (int)pl.params.size();
+  GGET_REQUIRE(n_out != nullptr && cap >= 0 && (items_out != nullptr || cap == 0), "group_plan: bad output arguments (cap %d)", cap);
+  GGET_REQUIRE((!lr_scale && !wd_scale && n == 0) || n == np, "group_plan: %d scales for %d parameters", n, np);
+  if (int e = check_scales("group_plan", "lr_scale", lr_scale, n, pl)) return e;
+  if (int e = check_scales("group_plan", "wd_scale", wd_scale, n, pl)) return e;
+  GGET_REQUIRE(frozen_layers >= -1, "group_plan: %d frozen layers", frozen_layers);
+  GGET_REQUIRE(world >= 0 && (world == 0 || (rank >= -1 && rank < world)), "group_plan: bad arguments (rank %d world %d)", rank, world);
+  std::vector<std::pair<uint64_t, uint64_t>> train, ranges;
+  if (frozen_layers >= 0) train = frozen_train_ranges(*cfg, pl, std::min(frozen_layers, cfg->num_layers));
+  if (world == 0) {
+    ranges = frozen_layers >= 0 ? train : std::vector<std::pair<uint64_t, uint64_t>>{{0, pl.n_params}};
+  } else {
+    std::vector<ShardBucket> plan;
+    for (const auto& b : bucket_ranges(*cfg, pl)) {
+      const auto r = bucket_train_share(b, frozen_layers, train);
+      plan.push_back(shard_bucket(r.first, r.second, world));
+    }
+    ranges = shard_share(plan, world, rank, rank < 0);
+  }
+  const std::vector<ScaleRun> runs = scale_runs(pl, lr_scale, wd_scale);
+  const WorkItems w = cut_items(ranges, &runs);
+  *n_out = (int32_t)w.items.size();
+  for (size_t i = 0; i < w.items.size() && i < (size_t)cap; ++i)
+    items_out[i] = gget_group_item_t{w.items[i].off, w.items[i].cnt, w.scales[2 * i], w.scales[2 * i + 1]};
   return 0;
 }
 
@@ -221,6 +373,8 @@ static int optimizer_step(gget_engine* h, bool sharded, float lr, float beta1, f
   a.grad = h->grad_src();
   h->grad_acc_count = 0;
   const OptWork* w = h->opt_work(sharded);
+  // parameter groups: the replicated step of an unfrozen model runs over the whole arena as items (the norm paths below do not change)
+  const OptWork* iw = w ? w : h->grouped() ? &h->group_work : nullptr;
   if (need_norm) {
     if (sharded) {
       if (int e = k_grad_sqnorm_slots(slots_dev, w->slot_of, w->nglobal, sq, st)) return e;
@@ -237,7 +391,8 @@ static int optimizer_step(gget_engine* h, bool sharded, float lr, float beta1, f
     } else if (int e = k_grad_sqnorm(a.grad, h->plan.n_params, sq, st, a.grad_f32)) return e;
   }
   // the item kernels share the per-element update with the grid-stride one: the same bits per element, given the same coefficient
-  return w ? k_adamw_items(a, w->items, w->nitems, st) : k_adamw(a, h->plan.n_params, st);
+  if (!iw) return k_adamw(a, h->plan.n_params, st);
+  return iw->scales ? k_adamw_group_items(a, iw->items, iw->scales, iw->nitems, st) : k_adamw_items(a, iw->items, iw->nitems, st);
 }
 
 extern "C" int gget_adamw_step(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -297,14 +452,12 @@ extern "C" int gget_shard_init(gget_handle_t h, int world, int rank, int32_t* sl
       chunk_slot.push_back(slot_of[j]);
     }
   }
-  // AdamW work items: this rank's body slice of every bucket (all of them for the loopback) and every tail
-  std::vector<std::pair<uint64_t, uint64_t>> share;
-  for (const ShardBucket& b : plan) {
-    for (int r = 0; r < world; ++r)
-      if (all_ranks || r == rank) share.push_back({b.off + (uint64_t)r * b.slice, b.slice});
-    share.push_back({b.tail_off, b.tail_cnt});
-  }
-  if (int e = h->shard_work.upload(cut_items(share), chunks, chunk_slot, slot_of)) return e;
+  // AdamW work items: this rank's body slice of every bucket (all of them for the loopback) and every tail, cut at the boundaries of the
+  // parameter groups when a scale table is set
+  std::vector<ScaleRun> runs;
+  if (h->grouped()) runs = scale_runs(h->plan, h->lr_scale.data(), h->wd_scale.data());
+  const WorkItems it = cut_items(shard_share(plan, world, rank, all_ranks), h->grouped() ? &runs : nullptr);
+  if (int e = h->shard_work.upload(it.items, chunks, chunk_slot, slot_of, it.scales)) return e;
   h->shard_world = world;
   h->shard_rank = rank;
   h->shard_slots = S;

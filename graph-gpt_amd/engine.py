@@ -31,6 +31,26 @@ def rope_tables(max_position: int, head_dim: int, theta: float):
     return freqs.cos().contiguous(), freqs.sin().contiguous()
 
 
+def make_config(spec: ModelSpec, max_tokens: int, max_batch: int) -> "L.GgetConfig":
+    """The gget_config_t of a model spec and its capacities (what Engine hands to gget_create; the handle-free planning entries -
+    gget_shard_plan, gget_group_plan - take the same struct)."""
+    cfg = L.GgetConfig()
+    (cfg.kind, cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size, cfg.num_layers, cfg.num_heads,
+     cfg.stacked_feat, cfg.next_n_token, cfg.gated_agg, cfg.causal, cfg.max_position, cfg.num_labels,
+     cfg.score_bias, cfg.pad_token_id) = spec.as_c_ints()
+    cfg.rms_eps, cfg.rope_theta, cfg.layer_scale_init = spec.rms_eps, spec.rope_theta, spec.layer_scale_init
+    cfg.max_tokens, cfg.max_batch = int(max_tokens), int(max_batch)
+    cfg.path_pdrop = float(getattr(spec, "path_pdrop", 0.0))
+    cfg.mlp_pdrop = float(getattr(spec, "mlp_pdrop", 0.0))
+    hm = [int(x) for x in getattr(spec, "head_mlp", ())]
+    assert len(hm) <= 4, "the MLP score head holds at most 4 hidden layers"
+    cfg.head_mlp_layers = len(hm)
+    for i, x in enumerate(hm):
+        cfg.head_mlp[i] = x
+    cfg.embed_dim = int(getattr(spec, "embed_dim", 0) or 0)
+    return cfg
+
+
 class Engine:
     def __init__(self, spec: ModelSpec, max_tokens: int, max_batch: int, device: Optional[torch.device] = None,
                  with_optimizer: bool = True):
@@ -39,20 +59,7 @@ class Engine:
         self.lib = L.load()
         self.spec = spec
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        cfg = L.GgetConfig()
-        (cfg.kind, cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size, cfg.num_layers, cfg.num_heads,
-         cfg.stacked_feat, cfg.next_n_token, cfg.gated_agg, cfg.causal, cfg.max_position, cfg.num_labels,
-         cfg.score_bias, cfg.pad_token_id) = spec.as_c_ints()
-        cfg.rms_eps, cfg.rope_theta, cfg.layer_scale_init = spec.rms_eps, spec.rope_theta, spec.layer_scale_init
-        cfg.max_tokens, cfg.max_batch = int(max_tokens), int(max_batch)
-        cfg.path_pdrop = float(getattr(spec, "path_pdrop", 0.0))
-        cfg.mlp_pdrop = float(getattr(spec, "mlp_pdrop", 0.0))
-        hm = [int(x) for x in getattr(spec, "head_mlp", ())]
-        assert len(hm) <= 4, "the MLP score head holds at most 4 hidden layers"
-        cfg.head_mlp_layers = len(hm)
-        for i, x in enumerate(hm):
-            cfg.head_mlp[i] = x
-        cfg.embed_dim = int(getattr(spec, "embed_dim", 0) or 0)
+        cfg = make_config(spec, max_tokens, max_batch)
         self.cfg = cfg
         sz = L.GgetSizes()
         L.check(self.lib.gget_query_sizes(C.byref(cfg), C.byref(sz)))
@@ -186,6 +193,69 @@ class Engine:
     def is_frozen(self, name: str) -> bool:
         p = self.params[name]
         return not any(off <= p["offset"] < off + n for off, n in self.train_ranges)
+
+    # ------------------------------------------------------------------ parameter groups (per-parameter lr / weight-decay scales)
+    @staticmethod
+    def scale_arrays(names, lr_scale=None, wd_scale=None):
+        """Two fp32 arrays indexed like `names` from {state-dict name: scale} dicts: a missing name takes 1.0, an unknown one raises."""
+        names = list(names)
+        out = []
+        for what, d in (("lr_scale", lr_scale or {}), ("wd_scale", wd_scale or {})):
+            unknown = sorted(k for k in d if k not in set(names))
+            if unknown:
+                raise KeyError(f"set_param_scales: {what} names no parameter of this model: {unknown[:6]}")
+            out.append(np.array([float(d.get(k, 1.0)) for k in names], dtype=np.float32))
+        return out
+
+    def set_param_scales(self, lr_scale: Optional[Dict[str, float]] = None, wd_scale: Optional[Dict[str, float]] = None):
+        """Parameter groups (gget_set_param_scales): every step runs parameter `name` at lr * lr_scale[name] and weight_decay *
+        wd_scale[name], one fp32 product each.  Keys are state-dict names; a missing name takes 1.0, an unknown one raises.  Both None
+        switches the groups off.  The table stays on the handle through set_frozen / shard_init, in either call order."""
+        if lr_scale is None and wd_scale is None:
+            L.check(self.lib.gget_set_param_scales(self.h, None, None, 0))
+            return
+        lr, wd = self.scale_arrays(self.params, lr_scale, wd_scale)
+        fp = C.POINTER(C.c_float)
+        L.check(self.lib.gget_set_param_scales(self.h, lr.ctypes.data_as(fp), wd.ctypes.data_as(fp), len(self.params)))
+
+    def param_scales(self):
+        """({name: lr_scale}, {name: wd_scale}) as the handle holds them (gget_param_scales); ones while no groups are set."""
+        n = len(self.params)
+        lr, wd = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        L.check(self.lib.gget_param_scales(self.h, lr.ctypes.data_as(fp), wd.ctypes.data_as(fp), n))
+        return ({k: float(x) for k, x in zip(self.params, lr)}, {k: float(x) for k, x in zip(self.params, wd)})
+
+    @staticmethod
+    def plan_params_of(cfg):
+        """The parameter table of a configuration without a handle (gget_plan_param_count / gget_plan_param_info): name -> dict as
+        `Engine.params`, plus `ndim`."""
+        lib, info = L.load(), L.GgetParamInfo()
+        n = lib.gget_plan_param_count(C.byref(cfg))
+        if n < 0:
+            raise L.GgetError(f"gget error: {lib.gget_last_error().decode()}")
+        out = OrderedDict()
+        for i in range(n):
+            L.check(lib.gget_plan_param_info(C.byref(cfg), i, C.byref(info)))
+            shape = tuple(int(info.shape[k]) for k in range(info.ndim))
+            out[info.name.decode()] = dict(shape=shape, offset=int(info.offset), numel=int(np.prod(shape)), layer=int(info.layer),
+                                           ndim=int(info.ndim))
+        return out
+
+    @staticmethod
+    def group_plan_of(cfg, lr_scale=None, wd_scale=None, frozen_layers: int = -1, world: int = 0, rank: int = -1):
+        """[(offset, count, lr_scale, wd_scale)]: the work items of the step of this configuration (gget_group_plan; defined once, in
+        C, from the configuration alone).  lr_scale / wd_scale: fp32 arrays indexed like the parameter table, or None = ones."""
+        lib, fp = L.load(), C.POINTER(C.c_float)
+        arr = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (lr_scale, wd_scale)]
+        n = max([0] + [len(a) for a in arr if a is not None])
+        ptr = [None if a is None else a.ctypes.data_as(fp) for a in arr]
+        args = (C.byref(cfg), ptr[0], ptr[1], n, int(frozen_layers), int(world), int(rank))
+        cnt = C.c_int32(0)
+        L.check(lib.gget_group_plan(*args, None, 0, C.byref(cnt)))
+        items = (L.GgetGroupItem * max(1, cnt.value))()
+        L.check(lib.gget_group_plan(*args, items, cnt.value, C.byref(cnt)))
+        return [(int(it.off), int(it.cnt), float(it.lr_scale), float(it.wd_scale)) for it in items[:cnt.value]]
 
     # ------------------------------------------------------------------ gradient accumulation (optimizer.gradient_accumulation_steps)
     def grad_acc_attach(self):

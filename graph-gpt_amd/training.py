@@ -57,7 +57,15 @@ class OptimConfig:
 
     def __init__(self, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=1.0, min_lr=0.0,
                  warmup_num_steps=0, total_num_steps=0, schedule="constant", onecycle_extra_step=1, gradient_accumulation_steps=1,
-                 zero_stage=0, use_ema=False, ema_decay=0.9999):
+                 zero_stage=0, use_ema=False, ema_decay=0.9999, layerwise_lr_decay=None, layerwise_lr_version=1, no_decay_1d=False):
+        # parameter groups built by initialize(): layer-wise lr decay (reference loss_utils.py:370-412, see layerwise_lr_scales; None =
+        # off, version 1 or 3) and the "no weight decay on 1-D parameters" split (norm weights, LayerScale, biases)
+        self.layerwise_lr_decay = None if layerwise_lr_decay is None else float(layerwise_lr_decay)
+        self.layerwise_lr_version, self.no_decay_1d = int(layerwise_lr_version), bool(no_decay_1d)
+        if self.layerwise_lr_decay is not None and not self.layerwise_lr_decay >= 0.0:
+            raise ValueError(f"layerwise_lr_decay {layerwise_lr_decay} is not >= 0")
+        if self.layerwise_lr_version not in (1, 3):
+            raise ValueError(f"layerwise_lr_version {layerwise_lr_version}: 1 or 3 (the reference's v2 follows module registration order)")
         # `training.optimizer.use_ema` / `ema_decay` (reference base_configs.py:75-87; the fine-tune launch scripts run use_ema=true with
         # 0.9999): GgetEngine keeps an exponential moving average of the fp32 master weights (see GgetEngine.ema_decay_at / step)
         self.use_ema, self.ema_decay = bool(use_ema), float(ema_decay)
@@ -89,6 +97,63 @@ class OptimConfig:
 def schedule_steps(total_tokens: float, tokens_per_sample: float, batch_size: int, world_size: int) -> int:
     """Optimizer steps of a token-budgeted run (reference base_configs.py:54-60): the global batch is world * batch_size."""
     return int(total_tokens // (tokens_per_sample * batch_size * world_size))
+
+
+# ----------------------------------------------------------------------------- parameter groups
+_EMBED_SIDE = ("embed_layernorm.", "embed_proj.", "emb_mask_token")     # feed the token embeddings (embed_dim > 0)
+_HEAD_SIDE = ("n_token_proj.", "cl_proj.")                              # feed / sit beside lm_head
+
+
+def layerwise_depths(names, num_layers: int, version: int = 1, feat_agg_group: bool = True) -> Dict[str, int]:
+    """Depth of every state-dict name in the reference's layer-wise groups, counted down from the head (depth 0).
+    version 1 (loss_utils.py:370-387) - the groups in order: embed_tokens, stacked_feat_agg (`feat_agg_group`: the reference adds the
+    group whenever the module exists, with or without parameters), one per decoder layer, model.norm, lm_head, score (each head if the
+    model has it); depth = groups behind it.  version 3 (:398-412): heads 0, everything else 1.
+    Names the reference's groups leave out take the depth of the group they feed: n_token_proj / cl_proj that of lm_head,
+    embed_layernorm / embed_proj / emb_mask_token that of embed_tokens."""
+    names = list(names)
+    heads = [h for h in ("lm_head", "score") if any(n.startswith(h + ".") for n in names)]
+    if version == 3:
+        return {n: 0 if n.startswith(tuple(h + "." for h in heads) + _HEAD_SIDE) else 1 for n in names}
+    if version != 1:
+        raise ValueError(f"layer-wise lr version {version}: 1 or 3")
+    order = ["embed"] + (["agg"] if feat_agg_group else []) + [f"layer{i}" for i in range(num_layers)] + ["norm"] + heads
+    depth_of = {g: len(order) - 1 - i for i, g in enumerate(order)}
+    out = {}
+    for n in names:
+        parts = n.split(".")
+        if n.startswith("model.embed_tokens.") or n.startswith(_EMBED_SIDE):
+            g = "embed"
+        elif n.startswith("stacked_feat_agg."):
+            g = "agg"
+        elif parts[:2] == ["model", "layers"]:
+            g = f"layer{int(parts[2])}"
+        elif n.startswith("model.norm."):
+            g = "norm"
+        elif n.startswith(_HEAD_SIDE):
+            g = "lm_head"
+        elif parts[0] in heads:
+            g = parts[0]
+        else:
+            raise KeyError(f"layerwise_depths: {n!r} belongs to no group")
+        out[n] = depth_of[g]
+    return out
+
+
+def _feat_agg_group(model) -> bool:
+    """Whether the reference's model has a `stacked_feat_agg` module (modeling_pretrain.py:67 always; modeling_finetune.py:74 only for
+    stack_method short / long) - v1 gives it a group of its own even when the module has no parameters."""
+    return isinstance(model, GraphGPTPretrainBase) or getattr(model.config, "stack_method", None) in ("short", "long")
+
+
+def layerwise_lr_scales(model, lr_decay: float, version: int = 1) -> Dict[str, float]:
+    """State-dict name -> lr_decay ** depth: the learning-rate scales of the reference's get_layerwise_param_groups (version 1) or
+    get_layerwise_param_groups_v3 (version 3), for Engine.set_param_scales / GgetEngine.set_param_scales.
+    The one deliberate difference: the reference's groups leave n_token_proj, cl_proj, embed_layernorm, embed_proj (and emb_mask_token)
+    out of the optimizer altogether - they would never train.  Here they take the depth of the group they feed: n_token_proj and
+    cl_proj with lm_head, embed_layernorm / embed_proj / emb_mask_token with embed_tokens."""
+    depths = layerwise_depths(model._flat, model.config.num_hidden_layers, version, _feat_agg_group(model))
+    return {n: math.pow(lr_decay, d) for n, d in depths.items()}
 
 
 # ----------------------------------------------------------------------------- engine protocol
@@ -140,6 +205,9 @@ class GgetEngine:
         # skipped (weights and Adam state untouched, Adam's step count not advanced) while the LR schedule still advances
         self.skip_nonfinite = False
         self.skipped_steps = 0
+        # parameter groups (set_param_groups / set_param_scales): ({name: lr_scale}, {name: wd_scale}) over every parameter, or None;
+        # the table lives on the engine instance and is handed to a re-created one in step(), as skip_nonfinite is
+        self._param_scales = None
         # weight EMA (optim.use_ema): step() calls so far that averaged = the reference's `train_stats.j` at its update_ema call
         self.ema_updates = 0
         if self.world > 1 and torch.cuda.is_available():     # (DpOptions.reserve_cus: a real multi-process job only, not a loopback world)
@@ -341,6 +409,73 @@ class GgetEngine:
             e._skip_nonfinite = on
         self.skip_nonfinite = on
 
+    # -- parameter groups (reference: torch parameter groups from loss_utils.py:370-412 handed to AdamW)
+    def set_param_scales(self, lr_scale: Optional[Dict[str, float]] = None, wd_scale: Optional[Dict[str, float]] = None):
+        """Per-parameter scales by state-dict name (a missing name takes 1.0, an unknown one raises); both None switches the groups off.
+        Every step then runs parameter `name` at lr_at(step) * lr_scale[name] and weight_decay * wd_scale[name] (Engine.set_param_scales)."""
+        if lr_scale is None and wd_scale is None:
+            self._param_scales = None
+        else:
+            names = list(self.module._flat)
+            for what, d in (("lr_scale", lr_scale or {}), ("wd_scale", wd_scale or {})):
+                unknown = sorted(k for k in d if k not in self.module._flat)
+                if unknown:
+                    raise KeyError(f"set_param_scales: {what} names no parameter of this model: {unknown[:6]}")
+            self._param_scales = ({n: float((lr_scale or {}).get(n, 1.0)) for n in names}, {n: float((wd_scale or {}).get(n, 1.0)) for n in names})
+        e = self.module._engine
+        if e is not None:
+            self._apply_param_scales(e)
+
+    def _apply_param_scales(self, e):
+        e.set_param_scales(*(self._param_scales or (None, None)))
+        e._param_scales_from = self._param_scales
+
+    def set_param_groups(self, groups, rest_lr_scale: Optional[float] = None):
+        """torch-style parameter groups.  Every group is a dict: "params" = Parameters of the module or state-dict names (any iterable);
+        "lr" (absolute, divided by optim.lr) or "lr_scale"; "weight_decay" (absolute, divided by optim.weight_decay) or "wd_scale" -
+        all optional, default scale 1.  Every group follows the one schedule shape: lr_at(step) times its scale.  A parameter in two
+        groups raises.  A parameter in no group raises with the names - torch would silently never train it - unless `rest_lr_scale`
+        is given: those parameters then run at that scale (0.0 = torch's behaviour, said out loud)."""
+        o = self.optim
+        name_of = {id(p): n for n, p in self.module._flat.items()}
+        lr_s, wd_s, twice = {}, {}, []
+        for gi, g in enumerate(groups):
+            if ("lr" in g and "lr_scale" in g) or ("weight_decay" in g and "wd_scale" in g):
+                raise ValueError(f"set_param_groups: group {gi} gives both an absolute value and a scale")
+            ls = float(g["lr"]) / float(o.lr) if "lr" in g else float(g.get("lr_scale", 1.0))
+            if "weight_decay" in g:
+                if float(o.weight_decay) == 0.0 and float(g["weight_decay"]) != 0.0:
+                    raise ValueError(f"set_param_groups: group {gi} asks for weight_decay {g['weight_decay']} but optim.weight_decay is 0 "
+                                     "(the group's value is a scale of it)")
+                ws = float(g["weight_decay"]) / float(o.weight_decay) if float(o.weight_decay) != 0.0 else 1.0
+            else:
+                ws = float(g.get("wd_scale", 1.0))
+            for p in ([g["params"]] if isinstance(g["params"], (str, torch.Tensor)) else list(g["params"])):
+                n = p if isinstance(p, str) else name_of.get(id(p))
+                if n is None or n not in self.module._flat:
+                    raise KeyError(f"set_param_groups: group {gi} holds {'a tensor that is' if n is None else repr(n) + ','} no parameter of this model")
+                if n in lr_s:
+                    twice.append(n)
+                lr_s[n], wd_s[n] = ls, ws
+        if twice:
+            raise ValueError(f"set_param_groups: some parameters appear in more than one parameter group: {twice}")
+        rest = [n for n in self.module._flat if n not in lr_s]
+        if rest and rest_lr_scale is None:
+            raise ValueError(f"set_param_groups: {len(rest)} parameters are in no group and would never train: {rest}; put them in a group "
+                             "or pass rest_lr_scale (0.0 = leave them untrained on purpose)")
+        for n in rest:
+            lr_s[n], wd_s[n] = float(rest_lr_scale), 1.0
+        self.set_param_scales(lr_s, wd_s)
+
+    @property
+    def last_lrs(self) -> Dict[str, float]:
+        """State-dict name -> learning rate of the last step: lr_at(step) times the parameter's scale."""
+        lr = getattr(self, "last_lr", None)         # (set by the first step)
+        if lr is None:
+            return {}
+        lr_s = self._param_scales[0] if self._param_scales is not None else {}
+        return {n: lr * lr_s.get(n, 1.0) for n in self.module._flat}
+
     # -- weight EMA (reference: EMAStats + timm ModelEmaV3, src/conf/stats_configs.py:102-146, src/utils/patch_utils.py:5-42)
     def ema_decay_at(self, step: int) -> float:
         """The decay of the update made when `step` loop iterations were done before it (the reference passes `train_stats.j`,
@@ -442,6 +577,8 @@ class GgetEngine:
         lr = o.lr_at(self.global_steps)
         if self.skip_nonfinite and getattr(e, "_skip_nonfinite", None) is not True:
             self.set_skip_nonfinite(True)       # (the model re-created its engine: the option lives on the engine instance)
+        if getattr(e, "_param_scales_from", None) is not self._param_scales:
+            self._apply_param_scales(e)         # (the same for the parameter groups)
         if ema_decay is not None:
             e.set_ema_decay(ema_decay)
         if self.sharded:
@@ -511,7 +648,14 @@ class GgetEngine:
 
 
 def initialize(model: _GgetModel, optim: Optional[OptimConfig] = None, process_group=None) -> GgetEngine:
-    return GgetEngine(model, optim, process_group)
+    eng = GgetEngine(model, optim, process_group)
+    o = eng.optim
+    decay, no_decay = getattr(o, "layerwise_lr_decay", None), getattr(o, "no_decay_1d", False)
+    if decay is not None or no_decay:
+        lr_s = layerwise_lr_scales(model, decay, getattr(o, "layerwise_lr_version", 1)) if decay is not None else {}
+        wd_s = {n: 0.0 for n, p in model._flat.items() if p.ndim == 1} if no_decay else {}
+        eng.set_param_scales(lr_s, wd_s)
+    return eng
 
 
 # ----------------------------------------------------------------------------- one optimisation step

@@ -461,6 +461,51 @@ int gget_shard_allgather_async(gget_handle_t h, int what, float* slots_dev, void
 int gget_adamw_step_sharded(gget_handle_t h, float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
                             float grad_scale, int step, const float* slots_dev, float* gnorm_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Parameter groups (per-parameter learning-rate and weight-decay scales).  replaces: torch parameter groups handed to AdamW(params=groups)
+ * - the reference's layer-wise lr decay (src/utils/loss_utils.py:370-412, get_layerwise_param_groups: lr = base_lr * lr_decay**depth per
+ * group) and the usual "no weight decay on norm weights" split.  The table holds two fp32 scales per parameter, indexed like
+ * gget_param_info.  With a table set, every optimizer step runs over work items (at most 2048 elements, one block each) cut so that no
+ * item crosses a parameter boundary at which either scale changes; the alignment gap behind a parameter, and the zero rows behind
+ * lm_head.weight, ride with the parameter in front of them (zeros: they stay zero under any scale).  The kernel forms
+ *     lr_i = lr * lr_scale        wd_i = weight_decay * wd_scale        (one fp32 product each)
+ * per item and the update runs with these two values in place of lr and weight_decay - nothing else differs, so an element's result is
+ * that of gget_adamw_step called with (lr_i, wd_i): with both scales 1.0f the bits equal the ungrouped step's.  lr_scale = 0 follows
+ * torch: m and v are updated, the master weight and its bf16 copy keep their bits.  The clip norm is over ALL trainable gradients whatever
+ * their scale (clip_grad_norm_ over model.parameters()); norm chunks, slots, GGET_OPT_NORM_FROM_BACKWARD, the fused and the stand-alone
+ * EMA, the fp32 accumulator and GGET_OPT_SKIP_NONFINITE_STEP work as without a table.  A parameter that belongs to no group of the
+ * caller's has no special state here: it takes whatever scale the caller wrote for it (1.0 = the step's own lr) - a caller that wants
+ * torch's "not in the optimizer" must freeze it or say lr_scale 0.  With no table set no launch changes.
+ * ------------------------------------------------------------------------------------------ */
+/* one work item of a grouped step: elements [off, off + cnt) of the flat arenas (multiples of 4, cnt <= 2048) and their two scales */
+typedef struct gget_group_item_t {
+  uint64_t off;
+  uint64_t cnt;
+  float lr_scale;
+  float wd_scale;
+} gget_group_item_t;
+/* replaces: the `lr` / `weight_decay` entries of torch parameter groups (loss_utils.py:383-386, :408-411).  n must equal
+ * gget_param_count; a NULL array means all ones; NULL, NULL, 0 switches the feature off (the state of a new handle).  Every scale must be
+ * finite and >= 0: a wrong n or a bad value is error 2 and nothing changes.  The table stays on the handle: gget_set_frozen and
+ * gget_shard_init apply it to the lists they build, and this call rebuilds theirs, so the call order does not matter.  Synchronous
+ * (uploads work-item tables).  The replicated step of an unfrozen model then runs over items covering the whole arena instead of the
+ * grid-stride launch. */
+int gget_set_param_scales(gget_handle_t h, const float* lr_scale, const float* wd_scale, int n);
+/* replaces: reading `optimizer.param_groups[i]["lr"]` back.  The table (ones while the feature is off) into lr_out / wd_out (either may
+ * be NULL); n must equal gget_param_count. */
+int gget_param_scales(gget_handle_t h, float* lr_out, float* wd_out, int n);
+/* replaces: nn.Module.named_parameters() before any device exists (what the reference's group builders walk): gget_param_count /
+ * gget_param_info from the configuration alone.  The count is -1 for a bad configuration. */
+int gget_plan_param_count(const gget_config_t* cfg);
+int gget_plan_param_info(const gget_config_t* cfg, int index, gget_param_info_t* out);
+/* replaces: nothing in the reference (torch iterates groups tensor by tensor); the handle-free twin of the lists above, as gget_shard_plan
+ * is of gget_shard_init: the work items the step of this configuration runs.  lr_scale / wd_scale / n as gget_set_param_scales (NULL,
+ * NULL, 0 = all ones); frozen_layers as gget_set_frozen; world = 0 the replicated step (gget_adamw_step), world >= 1 the sharded step
+ * of rank `rank`, rank = -1 every rank's share (the loopback communicator).  *n_out = the number of items; the first min(cap, *n_out)
+ * are written to items_out (cap = 0 with items_out NULL asks for the count).  Bad scales, n or ranks are error 2. */
+int gget_group_plan(const gget_config_t* cfg, const float* lr_scale, const float* wd_scale, int n, int frozen_layers, int world, int rank,
+                    gget_group_item_t* items_out, int cap, int32_t* n_out);
+
 /* Head bookkeeping of the last pre-train forward.  counts[0] = M (positions with >=1 masked
  * feature), counts[1] = Lm (masked feature tokens).  Synchronises `stream`.
  * logits: bf16 [Lm][ld] with ld = round_up(V,64) (pad columns are zero). */
