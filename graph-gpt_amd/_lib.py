@@ -209,6 +209,8 @@ SIGNATURES = {
     "gget_op_gemm_grouped_slab": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
     "gget_op_slab_reduce": (i32, [vp, i64, i32, vp, u64, i32, vp]),
     "gget_op_slab_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),
+    "gget_op_attn_bwd_rotated": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, f32, C.c_uint32, vp, u64, vp, vp]),
+    "gget_op_convert_segments": (i32, [vp, vp, vp, i32, vp]),
     "gget_op_rank_metrics_workspace": (C.c_size_t, [i32, i32]),
     "gget_op_rank_metrics": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "gget_op_link_hits_workspace": (C.c_size_t, [i32]),

@@ -618,6 +618,21 @@ extern "C" int gget_op_raw_tok_grad(const void* dx, const int32_t* flag, float* 
   GGET_REQUIRE(dx && flag && dtok && T >= 0 && e > 0, "raw_tok_grad: null argument or empty shape");
   return k_raw_tok_grad(dx, flag, dtok, T, e, (hipStream_t)stream);
 }
+// test-only entries of the step replay (tests/_step_replay.py): the launchers as the engine's step calls them, no arithmetic here
+extern "C" int gget_op_attn_bwd_rotated(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len,
+                                        const int32_t* row_base, void* dqkv, float* delta_ws, int B, int S, int H, int causal,
+                                        const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
+                                        uint32_t dropout_seed, void* dq_ws, uint64_t dq_slab_stride, const int32_t* long_list, void* stream) {
+  GGET_REQUIRE(qkv && dout && lse && dqkv && cos_tab && sin_tab, "attn_bwd_rotated: null argument");
+  GGET_REQUIRE(!long_list || row_base, "attn_bwd_rotated: the list of long samples belongs to the var-len layout");
+  return k_attn_bwd(qkv, out, dout, lse, key_len, dqkv, delta_ws, B, S, H, causal, cos_tab, sin_tab, position_ids, /*qk_rotated=*/1, dropout_p,
+                    dropout_seed, (hipStream_t)stream, nullptr, nullptr, row_base, dq_ws, (size_t)dq_slab_stride, long_list);
+}
+extern "C" int gget_op_convert_segments(const float* scratch, void* grads, const uint64_t* segs_dev, int nseg, void* stream) {
+  GGET_REQUIRE(scratch && grads && (segs_dev || nseg == 0) && nseg >= 0, "convert_segments: bad arguments");
+  static_assert(sizeof(GgetSegment) == 5 * sizeof(uint64_t), "gget_op_convert_segments: a segment is five uint64 (include/gget.h)");
+  return k_convert_segments(scratch, grads, reinterpret_cast<const GgetSegment*>(segs_dev), nseg, (hipStream_t)stream);
+}
 extern "C" int gget_op_gemm_indexed(int mode, const void* A, const void* B, void* C, int M_cap, int N, int K, int lda, int ldb, int ldc,
                                     const int32_t* m_dev, const int32_t* a_rows, const int32_t* b_tile_off, int b_tile_rows,
                                     const int32_t* c_rows, void* stream) {

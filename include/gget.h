@@ -1064,6 +1064,20 @@ int gget_op_slab_reduce(const float* slabs, int64_t slab_stride, int nslab, void
 #define GGET_SLAB_PLAN_QKVO 3      /* q|k|v + o at d % 192 != 0 */
 int gget_op_slab_plan(int which, int d, int V, int T, int* split);
 
+/* ---- test-only entries of the step replay (tests/_step_replay.py replays gget_forward_task + gget_backward launch by launch): the
+ * launchers as the engine's step calls them, no arithmetic of their own ---- */
+/* The attention backward on the engine's operands: q | k in `qkv` are ALREADY rotated (the q|k|v projection's RoPE epilogue), dq / dk are
+ * rotated back with cos_tab / sin_tab / position_ids ([B,S]-indexed).  row_base NULL = padded layout, else the var-len layout (needs
+ * key_len; long_list as gget_op_attn_bwd_varlen_list).  dq_ws / dq_slab_stride as gget_op_attn_bwd_fused, or NULL / 0. */
+int gget_op_attn_bwd_rotated(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len,
+                             const int32_t* row_base, void* dqkv, float* delta_ws, int B, int S, int H, int causal, const float* cos_tab,
+                             const float* sin_tab, const int64_t* position_ids, float dropout_p, uint32_t dropout_seed, void* dq_ws,
+                             uint64_t dq_slab_stride, const int32_t* long_list, void* stream);
+/* The fp32 accumulators -> bf16 gradients: segment i = segs_dev[5 i ..] = {src, dst, count, copies, stride} (uint64 elements: offset of
+ * replica 0 in `scratch`, offset in `grads`, elements - a multiple of 4 -, replicas to sum, elements between replicas);
+ * grads[dst + j] = bf16_rne(sum over the replicas of scratch[src + c stride + j]) in fp32, replica order.  nseg = 0: nothing. */
+int gget_op_convert_segments(const float* scratch, void* grads, const uint64_t* segs_dev, int nseg, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Rank metrics of the multi-label evaluation pass (csrc/metrics.hip; the Python surface is graph-gpt_amd/metrics.py rank_metrics).
  * replaces: MultiLabelClassificationMetrics.compute (src/utils/metrics_utils.py:112-114: torcheval BinaryAUROC over num_labels tasks),
