@@ -13,9 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgget_hip.so")
-SOURCES = ["engine.hip", "optimizer.hip", "comm.hip", "ops.hip", "residual.hip", "gemm.hip", "kernels.hip", "attention.hip", "menu.hip", "metrics.hip",
+SOURCES = ["engine.hip", "optimizer.hip", "comm.hip", "ops.hip", "residual.hip", "gemm.hip", "kernels.hip", "attention.hip", "attention32.hip", "menu.hip", "metrics.hip",
            "generation.hip", "infer.hip", "contrastive.hip"]
-HEADERS = ["common.h", "gemm.h", "kernels.h", "menu.h", "engine.h", os.path.join("..", "..", "include", "gget.h")]
+HEADERS = ["common.h", "attn_common.h", "gemm.h", "kernels.h", "menu.h", "engine.h", os.path.join("..", "..", "include", "gget.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # per-file extra flags (none at present; -fno-slp-vectorize on attention.hip was tried: forward unchanged, backward 2x slower)
 EXTRA_FLAGS = {}

@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "attn_common.h"
 #include <type_traits>
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -42,15 +43,6 @@ __device__ __forceinline__ int swz(int row, int byte_in_row) {
 
 // RoPE fused into the operand loads (hf apply_rotary_pos_emb :138-160, half-split pairing j <-> j+32): q and k stay
 // un-rotated in HBM; they are rotated in registers on the way into the MFMAs and dq/dk are rotated back on the way out.
-struct Rope {
-  const float* cos_tab;  // [max_pos][32] fp32, nullptr => no rotation (plain attention op)
-  const float* sin_tab;
-  const int64_t* pos;    // [B,S] or nullptr => position = index in the sequence
-  int S;
-};
-__device__ __forceinline__ int rope_pos(const Rope& R, int b, int s) {
-  return R.pos ? (int)R.pos[(size_t)b * R.S + s] : s;
-}
 // lo holds dh [j0, j0+8), up holds dh [j0+32, j0+40); rotate both in place by the angle table row `pos`
 __device__ __forceinline__ void rope_pair(uint4& lo, uint4& up, const Rope& R, int pos, int j0) {
   float a[8], b[8], c[8], sn[8];
@@ -71,15 +63,6 @@ __device__ __forceinline__ void rope_pair(uint4& lo, uint4& up, const Rope& R, i
   up = pack8(ob);
 }
 
-// Global loads of these helpers are UNCONDITIONAL: the row index is clamped into the sample ([0, row_lim - 1], at least 0) and rows
-// beyond the limit are zeroed with a select afterwards.  Written as `if (row < row_lim) v = load` the compiler branches around every
-// load and waits vmcnt(0) behind each one (round 3, ISA of the S <= 32 kernels: twelve serialised load -> wait -> ds_write round trips
-// per problem plus four for the V fragments - the kernels were bound by that chain, not by bytes); the RoPE test is made once per tile,
-// outside the chunk loops, for the same reason.
-__device__ __forceinline__ uint4 zero_if(bool dead, const uint4& v) {
-  return make_uint4(dead ? 0u : v.x, dead ? 0u : v.y, dead ? 0u : v.z, dead ? 0u : v.w);
-}
-__device__ __forceinline__ int clamp_row(int gr, int row_lim) { return max(min(gr, row_lim - 1), 0); }
 
 // [32 rows][64 dh] bf16 tile -> LDS (rows >= row_lim are zero-filled so masked probabilities never meet NaNs)
 __device__ __forceinline__ void load_tile(unsigned char* lds, const bf16_t* __restrict__ base, int r0, int row_lim,
@@ -203,61 +186,6 @@ __device__ __forceinline__ bf16x8_t frag_global(const bf16_t* __restrict__ base,
   const uint4 v = *reinterpret_cast<const uint4*>(base + (size_t)clamp_row(row, row_lim) * pitch + 16 * s + (lane >> 5) * 8);
   return __builtin_bit_cast(bf16x8_t, zero_if(row >= row_lim, v));
 }
-// Attention dropout (hf eager_attention_forward :210: dropout on the softmax output, training only; every reference
-// launch script sets attention_dropout=0.1).  Counter-based: the keep decision of element (batch*head, query, key) is a
-// hash of (seed, coordinates), so forward and the two backward kernels regenerate the same mask without storing it.
-struct Drop {
-  unsigned thresh;   // drop when the 16-bit field < thresh  (thresh = p * 2^16); 0 => no dropout
-  float inv_keep;    // 1 / (1 - p)
-  unsigned seed;
-};
-// One hash serves TWO scores: w(seed, bh, q, k >> 1) = mix((seed ^ bh*C0) + q*C1 + (k>>1)*C2), mix = one multiply between two
-// xor-shifts; key k uses the low (k even) or high (k odd) 16 bits of w.  The multiply is the full-rate 24-bit one (v_mul_u32_u24:
-// low 24 bits of the folded word x a 24-bit constant, low 32 bits of the product); a hash word is {v_add, v_xor sdwa, v_mul_u32_u24,
-// v_lshrrev, v_xor}.  (Round 3: replacing the quarter-rate 32-bit multiply changed NO kernel time - B16/S2048/H12 with p = 0.1: forward
-// 438.6 us, backward 1097 us before and after; what the dropout costs at head_dim 64 is its instruction COUNT beside the MFMAs, five
-// per score on top of 6.6, not the rate of any one of them.  The 24-bit mix stays for its better mask statistics.)
-// Measured on 3 x 6.3 M scores (tools/drop_hash_eval.py): drop rates 0.1000-0.1003 / 0.2997-0.3003 for
-// p = 0.1 / 0.3 in both fields; correlations between the two fields of a word, keys 1 / 2 apart, queries 1 / 2 apart, neighbouring
-// heads and the two diagonals all <= 1.5e-3 (noise floor 4e-4; the 32-bit multiply it replaces: <= 5e-3); per-row and per-column
-// drop-rate dispersion 0.98-1.02 of binomial.  In the kernels whose lanes walk along keys (forward, dQ) a lane's accumulator
-// registers come in (k, k+1) pairs, so one word serves two scores.  Callers pass the partial sum of everything fixed for the lane
-// (drop_base) and add the moving term.  tests/test_gpu_ops.py:_drop_mask is the Python twin.
-__device__ __forceinline__ unsigned drop_base(const Drop& D, unsigned bh, unsigned q_or_0, unsigned khalf_or_0) {
-  return (D.seed ^ (bh * 0x9E3779B1u)) + q_or_0 * 0x85EBCA77u + khalf_or_0 * 0xC2B2AE3Du;
-}
-__device__ __forceinline__ unsigned drop_word(unsigned x) {
-  x ^= x >> 16;
-  x = __umul24(x, 0x9E3779u);
-  x ^= x >> 15;
-  return x;
-}
-// keep-multiplier of key parity `odd` from the pair's hash word
-__device__ __forceinline__ float drop_mul_w(const Drop& D, unsigned w, int odd) {
-  const unsigned f = odd ? (w >> 16) : (w & 0xffffu);
-  return f < D.thresh ? 0.f : D.inv_keep;
-}
-// single score: x = drop_base(D, bh, q, 0) + (k >> 1) * C2 already summed by the caller
-__device__ __forceinline__ float drop_mul_x(const Drop& D, unsigned x, int odd) {
-  if (D.thresh == 0) return 1.f;
-  return drop_mul_w(D, drop_word(x), odd);
-}
-
-// Which keys a query may attend: right padding gives one length per batch row (key_len[b], keys [0, len)); packed rows
-// (several graphs back to back, block-diagonal [B,S,S] mask of reference src/utils/tokenizer_utils.py:349-355 /
-// modeling_helpers.py:51-64) give every token the inclusive key range [lo, hi] of its own graph.
-struct KeyRange {
-  const int32_t* key_len;   // [B] or nullptr (=> S); ignored when lo/hi are given
-  const int32_t* lo;        // [B,S] or nullptr
-  const int32_t* hi;        // [B,S]
-  // var-len (padding-free) token layout: first row of sample b in the token-major buffers (qkv / out / dout / dqkv); its rows are
-  // [row_base[b], row_base[b] + key_len[b]).  nullptr = padded layout, sample b at rows [b * S, b * S + S).  Logical [B,S] arrays
-  // (lse, delta, position ids, the dropout hash coordinates) keep their (b, s) indexing in both layouts.  Not combined with lo / hi.
-  const int32_t* row_base;
-};
-// wave-uniform min / max of small non-negative integers (exact in fp32)
-__device__ __forceinline__ int wave_imin(int v) { return (int)-wave_max(-(float)v); }
-__device__ __forceinline__ int wave_imax(int v) { return (int)wave_max((float)v); }
 
 // the 4 dh-fragments of one row (dh chunk [16s + 8hi, +8), s = 0..3), rotated: chunks s and s+2 are 32 channels apart
 __device__ __forceinline__ void frags_global_rope(bf16x8_t (&f)[4], const bf16_t* __restrict__ base, int row, int row_lim,
@@ -285,23 +213,6 @@ __device__ __forceinline__ bf16x8_t frag_tr(const unsigned char* lds, int dhb, i
   o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
   o[4] = up[0]; o[5] = up[1]; o[6] = up[2]; o[7] = up[3];
   return o;
-}
-// accumulator registers [8j, 8j+8) -> bf16 B operand (k = tile rows in the same order as frag_tr)
-__device__ __forceinline__ bf16x8_t acc_to_b(const f32x16_t& a, int j) {
-  uint4 v;
-  v.x = pack2bf(a[8 * j + 0], a[8 * j + 1]);
-  v.y = pack2bf(a[8 * j + 2], a[8 * j + 3]);
-  v.z = pack2bf(a[8 * j + 4], a[8 * j + 5]);
-  v.w = pack2bf(a[8 * j + 6], a[8 * j + 7]);
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-__device__ __forceinline__ int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-__device__ __forceinline__ f32x16_t zero16() {
-  f32x16_t z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
 }
 
 // store a transposed accumulator pair (O^T[dh][row]) as row-major bf16 [row][64 dh]; lane owns row (lane&31)
@@ -3325,20 +3236,17 @@ int attn_waves(int S) { return S >= 128 ? 4 : (S >= 64 ? 2 : 1); }
 bool attn_by_sample_rows() { return menu().attn_by_sample != 0; }
 constexpr int kLongGrid = 32;      // sample slots of a list-driven long launch (a block walks the list with this stride)
 
-Drop make_drop(float p, unsigned seed) {
-  Drop d;
-  d.thresh = p > 0.f ? (unsigned)(p * 65536.0f) : 0u;
-  d.inv_keep = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
-  d.seed = seed;
-  return d;
-}
-
 }  // namespace
 
 int k_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, int B, int S, int H, int causal,
                const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
                unsigned dropout_seed, hipStream_t st, const int32_t* key_lo, const int32_t* key_hi, const int32_t* row_base,
-               const int32_t* long_list) {
+               const int32_t* long_list, int head_dim) {
+  if (head_dim == 32) {     // the compact family of attention32.hip: q, k rotated in memory
+    GGET_REQUIRE(!cos_tab && !sin_tab, "attention: head_dim 32 takes q and k already rotated (no rotation on load)");
+    return k_attn32_fwd(qkv, key_len, out, lse, B, S, H, causal, dropout_p, dropout_seed, st, key_lo, key_hi, row_base);
+  }
+  GGET_REQUIRE(head_dim == 64, "attention: unsupported head_dim %d", head_dim);
   GGET_REQUIRE(!row_base || (key_len && !key_lo), "attention: the var-len token layout needs key_len and excludes per-token key ranges");
   const KeyRange KR{key_len, key_lo, key_hi, row_base};
   if (B == 0 || S == 0) return 0;
@@ -3379,7 +3287,10 @@ int k_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, i
 
 // attention weights of one layer from its rotated q | k and the forward's log-sum-exp (attn_probs_kernel); writes all of out [B,H,S,S]
 int k_attn_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
-                 const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed, hipStream_t st) {
+                 const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed, hipStream_t st,
+                 int head_dim) {
+  if (head_dim == 32) return k_attn32_probs(qkv, lse, key_len, row_base, key_lo, key_hi, out, B, S, H, causal, dropout_p, dropout_seed, st);
+  GGET_REQUIRE(head_dim == 64, "attn_probs: unsupported head_dim %d", head_dim);
   GGET_REQUIRE(qkv && lse && out, "attn_probs: null argument");
   GGET_REQUIRE(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attn_probs: bad shape B %d S %d H %d", B, S, H);
   GGET_REQUIRE(!key_lo == !key_hi, "attn_probs: half a key range");
@@ -3436,8 +3347,9 @@ static int launch_attn_oproj(const void* qkv, const int32_t* key_len, const int3
 }
 int k_attn_oproj_fwd(const void* qkv, const int32_t* key_len, const int32_t* row_base, void* attn_out, float* lse, const void* wo,
                      const void* x_in, void* x_mid, const void* nw, void* xn, float* rstd, int B, int S, int H, int causal, float eps,
-                     float dropout_p, unsigned dropout_seed, hipStream_t st, int* taken) {
+                     float dropout_p, unsigned dropout_seed, hipStream_t st, int* taken, int head_dim) {
   *taken = 0;
+  if (head_dim != 64) return 0;     // (the per-sample kernels hold 64-wide heads)
   // (S <= 32 only: a 33 .. 64-row sample inside this kernel - one workgroup over two row tiles - was built and measured slower than the
   //  three launches, profiles/r06_attn_oproj_fwd_long_experiment.diff; the backward counterpart is kept)
   if (B == 0 || S == 0 || S > 32 || !attn_oproj_enabled()) return 0;
@@ -3475,8 +3387,9 @@ int k_attn_oproj_bwd(const void* dxn, const void* x_mid, const void* nw, const f
                      int copies, uint64_t copy_stride, const void* wot_packed, const void* qkv, const float* lse, const int32_t* key_len,
                      const int32_t* row_base, void* dqkv, int B, int S, int H, int causal, const float* cos_tab, const float* sin_tab,
                      const int64_t* position_ids, float dropout_p, unsigned dropout_seed, int t_rows, hipStream_t st, int* taken,
-                     void* dattn_long, const int32_t* long_list) {
+                     void* dattn_long, const int32_t* long_list, int head_dim) {
   *taken = 0;
+  if (head_dim != 64) return 0;     // (the per-sample kernels hold 64-wide heads)
   // S <= 32, or - var-len layout, with room for the long samples' dattn rows - S <= 64: every sample by its own row count
   if (B == 0 || S == 0 || S > 64 || (S > 32 && (!row_base || !dattn_long || !attn_by_sample_rows())) || !attn_oproj_enabled())
     return 0;
@@ -3518,7 +3431,13 @@ int k_attn_bwd(const void* qkv, const void* out, const void* dout, const float* 
                float* delta_ws, int B, int S, int H, int causal, const float* cos_tab, const float* sin_tab,
                const int64_t* position_ids, int qk_rotated, float dropout_p, unsigned dropout_seed, hipStream_t st,
                const int32_t* key_lo, const int32_t* key_hi, const int32_t* row_base, void* dq_ws, size_t dq_slab_stride,
-               const int32_t* long_list) {
+               const int32_t* long_list, int head_dim) {
+  if (head_dim == 32) {     // the compact family of attention32.hip: q, k rotated in memory, the tables only rotate dq / dk back
+    GGET_REQUIRE(!cos_tab || qk_rotated, "attention: head_dim 32 takes q and k already rotated (no rotation on load)");
+    return k_attn32_bwd(qkv, out, dout, lse, key_len, dqkv, delta_ws, B, S, H, causal, cos_tab, sin_tab, position_ids, dropout_p, dropout_seed,
+                        st, key_lo, key_hi, row_base);
+  }
+  GGET_REQUIRE(head_dim == 64, "attention: unsupported head_dim %d", head_dim);
   GGET_REQUIRE(!row_base || (key_len && !key_lo), "attention: the var-len token layout needs key_len and excludes per-token key ranges");
   const KeyRange KR{key_len, key_lo, key_hi, row_base};
   if (B == 0 || S == 0) return 0;

@@ -75,7 +75,8 @@ struct Ws {
   uint64_t tlogits, tdlogits, pooled_h, auc_lists;
   uint64_t cl_z = 0, cl_e = 0, cl_dz = 0, cl_rn = 0, cl_stat = 0, cl_loss = 0;   // contrastive head (make_ws)
   uint64_t raw_x, raw_xn, raw_rstd, raw_dxn, raw_dx, raw_flag;   // raw-embedding inputs: blended bf16 [T,e], normalised [T,e], 1/rms [T], their gradients, mask flags [T]
-  uint64_t rr_cos, rr_sin, rr_ids;   // rope_range: per-token angle tables [T][32] fp32 and the identity position list [T] int64
+  uint64_t qkv32 = 0;                // head width 32: the q | k | v projection's fp32 accumulators [T][3 d], rotated and rounded once by rope32_f32_kernel
+  uint64_t rr_cos, rr_sin, rr_ids;   // rope_range: per-token angle tables [T][head_dim / 2] fp32 (room for 32 columns) and the identity position list [T] int64
   uint64_t tok_stat;   // token-level head: loss sum, labelled rows, 1 / rows
   uint64_t intra_rs, intra_cls;   // intra-instance token head: first row of every sample (int32 [max_batch + 1]), cls_idx clamped (int64 [max_batch])
   uint64_t long_wgt;   // stack_method = "long": per-sample loss weights (fp32 [max_batch])

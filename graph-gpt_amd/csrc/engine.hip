@@ -205,6 +205,7 @@ Ws make_ws(const gget_config_t& c, const Plan& pl) {
   w.dgu = b.take(T * 2 * ff * 2);
   w.dh = b.take(T * ff * 2);
   w.delta = b.take(T * H * 4);
+  if (c.num_heads * 32 == c.hidden_size) w.qkv32 = b.take(T * 3 * d * 4);     // head width 32: fp32 q | k | v of the layer being projected
   {   // long sequences: the key blocks' dQ partials of the fused attention backward, bf16 [ceil(S / 256)][T][d]
     const uint64_t Smax = c.max_tokens / (c.max_batch > 0 ? c.max_batch : 1);
     w.dq_acc = Smax >= 256 ? b.take(((Smax + 255) / 256) * T * d * 2) : 0;
@@ -228,7 +229,7 @@ Ws make_ws(const gget_config_t& c, const Plan& pl) {
   w.vl_ids = b.take(T * (uint64_t)c.stacked_feat * 8);
   w.vl_pad2c = b.take(T * 4);
   w.vl_c2p = b.take(T * 4);
-  if (d % 64 == 0 && !pl.has_res) {
+  if (d % 64 == 0 && !pl.has_res && c.num_heads * 64 == c.hidden_size) {     // (the per-sample kernels hold 64-wide heads)
     w.wo_pack = b.take((uint64_t)c.num_layers * d * d * 2);
     w.wot_pack = b.take((uint64_t)c.num_layers * d * d * 2);
   }
@@ -314,7 +315,8 @@ Ws make_ws(const gget_config_t& c, const Plan& pl) {
 int check_cfg(const gget_config_t* c) {
   GGET_REQUIRE(c != nullptr, "null config");
   GGET_REQUIRE(c->hidden_size > 0 && c->hidden_size % 64 == 0, "hidden_size must be a positive multiple of 64");
-  GGET_REQUIRE(c->num_heads * 64 == c->hidden_size, "num_heads*64 must equal hidden_size (head_dim is 64)");
+  GGET_REQUIRE(c->num_heads > 0 && (c->num_heads * 64 == c->hidden_size || c->num_heads * 32 == c->hidden_size),
+               "unsupported head_dim: hidden_size must equal num_heads*64 or num_heads*32");
   GGET_REQUIRE(c->intermediate_size > 0 && c->intermediate_size % 64 == 0, "intermediate_size must be a multiple of 64");
   GGET_REQUIRE(c->hidden_size <= 2048, "hidden_size > 2048 not supported by the norm kernels");
   GGET_REQUIRE(c->vocab_size > 1 && c->num_layers >= 1 && c->stacked_feat >= 1, "bad vocab/layers/stacked_feat");
@@ -420,7 +422,7 @@ extern "C" int gget_create(const gget_config_t* cfg, const gget_buffers_t* bufs,
   } else {
     float* ct = h->wsp<float>(h->ws.cos_tab);
     float* st = h->wsp<float>(h->ws.sin_tab);
-    if (k_rope_table(ct, st, cfg->max_position, cfg->rope_theta, nullptr)) { delete h; return 1; }
+    if (k_rope_table_hd(ct, st, cfg->max_position, cfg->rope_theta, cfg->hidden_size / cfg->num_heads, nullptr)) { delete h; return 1; }
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) { gget_set_error("rope table: %s", hipGetErrorString(e)); delete h; return 1; }
     h->cos_tab = ct;
@@ -674,7 +676,17 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
   // (LayerScale / DropPath path: the previous layer's residual kernel already normalised this layer's input - see below)
   if (!(h->plan.has_res && i > 0 && ls_norm_fused()))
     if (int e = k_rmsnorm_fwd(x_in, h->P + lo.ln1, xn1, h->wsp<float>(lw.rstd1), T, d, c.rms_eps, st)) return e;
-  {
+  const int hd = d / H;     // head width: 64, or 32 (tiny6 / small12)
+  if (hd == 32) {
+    // head width 32: the RoPE epilogue holds one 64-column head per wave, so the projection leaves its fp32 accumulators in a scratch
+    // buffer (the fp32 slab epilogue, one slab) and one kernel rotates the q and k columns in fp32 and rounds q, k, v to bf16 - ONE
+    // rounding, the cast points of the epilogue below; qkv holds ROTATED q, k
+    float* q32 = h->wsp<float>(h->ws.qkv32);
+    if (int e = gget_gemm_single(GGET_GEMM_NT, GGET_EPI_SLAB_F32, xn1, h->P + lo.wqkv, q32, nullptr, T, 3 * d, d, d, d, 3 * d, nullptr, nullptr,
+                                 1, st))
+      return e;
+    if (int e = k_rope32_f32(q32, qkv, h->cos_cur, h->sin_cur, h->pos_rows, T, h->S, H, st)) return e;
+  } else {
     // q|k|v projection with RoPE applied to the q and k columns in the GEMM epilogue (fp32 accumulators, one rounding):
     // qkv holds ROTATED q,k; attention consumes them as they are, its backward rotates dq,dk back.
     GemmGroup g;
@@ -694,7 +706,7 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
     if (int e = k_attn_oproj_fwd(qkv, h->wsp<int32_t>(h->ws.key_len), h->row_base(), attn, h->wsp<float>(lw.lse),
                                  h->wsp<bf16_t>(h->ws.wo_pack) + (size_t)i * d * d, x_in, xmid,
                                  h->P + lo.ln2, xn2, h->wsp<float>(lw.rstd2), h->B, h->S, H, c.causal, c.rms_eps, h->attn_drop_p,
-                                 h->attn_drop_seed + 0x9E37u * (unsigned)i, st, &taken))
+                                 h->attn_drop_seed + 0x9E37u * (unsigned)i, st, &taken, hd))
       return e;
     if (taken) {
       if (h->probe) GGET_HIP_CHECK(hipEventRecord(h->probe_event(1, 2 * i), st));
@@ -705,7 +717,7 @@ int layer_forward(gget_engine* h, int i, hipStream_t st) {
   }
   if (int e = k_attn_fwd(qkv, h->wsp<int32_t>(h->ws.key_len), attn, h->wsp<float>(lw.lse), h->B, h->S, H, c.causal,
                          nullptr, nullptr, nullptr, h->attn_drop_p, h->attn_drop_seed + 0x9E37u * (unsigned)i, st, h->klo(),
-                         h->khi(), h->row_base(), h->long_list()))
+                         h->khi(), h->row_base(), h->long_list(), hd))
     return e;
   if (h->plan.has_res) {
     bf16_t* araw = h->wsp<bf16_t>(lw.araw);
@@ -791,7 +803,8 @@ int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, 
     const int ncu = gget_gemm_num_cu() > 0 ? gget_gemm_num_cu() : 256;
     const int rounds = (B + ncu - 1) / ncu;
     const bool rounds_ok = B <= ncu || (long)B * 100 >= (long)rounds * ncu * 85;
-    if (!h->plan.has_res && !mask_is_3d && (S <= 32 || (S <= 64 && may_varlen)) && rounds_ok && h->ws.wo_pack && c.num_layers > 0) {
+    if (!h->plan.has_res && !mask_is_3d && (S <= 32 || (S <= 64 && may_varlen)) && rounds_ok && h->ws.wo_pack && c.num_layers > 0 &&
+        c.num_heads * 64 == d) {
       const size_t stride = c.num_layers > 1 ? h->plan.layers[1].wo - h->plan.layers[0].wo : 0;
       bool regular = true;
       for (int i = 0; i < c.num_layers; ++i) regular = regular && h->plan.layers[i].wo == h->plan.layers[0].wo + (size_t)i * stride;
@@ -874,8 +887,8 @@ int backbone_forward(gget_engine* h, long tc_hint, const int64_t* ids, int ldF, 
   }
   if (int e = early_work()) return e;
   if (h->rope_range > 0.f && pos) {
-    if (int e = k_rope_range_table(pos, h->wsp<float>(h->ws.rr_cos), h->wsp<float>(h->ws.rr_sin), h->wsp<int64_t>(h->ws.rr_ids), B, S,
-                                   h->rope_range, c.rope_theta > 0.f ? c.rope_theta : 10000.0f, st))
+    if (int e = k_rope_range_table_hd(pos, h->wsp<float>(h->ws.rr_cos), h->wsp<float>(h->ws.rr_sin), h->wsp<int64_t>(h->ws.rr_ids), B, S,
+                                      h->rope_range, c.rope_theta > 0.f ? c.rope_theta : 10000.0f, d / c.num_heads, st))
       return e;
     h->cos_cur = h->wsp<float>(h->ws.rr_cos); h->sin_cur = h->wsp<float>(h->ws.rr_sin); h->pos_cur = h->wsp<int64_t>(h->ws.rr_ids);
   }
@@ -1252,7 +1265,7 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
                                  align_up((uint64_t)d, 128), h->wsp<bf16_t>(w.wot_pack) + (size_t)i * d * d, h->wsp<bf16_t>(lw.qkv),
                                  h->wsp<float>(lw.lse), h->wsp<int32_t>(w.key_len), h->row_base(), dqkv, h->B, h->S, H, c.causal, h->cos_cur,
                                  h->sin_cur, h->pos_cur, h->attn_drop_p, h->attn_drop_seed + 0x9E37u * (unsigned)i, T, st, &taken,
-                                 dattn, h->long_list()))     // (dattn: only the rows of 33 .. 64-row samples are written, for their own launch)
+                                 dattn, h->long_list(), d / H))     // (dattn: only the rows of 33 .. 64-row samples are written, for their own launch)
       return e;
     front_fused = taken != 0;
   }
@@ -1284,7 +1297,7 @@ int layer_backward(gget_engine* h, int i, hipStream_t st) {
                          h->klo(), h->khi(), h->row_base(),
                          /* the slabs were sized for ceil(max_tokens / max_batch / 256) key blocks: a call with fewer, longer rows keeps the two-kernel form */
                          (w.dq_acc && (uint64_t)(h->S + 255) / 256 <= (c.max_tokens / (c.max_batch > 0 ? c.max_batch : 1) + 255) / 256) ? h->wsp<bf16_t>(w.dq_acc) : nullptr,
-                         (size_t)c.max_tokens * d, h->long_list()))
+                         (size_t)c.max_tokens * d, h->long_list(), d / H))
     return e;
   if (int e = gemm_nn(dqkv, h->P + lo.wqkv, dxn, T, d, 3 * d, 3 * d, d, d, nullptr, st)) return e;
   // (fused with the LayerScale backward of the layer below, this RMSNorm backward writes w.dscaled - which this layer's down_proj weight
@@ -1729,7 +1742,7 @@ extern "C" int gget_attention_probs(gget_handle_t h, int layer, void* out_dev, i
   const LayerWs& lw = h->ws.lw[layer];
   return k_attn_probs(h->wsp<bf16_t>(lw.qkv), h->wsp<float>(lw.lse), h->packed ? nullptr : h->wsp<int32_t>(h->ws.key_len), h->row_base(),
                       h->klo(), h->khi(), out_dev, h->B, h->S, h->cfg.num_heads, h->cfg.causal, apply_dropout ? h->attn_drop_p : 0.f,
-                      h->attn_drop_seed + 0x9E37u * (unsigned)layer, (hipStream_t)stream);
+                      h->attn_drop_seed + 0x9E37u * (unsigned)layer, (hipStream_t)stream, h->cfg.hidden_size / h->cfg.num_heads);
 }
 
 // The rotated q | k | v of decoder layer `layer` of the last forward as a copy in the [B, S, 3 d] layout, from either token layout (the

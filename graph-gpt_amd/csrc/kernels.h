@@ -241,11 +241,14 @@ int k_convert_segments(const float* scratch, void* grads, const GgetSegment* seg
 int k_attn_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, int B, int S, int H, int causal,
                const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
                unsigned dropout_seed, hipStream_t st, const int32_t* key_lo = nullptr, const int32_t* key_hi = nullptr,
-               const int32_t* row_base = nullptr, const int32_t* long_list = nullptr);
+               const int32_t* row_base = nullptr, const int32_t* long_list = nullptr, int head_dim = 64);
+// head_dim (k_attn_fwd / _bwd / _probs): 64, or 32 - routed at the top to the compact family of attention32.hip (q, k rotated in qkv, no
+// rotation on load; H = hidden / 32; angle tables [max_pos][16])
 // attention weights of one layer, bf16 [B,H,S,S] = m * exp(q k / 8 - lse) on the allowed keys, 0 elsewhere (attention.hip:
 // attn_probs_kernel); qkv holds rotated q | k; row_base != NULL: var-len token layout; key_lo / key_hi != NULL: packed rows
 int k_attn_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
-                 const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed, hipStream_t st);
+                 const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed, hipStream_t st,
+                 int head_dim = 64);
 // q | k | v rows of a layer copied into the [B, S, w] grid from either token layout, zeros behind a sample's tokens
 int k_qkv_grid(const void* src, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo, const int32_t* key_hi, void* out,
                int B, int S, int w, hipStream_t st);
@@ -263,15 +266,33 @@ int k_attn_oproj_bwd(const void* dxn, const void* x_mid, const void* nw, const f
                      int copies, uint64_t copy_stride, const void* wot_packed, const void* qkv, const float* lse, const int32_t* key_len,
                      const int32_t* row_base, void* dqkv, int B, int S, int H, int causal, const float* cos_tab, const float* sin_tab,
                      const int64_t* position_ids, float dropout_p, unsigned dropout_seed, int t_rows, hipStream_t st, int* taken,
-                     void* dattn_long = nullptr, const int32_t* long_list = nullptr);   // t_rows: rows of the token-major buffers (var-len: the pad rows behind the last sample get a zero dx_mid)
+                     void* dattn_long = nullptr, const int32_t* long_list = nullptr, int head_dim = 64);   // (head_dim 32: *taken = 0) t_rows: rows of the token-major buffers (var-len: the pad rows behind the last sample get a zero dx_mid)
 int k_attn_oproj_fwd(const void* qkv, const int32_t* key_len, const int32_t* row_base, void* attn_out, float* lse, const void* wo,
                      const void* x_in, void* x_mid, const void* nw, void* xn, float* rstd, int B, int S, int H, int causal, float eps,
-                     float dropout_p, unsigned dropout_seed, hipStream_t st, int* taken);
+                     float dropout_p, unsigned dropout_seed, hipStream_t st, int* taken, int head_dim = 64);
 int k_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len, void* dqkv,
                float* delta_ws, int B, int S, int H, int causal, const float* cos_tab, const float* sin_tab,
                const int64_t* position_ids, int qk_rotated, float dropout_p, unsigned dropout_seed, hipStream_t st,
                const int32_t* key_lo = nullptr, const int32_t* key_hi = nullptr, const int32_t* row_base = nullptr,
-               void* dq_ws = nullptr, size_t dq_slab_stride = 0, const int32_t* long_list = nullptr);   // dq_ws: bf16 [ceil(S / 256)][dq_slab_stride >= rows * H * 64] - S >= 256 (GGET_ATTN_FUSED_MIN_S) then runs the fused one-pass backward (attention.hip)
+               void* dq_ws = nullptr, size_t dq_slab_stride = 0, const int32_t* long_list = nullptr, int head_dim = 64);   // dq_ws: bf16 [ceil(S / 256)][dq_slab_stride >= rows * H * 64] - S >= 256 (GGET_ATTN_FUSED_MIN_S) then runs the fused one-pass backward (attention.hip)
+// attention32.hip: the head-width-32 family behind the three entries above, its in-place RoPE on the q and k columns of qkv [T, 3 d]
+// (pair distance 16, tables [max_pos][16]) and the angle tables of either width ([max_pos or tokens][head_dim / 2])
+int k_attn32_fwd(const void* qkv, const int32_t* key_len, void* out, float* lse, int B, int S, int H, int causal, float dropout_p,
+                 unsigned dropout_seed, hipStream_t st, const int32_t* key_lo, const int32_t* key_hi, const int32_t* row_base);
+int k_attn32_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len, void* dqkv, float* delta_ws,
+                 int B, int S, int H, int causal, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
+                 unsigned dropout_seed, hipStream_t st, const int32_t* key_lo, const int32_t* key_hi, const int32_t* row_base);
+int k_attn32_probs(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                   const int32_t* key_hi, void* out, int B, int S, int H, int causal, float dropout_p, unsigned dropout_seed,
+                   hipStream_t st);
+int k_rope32(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H, int inverse,
+             hipStream_t st);
+// fp32 q | k | v [T, 3 d] (the projection's accumulators) -> bf16 qkv with q, k rotated: one rounding
+int k_rope32_f32(const float* src, void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int T, int S, int H,
+                 hipStream_t st);
+int k_rope_table_hd(float* cos_tab, float* sin_tab, int max_pos, float theta, int head_dim, hipStream_t st);
+int k_rope_range_table_hd(const int64_t* pos, float* cos_t, float* sin_t, int64_t* ids, int B, int S, float range, float theta, int head_dim,
+                          hipStream_t st);
 // row_base ([B] int32, needs key_len): var-len (padding-free) token layout - sample b owns rows [row_base[b], row_base[b] + key_len[b]) of
 // qkv / out / dout / dqkv instead of [b * S, b * S + S); lse / delta / position ids stay [B,S]-indexed.
 // packed rows: inclusive key range [lo, hi] of every token from the block-diagonal mask [B,S,S] (first / last 1 of its row)

@@ -291,6 +291,58 @@ extern "C" int gget_op_attn_probs(const void* qkv, const float* lse, const int32
                                   void* stream) {
   return k_attn_probs(qkv, lse, key_len, row_base, key_lo, key_hi, out, B, S, H, causal, dropout_p, dropout_seed, (hipStream_t)stream);
 }
+// The head-width-parameterised entries: head_dim 64 forwards to the kernels above with the same arguments (q, k rotated in qkv), 32 runs
+// the family of attention32.hip.  Every check is made here, before any launch.
+static int hd_check(const char* who, int B, int S, int H, int head_dim, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                    const int32_t* key_hi) {
+  GGET_REQUIRE(head_dim == 64 || head_dim == 32, "%s: unsupported head_dim %d (64 or 32)", who, head_dim);
+  GGET_REQUIRE(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "%s: bad shape B %d S %d H %d", who, B, S, H);
+  GGET_REQUIRE(!key_lo == !key_hi, "%s: half a key range", who);
+  GGET_REQUIRE(!row_base || (key_len && !key_lo), "%s: the var-len token layout needs key_len and excludes per-token key ranges", who);
+  return 0;
+}
+extern "C" int gget_op_rope_hd(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B, int S, int H,
+                               int head_dim, int inverse, void* stream) {
+  GGET_REQUIRE(head_dim == 64 || head_dim == 32, "rope_hd: unsupported head_dim %d (64 or 32)", head_dim);
+  GGET_REQUIRE(qkv && cos_tab && sin_tab, "rope_hd: null argument");
+  GGET_REQUIRE(B > 0 && S > 0 && H > 0, "rope_hd: bad shape B %d S %d H %d", B, S, H);
+  if (head_dim == 64) return k_rope(qkv, cos_tab, sin_tab, position_ids, B * S, S, H, inverse, (hipStream_t)stream);
+  return k_rope32(qkv, cos_tab, sin_tab, position_ids, B * S, S, H, inverse, (hipStream_t)stream);
+}
+extern "C" int gget_op_rope_f32_hd(const float* src, void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B,
+                                   int S, int H, int head_dim, void* stream) {
+  GGET_REQUIRE(head_dim == 32, "rope_f32_hd: unsupported head_dim %d (32: the 64-wide projection rotates in its GEMM epilogue)", head_dim);
+  GGET_REQUIRE(src && qkv && cos_tab && sin_tab, "rope_f32_hd: null argument");
+  GGET_REQUIRE(B > 0 && S > 0 && H > 0, "rope_f32_hd: bad shape B %d S %d H %d", B, S, H);
+  return k_rope32_f32(src, qkv, cos_tab, sin_tab, position_ids, B * S, S, H, (hipStream_t)stream);
+}
+extern "C" int gget_op_attn_fwd_hd(const void* qkv, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                                   const int32_t* key_hi, void* out, float* lse, int B, int S, int H, int head_dim, int causal,
+                                   float dropout_p, uint32_t dropout_seed, void* stream) {
+  if (int e = hd_check("attn_fwd_hd", B, S, H, head_dim, key_len, row_base, key_lo, key_hi)) return e;
+  GGET_REQUIRE(qkv && out && lse, "attn_fwd_hd: null argument");
+  return k_attn_fwd(qkv, key_lo ? nullptr : key_len, out, lse, B, S, H, causal, nullptr, nullptr, nullptr, dropout_p, dropout_seed,
+                    (hipStream_t)stream, key_lo, key_hi, row_base, nullptr, head_dim);
+}
+extern "C" int gget_op_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len,
+                                   const int32_t* row_base, const int32_t* key_lo, const int32_t* key_hi, void* dqkv, float* delta_ws, int B,
+                                   int S, int H, int head_dim, int causal, const float* cos_tab, const float* sin_tab,
+                                   const int64_t* position_ids, float dropout_p, uint32_t dropout_seed, void* stream) {
+  if (int e = hd_check("attn_bwd_hd", B, S, H, head_dim, key_len, row_base, key_lo, key_hi)) return e;
+  GGET_REQUIRE(qkv && out && dout && lse && dqkv && delta_ws, "attn_bwd_hd: null argument");
+  GGET_REQUIRE(!cos_tab == !sin_tab, "attn_bwd_hd: half an angle table");
+  return k_attn_bwd(qkv, out, dout, lse, key_lo ? nullptr : key_len, dqkv, delta_ws, B, S, H, causal, cos_tab, sin_tab, position_ids,
+                    /*qk_rotated=*/1, dropout_p, dropout_seed, (hipStream_t)stream, key_lo, key_hi, row_base, nullptr, 0, nullptr, head_dim);
+}
+extern "C" int gget_op_attn_probs_hd(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                                     const int32_t* key_hi, void* out, int B, int S, int H, int head_dim, int causal, float dropout_p,
+                                     uint32_t dropout_seed, void* stream) {
+  if (int e = hd_check("attn_probs_hd", B, S, H, head_dim, key_len, row_base, key_lo, key_hi)) return e;
+  GGET_REQUIRE(qkv && lse && out, "attn_probs_hd: null argument");
+  GGET_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attn_probs_hd: dropout_p %g outside [0, 1)", (double)dropout_p);
+  return k_attn_probs(qkv, lse, key_len, row_base, key_lo, key_hi, out, B, S, H, causal, dropout_p, dropout_seed, (hipStream_t)stream,
+                      head_dim);
+}
 extern "C" int gget_op_ranges_from_mask3d(const int64_t* mask3d, int32_t* key_lo, int32_t* key_hi, int B, int S, void* stream) {
   GGET_REQUIRE(mask3d && key_lo && key_hi, "ranges_from_mask3d: null argument");
   return k_ranges_from_mask3d(mask3d, key_lo, key_hi, B, S, (hipStream_t)stream);

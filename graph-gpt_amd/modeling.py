@@ -85,7 +85,9 @@ class GraphGPTConfig:
             if not cond:
                 raise NotImplementedError(f"gget engine: {msg} (out of the hot-path scope, see DESIGN.md)")
         need(self.hidden_act == "gelu", f"hidden_act={self.hidden_act!r}; the reference configs use exact-erf 'gelu'")
-        need(self.head_dim == 64 and self.hidden_size == 64 * self.num_attention_heads, "head_dim must be 64")
+        need(self.head_dim in (32, 64) and self.hidden_size == self.head_dim * self.num_attention_heads,
+             f"head_dim={self.head_dim} with hidden_size={self.hidden_size}, num_attention_heads={self.num_attention_heads}: head_dim must be "
+             "64 or 32 and head_dim * num_attention_heads == hidden_size")
         need(self.num_key_value_heads == self.num_attention_heads, "GQA (num_key_value_heads != num_attention_heads) is not used by the reference configs")
         need(not self.attention_bias, "attention_bias=True (biased q/k/v/o projections)")
         need(not self.mlp_bias, "mlp_bias=True (biased gate/up/down projections)")
@@ -106,7 +108,7 @@ class GraphGPTConfig:
         need(self.pooling_method == "last", "pooling other than 'last'")
         return ModelSpec(kind=kind, vocab_size=self.vocab_size, hidden_size=self.hidden_size,
                          intermediate_size=self.intermediate_size, num_layers=self.num_hidden_layers,
-                         num_heads=self.num_attention_heads, head_dim=64, stacked_feat=self.stacked_feat,
+                         num_heads=self.num_attention_heads, head_dim=int(self.head_dim), stacked_feat=self.stacked_feat,
                          next_n_token=self.next_n_token if kind in (KIND_PRETRAIN, KIND_PRETRAIN_CL) else 1,
                          gated_agg=self.stacked_feat_agg_method == "gated", causal=bool(self.causal_attention),
                          rms_eps=self.rms_norm_eps, rope_theta=self.rope_theta, max_position=self.max_position_embeddings,

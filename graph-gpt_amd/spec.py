@@ -51,8 +51,10 @@ class ModelSpec:
         return self.kind in (KIND_PRETRAIN, KIND_PRETRAIN_CL)
 
     def __post_init__(self):
-        assert self.hidden_size == self.num_heads * self.head_dim, "no GQA / odd head dims on this path"
-        assert self.head_dim == 64, "reference fixes head_dim = 64 (src/utils/modules_utils.py:37-42)"
+        assert self.head_dim in (32, 64), (f"head_dim={self.head_dim}: the attention kernels hold head_dim 64 (src/utils/modules_utils.py:37-42) "
+                                           "and 32 (the tiny6 / small12 sizes of the launch scripts)")
+        assert self.hidden_size == self.num_heads * self.head_dim, (
+            f"head_dim={self.head_dim} * num_heads={self.num_heads} != hidden_size={self.hidden_size}: no GQA / odd head dims on this path")
 
     # ------------------------------------------------------------------ parameter table
     def param_table(self) -> "OrderedDict[str, Tuple[int, ...]]":
@@ -118,8 +120,11 @@ class ModelSpec:
                 self.max_position, self.num_labels, int(self.score_bias), self.pad_token_id]
 
 
-# Model-size table of the reference launch scripts (examples/graph_lvl/pcqm4m_v2_pretrain.sh:159-202)
+# Model-size table of the reference launch scripts (examples/graph_lvl/pcqm4m_v2_pretrain.sh:158-240).  A row without num_heads /
+# intermediate_size has 64-wide heads and a 4 d MLP; tiny6 and small12 are the two rows with 32-wide heads.
 MODEL_SIZES: Dict[str, Dict[str, int]] = {
+    "tiny6": dict(hidden_size=128, num_layers=6, num_heads=4, intermediate_size=512),
+    "small12": dict(hidden_size=384, num_layers=12, num_heads=12, intermediate_size=384),
     "tiny": dict(hidden_size=128, num_layers=2),
     "mini": dict(hidden_size=256, num_layers=4),
     "small": dict(hidden_size=512, num_layers=4),
@@ -133,5 +138,6 @@ MODEL_SIZES: Dict[str, Dict[str, int]] = {
 def spec_from_size(name: str, **kw) -> ModelSpec:
     sz = MODEL_SIZES[name]
     d = sz["hidden_size"]
-    return ModelSpec(hidden_size=d, intermediate_size=4 * d, num_layers=sz["num_layers"],
-                     num_heads=d // 64, head_dim=64, **kw)
+    heads = sz.get("num_heads", d // 64)
+    return ModelSpec(hidden_size=d, intermediate_size=sz.get("intermediate_size", 4 * d), num_layers=sz["num_layers"],
+                     num_heads=heads, head_dim=d // heads, **kw)

@@ -48,7 +48,8 @@ typedef struct gget_config_t {
   int32_t hidden_size;    /* d, multiple of 64 */
   int32_t intermediate_size; /* ff, multiple of 64 */
   int32_t num_layers;
-  int32_t num_heads;      /* d / 64 (head_dim is 64: src/utils/modules_utils.py:37-42) */
+  int32_t num_heads;      /* d / 64 (head_dim 64: src/utils/modules_utils.py:37-42) or d / 32 (the tiny6 / small12 sizes of the launch
+                           * scripts, hf head_dim = hidden_size / num_attention_heads); the head width is hidden_size / num_heads */
   int32_t stacked_feat;   /* F */
   int32_t next_n_token;   /* pre-train: F; 1 => n_token_proj is Identity */
   int32_t gated_agg;      /* stacked_feat_agg_method == "gated" */
@@ -86,7 +87,8 @@ typedef struct gget_buffers_t {
   void* adam_v_dev;
   void* grad_bf16_dev;
   void* workspace_dev;
-  const float* rope_cos_dev; /* [max_position][32] fp32, hf LlamaRotaryEmbedding tables; NULL => engine computes */
+  const float* rope_cos_dev; /* [max_position][head_dim / 2] fp32 (32 columns at head width 64, 16 at 32), hf LlamaRotaryEmbedding
+                              * tables; NULL => engine computes */
   const float* rope_sin_dev;
 } gget_buffers_t;
 
@@ -690,7 +692,8 @@ int gget_op_embed_bwd(const int64_t* ids, const void* dx, const void* emb, const
                       float* dgate_accum, int T, int F, int ldF, int d, int V, int pad_id, void* stream);
 int gget_op_rope(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B, int S,
                  int H, int inverse, void* stream);
-/* cos_tab/sin_tab ([max_pos][32] fp32, hf LlamaRotaryEmbedding tables) non-NULL: RoPE (hf apply_rotary_pos_emb
+/* (head_dim 64 in these entries; either width: the _hd forms below.)
+ * cos_tab/sin_tab ([max_pos][32] fp32, hf LlamaRotaryEmbedding tables) non-NULL: RoPE (hf apply_rotary_pos_emb
  * :138-160) is applied to q,k inside the kernels and undone on dq,dk; qkv / dqkv are the UN-rotated projections.
  * dropout_p > 0: attention dropout on the softmax output (hf eager_attention_forward :210), counter-based mask
  * keyed by (dropout_seed, batch*head, query, key) - see drop_mul() in csrc/attention.hip.
@@ -720,6 +723,34 @@ int gget_op_attn_bwd(const void* qkv, const void* out, const void* dout, const f
                      void* dqkv, float* delta_ws, int B, int S, int H, int causal, const float* cos_tab,
                      const float* sin_tab, const int64_t* position_ids, float dropout_p, uint32_t dropout_seed,
                      void* stream);
+/* Head-width-parameterised forms of gget_op_rope, the attention forward / backward and gget_op_attn_probs: head_dim 64 or 32 (any other
+ * width, a NULL operand, B, S or H <= 0, half a key range, or row_base together with ranges: error 2, "unsupported head_dim" for the width,
+ * nothing is launched).  qkv is [rows, 3 * H * head_dim] bf16 with q and k ALREADY rotated (the engine's layout); the tables of the backward
+ * ([max_pos][head_dim / 2]) only rotate dq / dk back, NULL tables = no rotation.  Key restriction: key_len (padded layout), key_len +
+ * row_base (var-len token layout), key_lo / key_hi (packed rows; key_len is ignored then), causal.  lse fp32 [B, H, S], delta_ws fp32
+ * [B, H, S] workspace.  head_dim 64 forwards to the kernels of the entries above with the same arguments (qk_rotated = 1): same bits.
+ * head_dim 32 (csrc/attention32.hip, H = hidden / 32) keeps the numerical contract above with x = <q, k> * 32^-1/2: the scale is not a
+ * power of two and is applied as ONE fp32 constant fl(32^-1/2 * log2 e) inside p = exp2(fma(s, c, -m2)) (forward and every recomputation
+ * of p; lse stays the natural log) and as the fp32 constant fl(32^-1/2) on dS; delta is sum_k m p dP in fp32 from the recomputed p and dP
+ * (a first walk of the dQ kernel over the row's key tiles; `out` is not read), left in delta_ws for the dK / dV kernel; the dropout mask is the same counter hash keyed by (seed, b * H + h, q, k >> 1); the pad-row rule is the one above; no
+ * atomics.  gget_op_rope_hd at width 32 pairs channel j with j + 16 (hf apply_rotary_pos_emb) in place on bf16 rows, fp32 arithmetic, one
+ * rounding.  gget_op_rope_f32_hd (head_dim 32 only) is the engine's form: src fp32 [B S, 3 d] - the q | k | v projection's fp32
+ * accumulators, written by the GEMM's fp32 slab epilogue - -> bf16 qkv with the q and k columns rotated and v copied, each element
+ * rounded ONCE: the cast points of the 64-wide projection, whose RoPE epilogue rotates the accumulators before their rounding. */
+int gget_op_rope_f32_hd(const float* src, void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B, int S,
+                        int H, int head_dim, void* stream);
+int gget_op_rope_hd(void* qkv, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, int B, int S, int H, int head_dim,
+                    int inverse, void* stream);
+int gget_op_attn_fwd_hd(const void* qkv, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo, const int32_t* key_hi,
+                        void* out, float* lse, int B, int S, int H, int head_dim, int causal, float dropout_p, uint32_t dropout_seed,
+                        void* stream);
+int gget_op_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_len, const int32_t* row_base,
+                        const int32_t* key_lo, const int32_t* key_hi, void* dqkv, float* delta_ws, int B, int S, int H, int head_dim,
+                        int causal, const float* cos_tab, const float* sin_tab, const int64_t* position_ids, float dropout_p,
+                        uint32_t dropout_seed, void* stream);
+int gget_op_attn_probs_hd(const void* qkv, const float* lse, const int32_t* key_len, const int32_t* row_base, const int32_t* key_lo,
+                          const int32_t* key_hi, void* out, int B, int S, int H, int head_dim, int causal, float dropout_p,
+                          uint32_t dropout_seed, void* stream);
 /* replaces: the `.to(device)` calls at the top of the reference's step (src/utils/training_utils.py:17-26) for a batch that sits in PINNED
  * host memory (hipHostMalloc / torch pin_memory: device-mapped): a kernel on `stream` reads it over the host link into dst_dev.  Stays in
  * the compute queue - an in-stream hipMemcpyAsync from pinned memory is a copy-engine job whose dependencies the runtime resolves on the

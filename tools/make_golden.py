@@ -154,7 +154,7 @@ CLIP = 1.0
 def run_case(name, kind, skw, bkw, ikw, classes):
     PT, FT, Cfg = classes
     size = ikw.pop("size", "tiny")
-    big = size != "tiny"
+    big = size not in ("tiny", "tiny6")     # (tiny6: d128 / L6 with 32-wide heads, tools/make_golden_hd32.py - full gradients fit)
     spec = spec_mod.spec_from_size(size, kind=spec_mod.KIND_PRETRAIN if kind == "pt" else spec_mod.KIND_TASK, **skw)
     state = weights_mod.make_state_dict(spec, seed=100 + bkw["seed"], **ikw)
     names = list(state.keys())
